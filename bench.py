@@ -20,6 +20,9 @@ synchronous call per step.
                           is timed too and attached as "weak".  At N = 1 the two are the same run.
 --scaling strong | weak   that reading only.
 
+--dump-outputs DIR: after the timed steps, what the last one returned (packed block streams, block lengths, total) goes to DIR/*.npy
+(dump_outputs); the seeded input is the same from run to run, so two builds can be compared output for output.
+
 Prints ONE JSON line on rank 0 (contract in the task statement): metric / value (whole-job MiB/s) / roofline (the kernel with
 the longest launch vs the HBM roof, every kernel's figure in roofline_kernels) / cpu_baseline (the CPU oracle = C restatement of
 the reference, -O3 -march=native, timed on the host cores over a bounded sample, two legs) / decode (device round trip of EVERY
@@ -38,11 +41,18 @@ sys.path.insert(0, ROOT)
 # The library asks nothing of the environment (its pipeline stages use streams of different priority levels, which HIP maps to
 # different hardware queues: INTEGRATION.md).  --hw-queues N sets GPU_MAX_HW_QUEUES=N for THIS run (it must be in the environment before
 # the HIP runtime initialises, hence the early look at argv); whatever is in effect is recorded in config.gpu_max_hw_queues.
+# At most 2: the GPUs this runs on are shared, and more hardware queues per process are not allowed there.
+MAX_HW_QUEUES = 2
 for _i, _a in enumerate(sys.argv):
-    if _a == "--hw-queues" and _i + 1 < len(sys.argv) and int(sys.argv[_i + 1]) > 0:
-        os.environ["GPU_MAX_HW_QUEUES"] = sys.argv[_i + 1]
-    elif _a.startswith("--hw-queues=") and int(_a.split("=")[1]) > 0:
-        os.environ["GPU_MAX_HW_QUEUES"] = _a.split("=")[1]
+    _q = None
+    if _a == "--hw-queues" and _i + 1 < len(sys.argv):
+        _q = sys.argv[_i + 1]
+    elif _a.startswith("--hw-queues="):
+        _q = _a.split("=", 1)[1]
+    if _q is not None and int(_q) > MAX_HW_QUEUES:
+        raise SystemExit("bench.py: --hw-queues %s: at most %d" % (_q, MAX_HW_QUEUES))
+    if _q is not None and int(_q) > 0:
+        os.environ["GPU_MAX_HW_QUEUES"] = _q
 
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
 NSETS = 4                # output buffer sets of a regime = the deepest submit / wait pipeline (W3_MAX_JOBS)
@@ -184,6 +194,34 @@ def cpu_baseline(name, sample, block_size, budget_s=8.0):
             "legs": legs}, out, lens, n2
 
 
+DUMP_BYTES = 64_000_000   # --dump-outputs: all files together
+
+
+def dump_outputs(dirname, d_out, d_lens, total, nb):
+    """--dump-outputs: the arrays a caller of the timed path receives from one step — the packed block streams, the per-block
+    compressed lengths and the total — as .npy files.  Blocks are independent: when the whole output does not fit in DUMP_BYTES, whole
+    blocks are taken in a fixed seeded order until it is full (the same blocks for the same output), and blocks.npy names them.
+        blocks.npy      float64[k]  the dumped blocks' indices, ascending (every block when they fit)
+        block_lens.npy  float64[k]  their compressed lengths in bytes
+        streams.npy     float32[m]  their streams' bytes, concatenated in block order (m = sum of block_lens)
+        total.npy       float64[1]  the compressed byte count of the whole output, every block included"""
+    import numpy as np
+    import torch
+    lens = d_lens[:nb].cpu().numpy().astype(np.int64)
+    offs = np.concatenate(([0], np.cumsum(lens)))
+    assert offs[-1] == total, "block lengths (%d bytes) do not add up to the total (%d)" % (offs[-1], total)
+    order = np.random.default_rng(0).permutation(nb)
+    cost = np.cumsum(4 * lens[order] + 16)   # a block's bytes as float32 + its index and length as float64
+    blocks = np.sort(order[cost <= DUMP_BYTES - 4096])   # (4096: the four .npy headers)
+    streams = torch.cat([d_out[int(offs[b]):int(offs[b + 1])] for b in blocks] + [d_out[:0]]).cpu().numpy()
+    os.makedirs(dirname, exist_ok=True)
+    files = {"blocks": blocks.astype(np.float64), "block_lens": lens[blocks].astype(np.float64), "streams": streams.astype(np.float32),
+             "total": np.array([total], dtype=np.float64)}
+    for name, arr in files.items():
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+    return {"dir": dirname, "blocks": int(len(blocks)), "of_blocks": nb, "files": sorted(name + ".npy" for name in files)}
+
+
 def launcher_command(n_gpus, argv, port):
     """The command that starts the N ranks of this bench (what the driver runs itself for N > 1)."""
     return [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n_gpus), "--master-addr", "127.0.0.1",
@@ -239,14 +277,21 @@ def parse_args(argv=None):
     ap.add_argument("--no-other-configs", action="store_true", help="skip the 3-step runs of BASELINE configs[2] / configs[4]")
     ap.add_argument("--quick", action="store_true", help="= --no-cpu-baseline --no-ref-model --no-decode --no-other-configs --no-host-path (profiling runs)")
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--hw-queues", type=int, default=0, help="GPU_MAX_HW_QUEUES for this run (0 = leave the environment alone: HIP's default of 4 per priority level)")
+    ap.add_argument("--hw-queues", type=int, default=0, help="GPU_MAX_HW_QUEUES for this run, at most %d (0 = leave the environment alone: HIP's default of 4 per priority level)" % MAX_HW_QUEUES)
     ap.add_argument("--no-host-path", action="store_true", help="skip the PCIe-inclusive legs (host_path: w3_encode_blocks / w3_encode_host_submit from pinned and pageable memory)")
     ap.add_argument("--force-exchange", action="store_true", help="run the RCCL exchange step even with 1 rank (rehearsal)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI, one GPU per rank (the measured path).  gloo = REHEARSAL of the multi-rank control flow on a box with "
                          "fewer GPUs than ranks: the ranks share the GPUs there are (rank r on device r mod count) and the exchange is staged through host "
                          "memory; its numbers mean nothing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step to DIR/<name>.npy (float32 / float64, at most %d MB; "
+                         "above that a fixed, seeded sample of whole blocks): two builds can be compared output for output" % (DUMP_BYTES // 10**6))
     a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1 (the timed region holds exactly that many steps)")
+    if a.warmup < 0:
+        ap.error("--warmup must not be negative")
     if a.quick:
         a.no_cpu_baseline = a.no_ref_model = a.no_decode = a.no_other_configs = a.no_host_path = True
     return a
@@ -503,6 +548,7 @@ def main():
     if args.variant:
         ctx.set_variant(*args.variant.split(","))
 
+    dumped = None
     readings = ["strong", "weak"] if (args.scaling == "both" and world > 1) else ["strong" if args.scaling == "both" else args.scaling]
     results = {}
     rg = None
@@ -516,6 +562,10 @@ def main():
             env["force_depth"] = 3   # (experiment: free-running jobs beyond 12,288 blocks)
         pipeline = min(pipeline, max(ctx.max_in_flight(rg.n, bs, model), env.get("force_depth", 0))) if pipeline > 1 else pipeline
         dt, acc = rg.timed(ctx, model, args.steps, args.warmup, pipeline)
+        if args.dump_outputs and rank == 0 and rd == readings[0]:
+            # (before anything below encodes into the same buffers again)
+            k = rg.last_buf
+            dumped = dump_outputs(args.dump_outputs, rg.d_outs[k], rg.d_lenss[k], int(rg.d_totals[k].item()), rg.nb)
         results[rd] = {"dt": dt, "acc": acc, "n": rg.n, "n_global": rg.n_global, "nb": rg.nb, "pipeline": pipeline,
                        "ratio": int(rg.d_totals[rg.last_buf].item()) / max(rg.n, 1),
                        "exchange_totals": list(rg.gathered) if rg.gathered else None}
@@ -731,6 +781,8 @@ def main():
         if decode:
             res["decode"] = decode
             res["config"]["decode"] = {"value": decode["value"], "unit": "MiB/s", "roundtrip_all_blocks": decode["roundtrip_all_blocks"]}
+        if dumped:
+            res["outputs_dumped"] = dumped
         if host_path:
             res["host_path"] = host_path
             res["config"]["host_path"] = {k: host_path[k] for k in ("calls_in_flight_pinned_MiBps", "one_call_pinned_MiBps", "one_call_pageable_MiBps", "h2d_pinned_ms", "d2h_pinned_ms") if k in host_path}

@@ -188,8 +188,10 @@ def main():
     ap.add_argument("--no-resident", action="store_true")
     ap.add_argument("--tune", type=int, default=0, help="W3_OPT_TUNE (bit 16 = 65536: the copies on two streams of their own)")
     ap.add_argument("--churn", type=int, default=0, help="contexts created, used and closed before the measured one")
-    ap.add_argument("--hw-queues", type=int, default=0, help="GPU_MAX_HW_QUEUES for this run (0 = leave the environment alone)")
+    ap.add_argument("--hw-queues", type=int, default=0, help="GPU_MAX_HW_QUEUES for this run, at most 2 (0 = leave the environment alone)")
     a = ap.parse_args()
+    if a.hw_queues > 2:
+        ap.error("--hw-queues: at most 2 (the GPUs this runs on are shared)")
     if a.hw_queues:
         os.environ["GPU_MAX_HW_QUEUES"] = str(a.hw_queues)   # (before anything initialises the HIP runtime)
     res = measure(a.model, int(a.bytes), chunks=[int(c) for c in a.chunks.split(",")], calls=a.calls, pageable=not a.no_pageable, resident=not a.no_resident, tune=a.tune, churn=a.churn)
