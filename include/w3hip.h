@@ -138,17 +138,27 @@ enum {
                            block, no table; default: the replay below 7,000 blocks, k_slot from there on), 1024 = decode on the
                            lane-per-block kernels only (default: sixteen lanes per block where k_decode_spec applies).  0 = defaults.
                            32 = FAULT INJECTION (test hook of the sampled verification): one LDS-add round of every block returns two
-                           lanes each other's value; refused (W3_E_INVALID) unless W3_OPT_VERIFY is on, so it cannot corrupt output */
+                           lanes each other's value (in the kernels W3_OPT_FAULT_KERNELS names); refused (W3_E_INVALID) unless
+                           W3_OPT_VERIFY is on, so it cannot corrupt output */
     W3_OPT_SLOT_BUDGET_MB = 8, /* cap (MiB) on the device memory one batch of slot-state hash maps may take; 0 = derive from free memory */
     W3_OPT_VERIFY = 9,  /* v = 1 (default) .. 256: after every two-phase predict that used returning LDS adds — whose lane-ordered resolution
-                           is measured, not documented by the ISA — max(16, nblocks * v / 256) sampled full-length blocks (at most v x 64 MiB of
-                           input; the sample ROTATES from call to call, over all blocks in 256 / v calls) are predicted again with ballot rounds
+                           is measured, not documented by the ISA — max(16, nblocks * v / 256) sampled blocks (at most nblocks, at most v x 64 MiB of
+                           input; the sample ROTATES from call to call) are predicted again with ballot rounds
                            and compared on the device; on a mismatch the call is re-encoded on the ballot path (w3_timing.n_lds_faults) and the
                            context stays there.  Cost at 1e9 B beside the coder: v = 1 +1.0 ms per 67.5 ms step, v = 2 +1.3, v = 4 +2.1.
                            RESIDUAL RISK, per call: a SYSTEMATIC change of the hardware's behaviour shows in any block and is caught by the
-                           first call; a fault confined to ONE block is missed with probability 1 - v/256 (and met after at most 256 / v
-                           calls); a fault that hits each block independently with probability q is missed with probability (1 - q)^S,
-                           S = the sample size.  A full in-round check needs a second returning LDS atomic per add (measured
+                           first call; a fault confined to ONE block is missed with probability 1 - S / nblocks per call.  COVERAGE BOUND
+                           (csrc/w3_verify.h, proved for every block count up to 20,000 and for series of alternating shapes and chunked
+                           calls by tests/test_verify_schedule.py): the rotation counts the context's calls PER SHAPE (n, block size) —
+                           whichever job slot a call of w3_encode_submit lands on, whatever calls of other shapes lie between them — and
+                           every block, the short last one included, is in the sample of at least one of any ceil(nblocks / S) calls of
+                           one shape (at one v): just over 256 / v calls for large inputs (259 at 1e9 B in 64 KiB blocks),
+                           ceil(nblocks / 16) for small ones (and more where the 64 MiB x v cap binds).  A w3_encode_blocks call counts
+                           once, with its own shape, and every piece it is cut into (W3_OPT_HOST_CHUNK_BLOCKS) takes that call's number:
+                           each piece's blocks are covered within ceil(piece blocks / S) such calls.  A call re-run after a detected fault
+                           or a stripe overflow keeps its number.  NOT covered: a context that cycles through more than 256 shapes (the
+                           count of a forgotten shape starts again at the context's count of calls).  A fault that hits each block independently with
+                           probability q is missed with probability (1 - q)^S, S = the sample size.  A full in-round check needs a second returning LDS atomic per add (measured
                            +4.1 % of the step for the atomics alone, and no LDS left for its shadow tables) and was not built.  Full coverage = decode the output (w3_decode_blocks_device shares no kernel with the
                            predict phase; bench.py does that for every block of its last step).  0 = off */
     W3_OPT_TUNE = 11,   /* scheduling / layout experiments (bit mask; output is identical whatever is set).  Bits 0 – 14: the submit / wait
@@ -157,8 +167,11 @@ enum {
                            the round-3 table formats / with the nibble-major ones whatever the batch size (default: by size); 19: the general k_decode_spec
                            where the instance specialised for all-raw-history models would run */
     W3_OPT_FAULT_BLOCK = 10, /* test hook, with W3_OPT_VARIANT bit 32: the one block the injected fault hits (-1 = every block, default) */
-    W3_OPT_HOST_CHUNK_BLOCKS = 12 /* w3_encode_blocks: blocks per pipelined piece of a host-buffer call (0 = default: equal pieces of at most
+    W3_OPT_HOST_CHUNK_BLOCKS = 12, /* w3_encode_blocks: blocks per pipelined piece of a host-buffer call (0 = default: equal pieces of at most
                            4,096 blocks; tests use small values to get ragged pieces) */
+    W3_OPT_FAULT_KERNELS = 13 /* test hook, with W3_OPT_VARIANT bit 32: bit mask (1 .. 7) of the kernels whose returning LDS adds the injected
+                           fault mis-orders — 1 = k_predict_small's rounds (default), 2 = k_rank_sorted's rounds, 4 = k_partition8's
+                           cursor adds (two records of one bin swap their slots in the tile: a permutation, never another index) */
 };
 enum { W3_PATH_AUTO = 0, W3_PATH_GENERIC = 1, W3_PATH_TWOPHASE = 2 };
 int         w3_ctx_set_option(w3_ctx *ctx, int opt, int64_t value);

@@ -65,7 +65,9 @@ NAMES = ["slot0", "slot1", "slot2", "slot3_tiny_table", "slot7", "slot2_hashmap_
 
 
 
-def check(ctx, oracle, name, data, bs, decode=True):
+def check(ctx, oracle, name, data, bs, decode=True, variant=()):
+    """`variant`: W3_OPT_VARIANT names every encode of the check runs under (the context is left on them; its other variants are
+    added to them and taken off again)."""
     dev, orc = pair(oracle, name)
     out, lens = ctx.encode_blocks(dev(), data, bs)
     want, wlens = oracle.encode_blocks(orc(), data, bs, nthreads=8)
@@ -76,12 +78,12 @@ def check(ctx, oracle, name, data, bs, decode=True):
         # k_slot (hash map in HBM, the form for many blocks) and the lane-per-block k_cm must agree with it
         assert ctx.timing()["path"] == 2, name
         if "slot" in name or "full_cm" in name:
-            ctx.set_variant("slot_table")
+            ctx.set_variant(*variant, "slot_table")
             try:
                 out3, lens3 = ctx.encode_blocks(dev(), data, bs)
                 assert ctx.timing()["path"] == 2
             finally:
-                ctx.set_variant()
+                ctx.set_variant(*variant)
             assert lens3.tolist() == wlens.tolist() and out3.tobytes() == want.tobytes(), name + " (k_slot)"
         ctx.set_path("generic")
         try:
@@ -92,11 +94,11 @@ def check(ctx, oracle, name, data, bs, decode=True):
         assert lens2.tolist() == wlens.tolist() and out2.tobytes() == want.tobytes(), name + " (k_cm)"
     if decode:
         assert ctx.decode_blocks(dev(), out, lens, bs, len(data)).tobytes() == bytes(data), name
-        ctx.set_variant("decode_lane")   # the lane-per-block decoder (k_cm_nl), where the default is k_decode_spec (sixteen lanes per block)
+        ctx.set_variant(*variant, "decode_lane")   # the lane-per-block decoder (k_cm_nl), where the default is k_decode_spec (sixteen lanes per block)
         try:
             assert ctx.decode_blocks(dev(), out, lens, bs, len(data)).tobytes() == bytes(data), name + " (lane-per-block decoder)"
         finally:
-            ctx.set_variant()
+            ctx.set_variant(*variant)
         if bs < 262144:                  # (256 KiB blocks: a decode is a latency chain of 2 M steps per block — the two-bit form is covered at the smaller sizes)
             ctx.set_tune(16384)          # k_decode_spec with two bits per speculated group (a tested variant)
             try:

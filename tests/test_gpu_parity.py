@@ -340,7 +340,8 @@ def test_sampled_verification_catches_misordered_lds_adds(oracle):
 
 def test_sampled_verification_rotates_over_all_blocks(oracle):
     """The sample is max(16, nblocks / 256) blocks and ROTATES from call to call: a fault confined to ONE block that the first
-    call's sample misses is met after a bounded number of calls (nblocks / sample).  Until then the corrupted stream goes out —
+    call's sample misses is met after a bounded number of calls (ceil(nblocks / sample): w3_verify.h; every block, whatever the block
+    count, tests/test_gpu_lds_fault.py).  Until then the corrupted stream goes out —
     the coverage limit of a sampled check, stated in w3hip.h; the full check is a decode of the output (bench.py, test_gpu_fullsize)."""
     bs, nb = 1024, 400
     data = markov_text(bs * nb, seed=29)
@@ -349,7 +350,7 @@ def test_sampled_verification_rotates_over_all_blocks(oracle):
         c.set_path("twophase")
         dev, orc = pair(oracle, "order0")
         want, wlens = oracle.encode_blocks(orc(), data, bs, nthreads=8)
-        gap = nb // 16                      # 16 sampled blocks, 25 apart; call k samples blocks 25 s + (k mod 25)
+        gap = nb // 16                      # 16 sampled blocks; slot s covers blocks [25 s, 25 s + 25) and call k takes 25 s + (k mod 25)
         victim = 25 * 3 + 7                 # first in the sample at call 7
         c.set_variant("inject_lds_fault")
         c.set_fault_block(victim)
@@ -566,8 +567,8 @@ def test_twophase_rejects_what_it_does_not_cover(ctx, oracle):
     check_blocks(ctx, oracle, "ordern_22_2", b"abcdefgh", 3, "twophase")
 
 
-def test_twophase_counter_saturation(ctx, oracle):
-    """Counter::update halves both counts at 65535 (counter.rs:22-25): long constant runs, incl. multiple halvings."""
+def saturation_cases():
+    """Inputs whose Counters reach 65535 and halve (counter.rs:22-25): long constant runs, incl. multiple halvings.  -> {name: (data, bs)}"""
     rng = np.random.default_rng(5)
     z = bytearray(300000)
     for k in (70000, 140000, 141000, 290000):
@@ -578,7 +579,12 @@ def test_twophase_counter_saturation(ctx, oracle):
         "aa": (b"\xaa" * 200000, 131072), "ab": (b"ab" * 150000, 262144),
         "noisy_zero": (bytes(np.where(rng.random(262144) < 0.0005, 1, 0).astype(np.uint8)), 262144),
     }
-    for cname, (data, bs) in cases.items():
+    return cases
+
+
+def test_twophase_counter_saturation(ctx, oracle):
+    """Counter::update halves both counts at 65535 (counter.rs:22-25): long constant runs, incl. multiple halvings."""
+    for cname, (data, bs) in saturation_cases().items():
         for name in ("order0", "best012", "main_default"):
             check_blocks(ctx, oracle, name, data, bs, "twophase")
 

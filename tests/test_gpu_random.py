@@ -41,6 +41,12 @@ def test_random_shapes(ctx, oracle, case):  # noqa: F811
     out, lens = check_blocks(ctx, oracle, name, data, bs, "twophase")
     # and back: k_decode_spec (sixteen lanes per block) and the lane-per-block decoder must both return the input
     assert decode_both(ctx, pair(oracle, name)[0](), out, lens, bs, len(data)).tobytes() == data
+    if case % 4 == 0:   # every fourth case also on the ballot path (ballot rounds, 4-bit partitions): where a context goes after an LDS-add fault
+        ctx.set_variant("no_lds_atomics")
+        try:
+            check_blocks(ctx, oracle, name, data, bs, "twophase")
+        finally:
+            ctx.set_variant()
 
 
 CM_MODELS = ["slot1", "slot2", "slot_mix", "o012_apm", "apm_chain4", "full_cm_small_tables", "apm1_order0_r3", "slot7"]

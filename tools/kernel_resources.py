@@ -25,7 +25,7 @@ def main():
             rows[cur] = {}
             continue
         for k, short in keys.items():
-            m = re.search(r"remark: .*\s" + re.escape(k) + r": (\d+)", line)
+            m = re.search(r"remark: .*\s(?:Total)?" + re.escape(k) + r": (\d+)", line)   # (gfx950: "TotalSGPRs")
             if m and cur:
                 rows[cur][short] = int(m.group(1))
     names = subprocess.run(["c++filt"], input="\n".join(rows), capture_output=True, text=True).stdout.splitlines()

@@ -83,6 +83,15 @@ class Context:
         """Test hook (with set_variant("inject_lds_fault")): the one block the injected fault hits; -1 = every block."""
         self._chk(self.lib.w3_ctx_set_option(self.h, L.W3_OPT_FAULT_BLOCK, int(block)))
 
+    def set_fault_kernels(self, *names):
+        """Test hook (with set_variant("inject_lds_fault")): the kernels whose returning LDS adds the injected fault mis-orders, by
+        name: predict_small (the default), rank_sorted, partition8.  No names = the default."""
+        bits = {"predict_small": 1, "rank_sorted": 2, "partition8": 4}
+        v = 0
+        for nm in names:
+            v |= bits[nm]
+        self._chk(self.lib.w3_ctx_set_option(self.h, L.W3_OPT_FAULT_KERNELS, v or 1))
+
     def set_slot_budget_mb(self, mb=0):
         self._chk(self.lib.w3_ctx_set_option(self.h, L.W3_OPT_SLOT_BUDGET_MB, int(mb)))
 

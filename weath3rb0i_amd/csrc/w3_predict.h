@@ -69,9 +69,12 @@ struct PredictArgs {
     uint32_t hbits;         // H = bits_in_context - 3
     uint32_t maxseg;        // k_rank_sorted: rounds with more groups than this take the ballot path (W3_ATOMIC_MAXSEG)
     uint32_t dbg_flags;      // bit0 = skip the stream stores (timing experiments only); bit1 = ballot rounds only (no LDS atomics);
-                             // bit3 = FAULT INJECTION for the tests of the sampled verification: one returning add of every block hands two lanes each other's value
+                             // bits 3 / 4 / 5 = FAULT INJECTION for the tests of the sampled verification (W3_OPT_FAULT_KERNELS) in k_predict_small /
+                             // k_rank_sorted / k_partition8 (bits 4 and 5 select those kernels' FAULT instances: launch_rank, launch_partition8):
+                             // one round of returning adds per block hands pairs of lanes each other's result (a mis-ordered add; in
+                             // k_partition8 only between lanes of the same bin, so the tile's slots stay a permutation)
     unsigned long long *dbg; // optional: per-phase s_memtime sums (diagnostic builds/runs only; never read by kernels)
-    uint32_t fault_block;    // dbg_flags bit3: the one block the injected fault hits, or 0xFFFFFFFF = every block
+    uint32_t fault_block;    // dbg_flags bits 3 - 5: the one block the injected fault hits, or 0xFFFFFFFF = every block
 };
 
 #define W3_STAMP(slot)                                                                         \
@@ -285,6 +288,9 @@ __device__ __forceinline__ uint4 mix_p(uint4 cur, uint4 nw) {
     return make_uint4(mix_pair(cur.x, nw.x), mix_pair(cur.y, nw.y), mix_pair(cur.z, nw.z), mix_pair(cur.w, nw.w));
 }
 
+#define W3_HD __host__ __device__ __forceinline__
+#include "w3_verify.h"   // the sampled verification's schedule (twophase_verify, k_gather_blocks, k_compare_blocks; also run by tests/test_verify_schedule.py)
+#undef W3_HD
 #include "w3_window.h"   // window_head / load_window / wave_window: the input-window loads (plain C++, also compiled for the host by tests/test_window_loads.py)
 
 // ---------------------------------------------------------------------------
@@ -593,7 +599,8 @@ __device__ __forceinline__ void wave_excl_scan_256(uint32_t *cnt, uint32_t *excl
     if (excl2) { excl2[4 * lane] = base; excl2[4 * lane + 1] = base + c0; excl2[4 * lane + 2] = base + c0 + c1; excl2[4 * lane + 3] = base + c0 + c1 + c2; }
 }
 
-template <int MODE, int NW = 1>
+// FAULT: the instance with the test hook of the sampled verification (dbg_flags bit 5; the production instances carry no trace of it)
+template <int MODE, int NW = 1, bool FAULT = false>
 __global__ void __launch_bounds__(64 * NW) k_partition8(PredictArgs a) {
     __shared__ uint2 tile_[NW][W3_P8_TILE];
     __shared__ uint32_t cnt_[NW][4][256];   // gcur, tcnt, tstart, tcur
@@ -684,7 +691,14 @@ __global__ void __launch_bounds__(64 * NW) k_partition8(PredictArgs a) {
 #pragma unroll
             for (uint32_t r = 0; r < W3_P8_ROUNDS; r++) {
                 if (r * 64u + lane < tlen) {
-                    const uint32_t slot = __hip_atomic_fetch_add(&tcur[(rec[r].y >> KSH) & 0xFFu], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    uint32_t slot = __hip_atomic_fetch_add(&tcur[(rec[r].y >> KSH) & 0xFFu], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    // (test hook: a mis-ordered add in round 1 of the block's first tile — all 64 lanes active there; two lanes
+                    //  of the same bin exchange their slots, so the tile's slots stay a permutation and the bin runs stay in place)
+                    if (FAULT && r == 1u && t0 == 0u && tlen >= 128u && (a.fault_block == 0xFFFFFFFFu || a.fault_block == b)) {
+                        const uint32_t d = (rec[r].y >> KSH) & 0xFFu;
+                        const uint32_t d_x = (uint32_t)__shfl_xor((int)d, 1, 64), slot_x = (uint32_t)__shfl_xor((int)slot, 1, 64);
+                        if (d_x == d) slot = slot_x;
+                    }
                     tile[slot] = rec[r];
                 }
             }
@@ -781,7 +795,8 @@ __global__ void __launch_bounds__(64 * NW) k_partition8(PredictArgs a) {
 // writes every 128-byte line receives merge (3.2x cheaper than with 4096 blocks live; see
 // profiles/r1_ubench_partial_line_merge_vs_footprint.txt).
 // PF: rounds per operand batch (8: 12 KiB of LDS per wavefront; 4: 10 KiB, so that EIGHT wavefronts fit the half of a CU)
-template <int NBYTES, int NW = 1, int PF = W3_PF>
+// FAULT: the instance with the test hook of the sampled verification (dbg_flags bit 4; the production instances carry no trace of it)
+template <int NBYTES, int NW = 1, int PF = W3_PF, bool FAULT = false>
 __global__ void __launch_bounds__(64 * NW) k_rank_sorted(PredictArgs a) {
     __shared__ uint32_t tbl_[NW][8 * 256];
     __shared__ uint2 st_r_[NW][PF * 64];   // record staging (one batch of rounds)
@@ -896,6 +911,9 @@ __global__ void __launch_bounds__(64 * NW) k_rank_sorted(PredictArgs a) {
                     carried = false;
                 }
                 __asm__ volatile("" ::: "memory");
+                if constexpr (FAULT) {   // (test hook: a mis-ordered add in the round that holds element 64 of the block's sorted order)
+                    if (64u - (lo + base) < 64u && (a.fault_block == 0xFFFFFFFFu || a.fault_block == b)) v[0] = (uint32_t)__shfl_xor((int)v[0], 1, 64);
+                }
 #pragma unroll
                 for (int j = 0; j < 8; j++) p[j] = counter_p_packed(v[j]);
                 exact = atomic_round_hot(v);
@@ -1017,19 +1035,21 @@ __global__ void __launch_bounds__(64) k_huffkeys_fix(HuffKeyArgs a) {
 // ---------------------------------------------------------------------------
 // Sampled verification of the LDS-add rounds (w3_twophase.h, twophase_verify): S blocks of the input are gathered into a
 // compact buffer, predicted a second time with the ballot rounds (exact by construction), and the streams compared.
-// Sampled block s = block s * nb_full / S + rot (full-length blocks only; rot < nb_full / S rotates the sample from call to call,
-// so that after nb_full / S calls every block has been in it once).
+// Sample slot s holds block verify_block(rot, s, nb, S) (w3_verify.h: every block within ceil(nb / S) calls); only the last slot can
+// hold the input's short last block, so the sample is S - 1 full blocks and then one of its real length.
 // ---------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_gather_blocks(const uint8_t *in, uint32_t bs, uint32_t nb_full, uint32_t S, uint32_t rot, uint8_t *out) {
+__global__ void __launch_bounds__(256) k_gather_blocks(const uint8_t *in, uint64_t n, uint32_t bs, uint32_t nb, uint32_t S, uint32_t rot, uint8_t *out) {
     const uint32_t s = blockIdx.y;
-    const uint64_t src = (uint64_t)((uint64_t)s * nb_full / S + rot) * bs;
-    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < bs; i += gridDim.x * 256u) out[(uint64_t)s * bs + i] = in[src + i];
+    const uint64_t src = (uint64_t)verify_block(rot, s, nb, S) * bs;
+    const uint32_t len = (uint32_t)(n - src < bs ? n - src : bs);
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < len; i += gridDim.x * 256u) out[(uint64_t)s * bs + i] = in[src + i];
 }
-__global__ void __launch_bounds__(256) k_compare_blocks(const uint4 *main_p, const uint4 *ver_p, uint32_t bs, uint32_t nb_full, uint32_t S, uint32_t rot, uint32_t *mismatch) {
+__global__ void __launch_bounds__(256) k_compare_blocks(const uint4 *main_p, const uint4 *ver_p, uint64_t n, uint32_t bs, uint32_t nb, uint32_t S, uint32_t rot, uint32_t *mismatch) {
     const uint32_t s = blockIdx.y;
-    const uint64_t src = (uint64_t)((uint64_t)s * nb_full / S + rot) * bs;
+    const uint64_t src = (uint64_t)verify_block(rot, s, nb, S) * bs;
+    const uint32_t len = (uint32_t)(n - src < bs ? n - src : bs);
     uint32_t bad = 0;
-    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < bs; i += gridDim.x * 256u) {
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < len; i += gridDim.x * 256u) {
         const uint4 x = main_p[src + i], y = ver_p[(uint64_t)s * bs + i];
         bad |= (x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w);
     }

@@ -101,8 +101,9 @@ struct TwoPhaseWs {
     uint32_t acc_limit = 46;   // test hook: lower values force the fast coder's fallback
     uint32_t variant = 0;      // W3_VAR_* (W3_OPT_VARIANT)
     uint32_t slot_budget_mb = 0;   // W3_OPT_SLOT_BUDGET_MB: cap on the slot leaves' hash-map batch (0 = from the free device memory)
-    uint32_t verify_calls = 0; // rotates the verification's sample
+    uint64_t verify_calls = 0; // the call's number for the sample's rotation (w3_verify.h: counted per shape by the context)
     uint32_t fault_block = 0xFFFFFFFFu;   // W3_OPT_FAULT_BLOCK (with W3_VAR_INJECT_LDS_FAULT)
+    uint32_t fault_kernels = 1u;          // W3_OPT_FAULT_KERNELS: which kernels the injected fault hits (1 k_predict_small, 2 k_rank_sorted, 4 k_partition8)
     int verify = 1;            // W3_OPT_VERIFY: sampled re-prediction with ballot rounds after every predict phase that used LDS-add rounds
     TwoPhaseWs *vws = nullptr; // workspace of that re-prediction (owned)
     void *vin = nullptr; size_t vin_cap = 0;   // the sampled blocks, gathered
@@ -265,6 +266,19 @@ static inline bool twophase_lds_order_ok(TwoPhaseWs &ws, hipStream_t s) {
     return ok;
 }
 
+// k_partition8 / k_rank_sorted, or their instances with the fault hook of the sampled verification's tests (W3_OPT_FAULT_KERNELS bits
+// 4 / 2: PredictArgs::dbg_flags bits 5 / 4) — a separate instance, so that the production kernels carry no trace of the hook
+template <int MODE, int NW>
+static inline void launch_partition8(bool fault, dim3 grid, hipStream_t s, const w3::PredictArgs &pa) {
+    if (fault) hipLaunchKernelGGL((w3::k_partition8<MODE, NW, true>), grid, dim3(64 * NW), 0, s, pa);
+    else hipLaunchKernelGGL((w3::k_partition8<MODE, NW>), grid, dim3(64 * NW), 0, s, pa);
+}
+template <int NBYTES, int NW, int PF>
+static inline void launch_rank(bool fault, dim3 grid, hipStream_t s, const w3::PredictArgs &pa) {
+    if (fault) hipLaunchKernelGGL((w3::k_rank_sorted<NBYTES, NW, PF, true>), grid, dim3(64 * NW), 0, s, pa);
+    else hipLaunchKernelGGL((w3::k_rank_sorted<NBYTES, NW, PF>), grid, dim3(64 * NW), 0, s, pa);
+}
+
 // need_P: also merge the leaves' streams into ws.P (k_mix).  The default coder (k_coder_x3) mixes on the fly
 // and needs no P for up to 4 live leaves.
 // The predict phase in two halves (the submit / wait pipeline puts the previous call's APM stage between them):
@@ -419,7 +433,7 @@ static inline int twophase_predict_a(TwoPhaseWs &ws, hipStream_t s, const Parsed
         pa.maxseg = W3_ATOMIC_MAXSEG;
         if (const char *ev_ = w3_tune_env("W3_ATOMIC_MAXSEG")) pa.maxseg = (uint32_t)std::max(0, atoi(ev_));   // tuning hook
         if (!lds_atomics) pa.dbg_flags |= 2u;
-        if (ws.variant & W3_VAR_INJECT_LDS_FAULT) pa.dbg_flags |= 8u;
+        if (ws.variant & W3_VAR_INJECT_LDS_FAULT) pa.dbg_flags |= (ws.fault_kernels & 7u) << 3;   // bits 3 / 4 / 5: see PredictArgs::dbg_flags
         pa.fault_block = ws.fault_block;
         bytes += n * 17;
         if (c == LEAF_SMALL_AC) {
@@ -495,10 +509,11 @@ static inline int twophase_predict_a(TwoPhaseWs &ws, hipStream_t s, const Parsed
             const uint32_t grid_p8h = std::min<uint32_t>((nb + W3_NW_PART - 1) / W3_NW_PART, 2 * W3_HALF_CU_GRID);
             const bool p8h = p8 && ws.half_cu && (ws.tune & 32u);   // W3_OPT_TUNE bit 5: the first predict half in half-CU shapes too
             if (ev && w < 4) (void)hipEventRecord(ev[2 * (W3_EV_PART0 + w)], sp);
-            if (c == LEAF_WIDE1 && p8h) hipLaunchKernelGGL((w3::k_partition8<1, W3_NW_PART>), dim3(grid_p8h), dim3(64 * W3_NW_PART), 0, sp, pa);
-            else if (chained && p8h) hipLaunchKernelGGL((w3::k_partition8<3, W3_NW_PART>), dim3(grid_p8h), dim3(64 * W3_NW_PART), 0, sp, pa);
-            else if (c == LEAF_WIDE1 && p8) hipLaunchKernelGGL(w3::k_partition8<1>, dim3(grid_wide), dim3(64), 0, sp, pa);
-            else if (chained && p8) hipLaunchKernelGGL(w3::k_partition8<3>, dim3(grid_wide), dim3(64), 0, sp, pa);
+            const bool f8 = (pa.dbg_flags & 32u) != 0u;   // (the instance with the fault hook: tests of the sampled verification)
+            if (c == LEAF_WIDE1 && p8h) launch_partition8<1, W3_NW_PART>(f8, dim3(grid_p8h), sp, pa);
+            else if (chained && p8h) launch_partition8<3, W3_NW_PART>(f8, dim3(grid_p8h), sp, pa);
+            else if (c == LEAF_WIDE1 && p8) launch_partition8<1, 1>(f8, dim3(grid_wide), sp, pa);
+            else if (chained && p8) launch_partition8<3, 1>(f8, dim3(grid_wide), sp, pa);
             else if (c == LEAF_WIDE1) hipLaunchKernelGGL(w3::k_partition<1>, dim3(grid_wide), dim3(64), 0, sp, pa);
             else if (chained) hipLaunchKernelGGL(w3::k_partition<3>, dim3(grid_wide), dim3(64), 0, sp, pa);
             else hipLaunchKernelGGL(w3::k_partition<2>, dim3(grid_wide), dim3(64), 0, sp, pa);
@@ -554,17 +569,19 @@ static inline int twophase_predict_b(TwoPhaseWs &ws, hipStream_t s, const Parsed
     for (int w = 0; w < n_def; w++) {
         if (forked) (void)hipStreamWaitEvent(s, ws.ev_join[n_def - 1], 0);   // every leaf's records are sorted
         if (ev) (void)hipEventRecord(ev[2 * (W3_EV_RANK0 + w)], s);
+        const bool w1 = deferred[w].cls == LEAF_WIDE1, fr = (deferred[w].pa.dbg_flags & 16u) != 0u;   // (fr: the instance with the fault hook)
+        const dim3 gr(deferred[w].grid_rank);
         if (ws.half_cu && (w == 0 || (ws.tune & (32u | 64u))) && !(ws.tune & 8u) && (ws.tune & 32768u)) {
-            if (deferred[w].cls == LEAF_WIDE1) hipLaunchKernelGGL((w3::k_rank_sorted<1, W3_NW_RANK8, 4>), dim3(deferred[w].grid_rank), dim3(64 * W3_NW_RANK8), 0, s, deferred[w].pa);
-            else hipLaunchKernelGGL((w3::k_rank_sorted<2, W3_NW_RANK8, 4>), dim3(deferred[w].grid_rank), dim3(64 * W3_NW_RANK8), 0, s, deferred[w].pa);
+            if (w1) launch_rank<1, W3_NW_RANK8, 4>(fr, gr, s, deferred[w].pa);
+            else launch_rank<2, W3_NW_RANK8, 4>(fr, gr, s, deferred[w].pa);
         } else if (ws.half_cu && (ws.tune & 32768u)) {   // the later rank kernels: single wavefronts of 10 KiB (eight beside the coder's 74 KiB)
-            if (deferred[w].cls == LEAF_WIDE1) hipLaunchKernelGGL((w3::k_rank_sorted<1, 1, 4>), dim3(deferred[w].grid_rank), dim3(64), 0, s, deferred[w].pa);
-            else hipLaunchKernelGGL((w3::k_rank_sorted<2, 1, 4>), dim3(deferred[w].grid_rank), dim3(64), 0, s, deferred[w].pa);
+            if (w1) launch_rank<1, 1, 4>(fr, gr, s, deferred[w].pa);
+            else launch_rank<2, 1, 4>(fr, gr, s, deferred[w].pa);
         } else if (ws.half_cu && (w == 0 || (ws.tune & (32u | 64u))) && !(ws.tune & 8u)) {
-            if (deferred[w].cls == LEAF_WIDE1) hipLaunchKernelGGL((w3::k_rank_sorted<1, W3_NW_RANK>), dim3(deferred[w].grid_rank), dim3(64 * W3_NW_RANK), 0, s, deferred[w].pa);
-            else hipLaunchKernelGGL((w3::k_rank_sorted<2, W3_NW_RANK>), dim3(deferred[w].grid_rank), dim3(64 * W3_NW_RANK), 0, s, deferred[w].pa);
-        } else if (deferred[w].cls == LEAF_WIDE1) hipLaunchKernelGGL(w3::k_rank_sorted<1>, dim3(deferred[w].grid_rank), dim3(64), 0, s, deferred[w].pa);
-        else hipLaunchKernelGGL(w3::k_rank_sorted<2>, dim3(deferred[w].grid_rank), dim3(64), 0, s, deferred[w].pa);
+            if (w1) launch_rank<1, W3_NW_RANK, W3_PF>(fr, gr, s, deferred[w].pa);
+            else launch_rank<2, W3_NW_RANK, W3_PF>(fr, gr, s, deferred[w].pa);
+        } else if (w1) launch_rank<1, 1, W3_PF>(fr, gr, s, deferred[w].pa);
+        else launch_rank<2, 1, W3_PF>(fr, gr, s, deferred[w].pa);
         if (ev) (void)hipEventRecord(ev[2 * (W3_EV_RANK0 + w) + 1], s);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) { err = std::string("rank launch: ") + hipGetErrorString(e); return W3_E_HIP; }
@@ -697,33 +714,29 @@ static inline int twophase_predict(TwoPhaseWs &ws, hipStream_t s, const ParsedSp
     return twophase_predict_b(ws, s, ps, d_in, n, block_size, nb, need_P, d_P, ev, tm, err);
 }
 
-#define W3_VERIFY_BLOCKS 16u   // sampled blocks per call, at least; max(this, nblocks / 256) are taken, and the sample ROTATES from call to call
-                               // (a systematic change of hardware behaviour shows in any block; a fault confined to one block is
-                               // met after at most nblocks / sample calls)
-
 // Always-on insurance for the one undocumented hardware property the default predict kernels rely on (returning LDS adds of
-// one wavefront resolve in ascending lane order: atomic_round, k_partition8).  After a predict phase that used it, up to W3_VERIFY_BLOCKS
-// evenly spaced full-length blocks (at most 64 MiB) are predicted AGAIN with the ballot rounds and 4-bit partitions — exact
-// by construction, no lane-order assumption — and every leaf's stream is compared on the device.  The main phase ran
+// one wavefront resolve in ascending lane order: atomic_round, k_partition8).  After a predict phase that used it, S sampled blocks
+// (w3_verify.h: max(W3_VERIFY_BLOCKS, nblocks * v / 256), at most v x 64 MiB; the sample rotates from call to call and takes every
+// block, the short last one included, within ceil(nblocks / S) calls) are predicted AGAIN with the ballot rounds and 4-bit partitions
+// — exact by construction, no lane-order assumption — and every leaf's stream is compared on the device.  The main phase ran
 // under the production load (all CUs, 8 waves per CU); that is the condition the per-context self-test cannot reproduce.
 // d_mismatch (device word, zeroed by the caller) counts differing waves; the caller reads it with its status flags
 // and, when it is not zero, re-encodes the whole call on the ballot path and keeps the context there.
 static inline int twophase_verify(TwoPhaseWs &ws, hipStream_t s, const ParsedSpec &ps, const uint8_t *d_in, size_t n, size_t block_size,
                                   uint32_t nb, uint32_t *d_mismatch, std::string &err) {
-    if (!ws.verify || !ws.used_lds_atomics) return W3_OK;
-    const uint32_t nb_full = (uint32_t)(n / block_size);
+    if (!ws.verify || !ws.used_lds_atomics || nb == 0) return W3_OK;
     // ws.verify = v >= 1: v / 256 of the blocks (W3_OPT_VERIFY; 1 = the default sample), at most 64 MiB x v of input
-    const uint64_t vv = (uint64_t)std::max(1, ws.verify);
-    uint32_t S = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(nb_full, std::max<uint64_t>(W3_VERIFY_BLOCKS, nb_full * vv / 256u)), std::max<uint64_t>(1, vv * (64ull << 20) / block_size));
-    size_t vn = (size_t)S * block_size;
-    const uint32_t gap = S ? nb_full / S : 0u, rot = gap ? ws.verify_calls++ % gap : 0u;
+    const uint32_t S = w3::verify_sample_size(nb, block_size, (uint32_t)std::max(1, ws.verify));
+    const uint32_t rot = w3::verify_rotation(ws.verify_calls, nb, S);
+    const uint64_t last_off = (uint64_t)w3::verify_block(rot, S - 1u, nb, S) * block_size;   // only the last slot can hold the short last block
+    const size_t vn = (size_t)(S - 1u) * block_size + (size_t)std::min<uint64_t>(block_size, n - last_off);
     const uint8_t *vsrc = nullptr;
     int rc;
-    if (nb_full == 0) { S = 1; vn = n; vsrc = d_in; (void)nb; }   // a single short block: verify it whole, in place
+    if (nb == 1) vsrc = d_in;   // a single block: verify it whole, in place
     else {
         if ((rc = tp_ensure(ws.vin, ws.vin_cap, vn, err))) return rc;
         hipLaunchKernelGGL(w3::k_gather_blocks, dim3(std::min<uint32_t>((uint32_t)((block_size + 255) / 256), 64u), S), dim3(256), 0, s,
-                           d_in, (uint32_t)block_size, nb_full, S, rot, (uint8_t *)ws.vin);
+                           d_in, (uint64_t)n, (uint32_t)block_size, nb, S, rot, (uint8_t *)ws.vin);
         vsrc = (const uint8_t *)ws.vin;
     }
     if (!ws.vws) ws.vws = new TwoPhaseWs();
@@ -745,10 +758,9 @@ static inline int twophase_verify(TwoPhaseWs &ws, hipStream_t s, const ParsedSpe
     vps.n_huff = ps.n_huff; vps.huff = ps.huff;
     if (vps.n_leaves == 0) return W3_OK;
     if ((rc = twophase_predict(v, s, vps, vsrc, vn, block_size, (uint32_t)((vn + block_size - 1) / block_size), false, nullptr, nullptr, nullptr, err))) return rc;
-    const uint32_t cmp_bs = nb_full ? (uint32_t)block_size : (uint32_t)n;
     for (int k = 0; k < nmap; k++)
-        hipLaunchKernelGGL(w3::k_compare_blocks, dim3(std::min<uint32_t>((cmp_bs + 255u) / 256u, 64u), S), dim3(256), 0, s,
-                           ws.mix.src[map[k]], v.mix.src[k], cmp_bs, nb_full ? nb_full : 1u, S, rot, d_mismatch);
+        hipLaunchKernelGGL(w3::k_compare_blocks, dim3(std::min<uint32_t>((uint32_t)((block_size + 255) / 256), 64u), S), dim3(256), 0, s,
+                           ws.mix.src[map[k]], v.mix.src[k], (uint64_t)n, (uint32_t)block_size, nb, S, rot, d_mismatch);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { err = std::string("verify launch: ") + hipGetErrorString(e); return W3_E_HIP; }
     return W3_OK;

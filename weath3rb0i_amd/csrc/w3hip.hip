@@ -50,6 +50,7 @@ struct JobState {
     w3_huff_table huff_copy[W3_MAX_HUFF];
     const uint8_t *d_in = nullptr; size_t n = 0, block_size = 0; uint8_t *d_out = nullptr; size_t out_cap = 0;
     uint32_t *d_block_lens = nullptr; uint64_t *d_total = nullptr;
+    uint64_t vcall = 0;            // the call's number for the verification's rotation (the redo keeps it)
     w3_timing tm{};
     w3_timing tm_ev{}; bool tm_snap = false;   // the event times, collected early (a synchronous fallback is about to reuse job 0's events)
     int sync_rc = W3_OK;           // state 2: what the synchronous run inside w3_encode_submit returned
@@ -76,6 +77,7 @@ struct HostJob {
                                    // 3 through on the device (rc / total known), output not fetched yet
     int djob = -1, rc = W3_OK;
     uint64_t seq = 0, total = 0;
+    uint64_t vcall = 0;            // the call's number for the verification's rotation (w3_encode_blocks: the same for all its pieces)
     DevBuf d_in, d_out, d_lens, d_total;
     hipEvent_t ev_d2h = nullptr;
     w3_model_spec spec{};
@@ -112,7 +114,20 @@ struct w3_ctx {
     hipStream_t s_h2d_own = nullptr, s_d2h_own = nullptr;
     uint64_t hseq = 0;
     uint32_t host_chunk_blocks = 0;                 // W3_OPT_HOST_CHUNK_BLOCKS (0 = auto)
-    uint32_t n_encodes = 0;                         // rotates the sampled verification over the blocks, whichever job slot a call lands on
+    // the sampled verification's rotation (w3_verify.h): a number per call, counted per input shape, whichever job slot the call lands
+    // on; vcall_pin >= 0: the number the call being made now takes (a redo, or a piece of a host call) instead of a new one
+    w3::VerifyCalls vcalls;
+    int64_t vcall_pin = -1;
+};
+
+static uint64_t verify_call(w3_ctx *ctx, size_t n, size_t block_size) {
+    return ctx->vcall_pin >= 0 ? (uint64_t)ctx->vcall_pin : ctx->vcalls.next(n, block_size);
+}
+// for the duration of a scope, calls take the number `v` (the number in effect before is restored afterwards)
+struct VcallPin {
+    w3_ctx *c; int64_t saved;
+    VcallPin(w3_ctx *c_, uint64_t v) : c(c_), saved(c_->vcall_pin) { c->vcall_pin = (int64_t)v; }
+    ~VcallPin() { c->vcall_pin = saved; }
 };
 
 // the members of job j under one name
@@ -314,6 +329,10 @@ extern "C" int w3_ctx_set_option(w3_ctx *ctx, int opt, int64_t value) {
     case W3_OPT_FAULT_BLOCK:
         if (value < -1 || value > 0x7FFFFFFF) return W3_E_INVALID;
         ctx->tp.fault_block = value < 0 ? 0xFFFFFFFFu : (uint32_t)value;
+        return W3_OK;
+    case W3_OPT_FAULT_KERNELS:
+        if (value < 1 || value > 7) return W3_E_INVALID;
+        ctx->tp.fault_kernels = (uint32_t)value;
         return W3_OK;
     case W3_OPT_HOST_CHUNK_BLOCKS:
         if (value < 0 || value > 0x7FFFFFFF) return W3_E_INVALID;
@@ -768,7 +787,7 @@ static void sync_job_options(w3_ctx *ctx, JobRef &J) {
     if (&J.tp == &ctx->tp) return;
     J.tp.coder_mode = ctx->tp.coder_mode; J.tp.acc_limit = ctx->tp.acc_limit; J.tp.debug_stamps = 0;
     J.tp.variant = ctx->tp.variant; J.tp.slot_budget_mb = ctx->tp.slot_budget_mb; J.tp.verify = ctx->tp.verify;
-    J.tp.stretch = ctx->tp.stretch; J.tp.squash = ctx->tp.squash; J.tp.st = ctx->tp.st; J.tp.fault_block = ctx->tp.fault_block; J.tp.tune = ctx->tp.tune;
+    J.tp.stretch = ctx->tp.stretch; J.tp.squash = ctx->tp.squash; J.tp.st = ctx->tp.st; J.tp.fault_block = ctx->tp.fault_block; J.tp.fault_kernels = ctx->tp.fault_kernels; J.tp.tune = ctx->tp.tune;
     // the lane-order self-test runs once, on job 0's workspace; the other slots take its verdict (and lose a stale one when
     // W3_OPT_VARIANT has reset job 0's)
     if (ctx->tp.lds_order < 0) (void)twophase_lds_order_ok(ctx->tp, ctx->stream);
@@ -832,7 +851,7 @@ static int encode_core(w3_ctx *ctx, JobRef J, const w3_model_spec *spec, const u
     sync_job_options(ctx, J);
     if ((rc = attach_aux_streams(ctx, J, &J.tp == &ctx->tp ? 0 : (int)(&J.st - ctx->js)))) return rc;
     J.tp.half_cu = (ctx->tp.variant & W3_VAR_HALF_CU) != 0;
-    J.tp.verify_calls = ctx->n_encodes++;
+    J.tp.verify_calls = verify_call(ctx, n, block_size);
 
     hipEvent_t *evp = ctx->opt_timing ? J.ev : nullptr;
     uint32_t cap = default_stripe_cap(block_size);
@@ -1106,7 +1125,7 @@ extern "C" int w3_encode_submit(w3_ctx *ctx, const w3_model_spec *spec, const ui
     sync_job_options(ctx, J);
     if ((rc = attach_aux_streams(ctx, J, j))) return rc;
     J.tp.half_cu = !(ctx->tp.variant & W3_VAR_FULL_CU);
-    J.tp.verify_calls = ctx->n_encodes++;   // (the sample's rotation is the context's: a call's job slot does not matter)
+    J.tp.verify_calls = st.vcall = verify_call(ctx, n, block_size);   // (counted per shape by the context: a call's job slot does not matter)
     st.cap = default_stripe_cap(block_size);
     ENSURE(ctx, J.stripes, (size_t)nb * st.cap);
     hipEvent_t *evp = st.timed ? J.ev : nullptr;
@@ -1191,6 +1210,7 @@ extern "C" int w3_encode_wait(w3_ctx *ctx, int job) {
             ctx->tp.variant |= W3_VAR_NO_LDS_ATOMICS; ctx->tp.lds_order = 0;
             for (auto &x : ctx->jx) { x.tp.variant |= W3_VAR_NO_LDS_ATOMICS; x.tp.lds_order = 0; }
         }
+        VcallPin pin(ctx, st.vcall);   // (the same call: the same rotation)
         const int rc = encode_core(ctx, J, &st.spec, st.d_in, st.n, st.block_size, st.d_out, st.out_cap, st.d_block_lens, st.d_total, ctx->stream);
         ctx->timing.n_lds_faults += mism;
         return rc;
@@ -1253,6 +1273,7 @@ static void host_start_pending(w3_ctx *ctx) {
         for (const auto &o : ctx->js) in_flight += o.state != 0;
         if (in_flight >= w3_encode_max_in_flight(&h->spec, h->n, h->block_size)) return;
         // (the job starts behind everything enqueued on the H2D stream so far: its own input was the last of it)
+        VcallPin pin(ctx, h->vcall);
         h->rc = w3_encode_submit(ctx, &h->spec, (const uint8_t *)h->d_in.p, h->n, h->block_size, (uint8_t *)h->d_out.p, h->dcap,
                                  (uint32_t *)h->d_lens.p, (uint64_t *)h->d_total.p, ctx->s_h2d, &h->djob);
         h->state = h->rc ? 3 : 2;   // (a refused submit is reported by the wait)
@@ -1286,6 +1307,7 @@ static void host_finish_device(w3_ctx *ctx, HostJob &h) {
             int rc = parse_spec(&h.spec, ps);
             if (rc) return rc;
             const int slot = submit_pipelines(ctx, ps, (uint32_t)h.nb, h.block_size, h.n) ? h.djob : 0;
+            VcallPin pin(ctx, h.vcall);
             rc = encode_core(ctx, jobref(ctx, slot), &h.spec, (const uint8_t *)h.d_in.p, h.n, h.block_size, (uint8_t *)h.d_out.p, h.dcap,
                              (uint32_t *)h.d_lens.p, (uint64_t *)h.d_total.p, ctx->stream);
             if (rc) return rc;
@@ -1295,8 +1317,9 @@ static void host_finish_device(w3_ctx *ctx, HostJob &h) {
     }
 }
 
+// vcall: the call's number for the verification's rotation (w3_encode_blocks: its own, for every piece), or -1: a new one
 static int host_submit_core(w3_ctx *ctx, const w3_model_spec *spec, const ParsedSpec &ps, const uint8_t *in, size_t n, size_t block_size,
-                            uint8_t *out, size_t out_cap, uint32_t *block_lens, int *hjob) {
+                            uint8_t *out, size_t out_cap, uint32_t *block_lens, int *hjob, int64_t vcall = -1) {
     int rc = host_streams(ctx);
     if (rc) return rc;
     const size_t nb = (n + block_size - 1) / block_size;
@@ -1315,6 +1338,7 @@ static int host_submit_core(w3_ctx *ctx, const w3_model_spec *spec, const Parsed
     if (ps.n_huff) { memcpy(h.huff_copy, ps.huff, sizeof(w3_huff_table) * ps.n_huff); h.spec.huff = h.huff_copy; }
     h.n = n; h.block_size = block_size; h.nb = nb; h.out = out; h.out_cap = out_cap; h.block_lens = block_lens;
     h.djob = -1; h.rc = W3_OK; h.total = 0;
+    h.vcall = vcall >= 0 ? (uint64_t)vcall : verify_call(ctx, n, block_size);
     memset(&h.tm, 0, sizeof h.tm);
     // the device output buffer: the realistic bound, never more than the hard one (a call beyond it is redone: host_finish_device)
     h.dcap = std::min<size_t>(w3_max_compressed_size(n, block_size), 2 * n + 64 * nb + 64);
@@ -1500,6 +1524,9 @@ extern "C" int w3_encode_blocks(w3_ctx *ctx, const w3_model_spec *spec, const ui
     if ((rc = parse_spec(spec, ps))) { ctx->err = "malformed model spec"; return rc; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t cb = host_chunk_blocks(ctx, ps, nb, block_size, n);
+    // one number for the verification's rotation, taken by every piece: with a number per piece, the pieces of equal shape would share
+    // one count and each would only ever see every k-th rotation (k pieces per call)
+    const int64_t vcall = (int64_t)verify_call(ctx, n, block_size);
     // The pieces in flight, oldest first.  A piece's streams go to `out` at the sum of the earlier pieces' sizes, known when it is
     // waited for; once the caller's buffer is full the later pieces are still encoded (*out_len must hold the size needed) but
     // only their length tables are fetched.
@@ -1534,7 +1561,7 @@ extern "C" int w3_encode_blocks(w3_ctx *ctx, const w3_model_spec *spec, const ui
         while (qn >= host_depth(spec, hi - lo, block_size)) wait_oldest();
         if (first_err != W3_OK && first_err != W3_E_NOSPACE) break;
         int hjob = -1;
-        rc = host_submit_core(ctx, spec, ps, in + lo, hi - lo, block_size, nullptr, 0, block_lens + b0, &hjob);
+        rc = host_submit_core(ctx, spec, ps, in + lo, hi - lo, block_size, nullptr, 0, block_lens + b0, &hjob, vcall);
         if (rc) { if (first_err == W3_OK) first_err = rc; break; }
         q[qn++] = hjob;
     }
@@ -1988,6 +2015,7 @@ extern "C" int w3_encode_sharded_wait(w3_ctx *const *ctxs, int n_ctx, int sjob, 
                 HIPCHK(c, hipDeviceSynchronize());
                 ENSURE(c, x.out, (size_t)t);
                 x.cap = (size_t)t;
+                VcallPin pin(c, ds.vcall);
                 rc1 = encode_core(c, jobref(c, x.djob), &x.spec, x.d_in, x.n, x.block_size, (uint8_t *)x.out.p, x.cap, (uint32_t *)x.lens.p, (uint64_t *)x.total.p, c->stream);
                 if (rc1 == W3_OK) HIPCHK(c, hipMemcpy(&t, x.total.p, 8, hipMemcpyDeviceToHost));
             }
