@@ -16,17 +16,23 @@ phase runs beside step k's APM and coder kernels; the timed region holds exactly
 synchronous call per step.
 
 --scaling both (default)  value = the STRONG reading: ONE stream of --size bytes cut into contiguous block ranges over the N GPUs
-                          (BASELINE.json configs[3]: "enwik9 sharded across 8"); for N > 1 the WEAK reading (--size bytes per GPU)
-                          is timed too and attached as "weak".  At N = 1 the two are the same run.
+                          (BASELINE.json configs[3]: "enwik9 sharded across 8"); with --full and N > 1 the WEAK reading (--size bytes
+                          per GPU) is timed too and attached as "weak".  At N = 1 the two are the same run.
 --scaling strong | weak   that reading only.
 
 --dump-outputs DIR: after the timed steps, what the last one returned (packed block streams, block lengths, total) goes to DIR/*.npy
 (dump_outputs); the seeded input is the same from run to run, so two builds can be compared output for output.
 
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, dump (if asked) and print the line.
+--full adds everything else, each in runs of its own after the timed steps: at N > 1 the weak reading; at N = 1 one_call_at_a_time
+(+ roofline.solo, floors.coder_floor_ms), reference_stream_model, small_inputs, decode, host_path, other_configs and cpu_baseline
+(the --no-* options leave single items out).
+
 Prints ONE JSON line on rank 0 (contract in the task statement): metric / value (whole-job MiB/s) / roofline (the kernel with
-the longest launch vs the HBM roof, every kernel's figure in roofline_kernels) / cpu_baseline (the CPU oracle = C restatement of
-the reference, -O3 -march=native, timed on the host cores over a bounded sample, two legs) / decode (device round trip of EVERY
-block of the last step's output) / other_configs (BASELINE configs[2] and configs[4] shapes, 3 steps each) / floors.
+the longest launch vs the HBM roof, every kernel's figure in roofline_kernels) / floors; with --full also cpu_baseline (the CPU
+oracle = C restatement of the reference, -O3 -march=native, timed on the host cores over a bounded sample, two legs) / decode
+(device round trip of EVERY block of the last step's output) / other_configs (BASELINE configs[2] and configs[4] shapes, 3 steps
+each) and the rest named above.
 """
 import argparse
 import json
@@ -271,14 +277,19 @@ def parse_args(argv=None):
     ap.add_argument("--tune", type=int, default=0, help="W3_OPT_TUNE bit mask (scheduling experiments)")
     ap.add_argument("--verify", type=int, default=1, help="W3_OPT_VERIFY: v / 256 of the blocks are re-predicted with ballot rounds per call (1 = default sample)")
     ap.add_argument("--no-verify", action="store_true", help="switch W3_OPT_VERIFY off (sampled ballot-round re-prediction of every predict phase; on by default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-ref-model", action="store_true", help="skip the extra order012 measurement (the largest model whose streams are entirely the reference's)")
-    ap.add_argument("--no-decode", action="store_true", help="skip the device round trip of the last step's whole output")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the 3-step runs of BASELINE configs[2] / configs[4]")
-    ap.add_argument("--quick", action="store_true", help="= --no-cpu-baseline --no-ref-model --no-decode --no-other-configs --no-host-path (profiling runs)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure and check what the headline figure does not need (off: a plain "
+                    "run sets up, warms up, times --steps, dumps and prints): weak reading (N > 1), one call at a time, reference-stream model, small inputs, "
+                    "device round trip, host path, other configs, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle's baseline and its bit-exactness check")
+    ap.add_argument("--no-ref-model", action="store_true", help="with --full: skip the extra order012 measurement (the largest model whose streams are entirely the reference's) "
+                    "and the one-call-at-a-time leg")
+    ap.add_argument("--no-decode", action="store_true", help="with --full: skip the device round trip of the last step's whole output")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the short runs of BASELINE configs[2] / configs[4] and of the small inputs")
+    ap.add_argument("--quick", action="store_true", help="= --no-cpu-baseline --no-ref-model --no-decode --no-other-configs --no-host-path: with --full only the weak "
+                    "reading remains; without it, a plain run (profiling runs)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--hw-queues", type=int, default=0, help="GPU_MAX_HW_QUEUES for this run, at most %d (0 = leave the environment alone: HIP's default of 4 per priority level)" % MAX_HW_QUEUES)
-    ap.add_argument("--no-host-path", action="store_true", help="skip the PCIe-inclusive legs (host_path: w3_encode_blocks / w3_encode_host_submit from pinned and pageable memory)")
+    ap.add_argument("--no-host-path", action="store_true", help="with --full: skip the PCIe-inclusive legs (host_path: w3_encode_blocks / w3_encode_host_submit from pinned and pageable memory)")
     ap.add_argument("--force-exchange", action="store_true", help="run the RCCL exchange step even with 1 rank (rehearsal)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI, one GPU per rank (the measured path).  gloo = REHEARSAL of the multi-rank control flow on a box with "
@@ -549,7 +560,7 @@ def main():
         ctx.set_variant(*args.variant.split(","))
 
     dumped = None
-    readings = ["strong", "weak"] if (args.scaling == "both" and world > 1) else ["strong" if args.scaling == "both" else args.scaling]
+    readings = ["strong", "weak"] if (args.scaling == "both" and world > 1 and args.full) else ["strong" if args.scaling == "both" else args.scaling]
     results = {}
     rg = None
     for rd in readings:
@@ -579,7 +590,7 @@ def main():
     path = int(acc.get("path", 0))
     coder_name = args.coder if (args.coder != "x4" or (pipeline == 1 and "half_cu" not in args.variant)) else "x5"
 
-    extras = world == 1 and not exchange and rank == 0
+    extras = args.full and world == 1 and not exchange and rank == 0
     ref_model = decode = sync_line = None
     kept = []   # (compressed stream, lens) of the live output buffers of the timed steps
     if extras:
@@ -709,6 +720,10 @@ def main():
         elif sync_line:
             sync_line.pop("_rows", None)
         coder_ms = acc.get("coder_ms", 0.0) / args.steps
+        # the coder's launch with nothing beside it: the one-call-at-a-time leg's (--full), or this run's own when it made one call at a time
+        coder_floor = None
+        if path == 2:
+            coder_floor = sync_line["kernel_ms_per_step"]["coder_ms"] if sync_line else round(coder_ms, 3) if pipeline == 1 else None
         steps_per_lane = 8 * min(bs, max(n, 1))
         readings_txt = {"strong": "ONE stream of %d bytes cut over %d GPU(s)" % (r0["n_global"], world),
                         "weak": "%d bytes per GPU (%d in all)" % (n, n_global)}[main_rd]
@@ -742,9 +757,9 @@ def main():
                          "frac": dom["frac"], "traffic": dom["traffic"], "traffic_source": dom["traffic_source"],
                          "avg_launch_ms": dom["avg_launch_ms"], "algorithmic_bytes_per_launch": dom["algorithmic_bytes_per_launch"], "launches_per_step": 1,
                          "chosen_by": "longest average launch among the step's kernels (hipEvents on each kernel's launch stream)",
-                         "note": ("with several encodes in flight the coder's launch is stretched by the kernels beside it (one latency chain per lane: %s ms with nothing "
-                                  "beside it, floors.coder_floor_ms) — the kernels that own the chip are in roofline_kernels (k_apm0, k_rank_sorted) and whole_step is the step's "
-                                  "algorithmic bytes over its time" % (sync_line["kernel_ms_per_step"]["coder_ms"] if sync_line else "?")) if pipeline >= 2 and "coder" in dom["kernel"] else None,
+                         "note": ("with several encodes in flight the coder's launch is stretched by the kernels beside it (one latency chain per lane: %s, floors.coder_floor_ms) "
+                                  "— the kernels that own the chip are in roofline_kernels (k_apm0, k_rank_sorted) and whole_step is the step's algorithmic bytes over its time"
+                                  % ("%s ms with nothing beside it" % coder_floor if coder_floor is not None else "its launch with nothing beside it is measured by --full")) if pipeline >= 2 and "coder" in dom["kernel"] else None,
                          "solo": solo,
                          "kernels": [{"kernel": r["kernel"].split(" (")[0], "ms": r["avg_launch_ms"], "frac": r["frac"]} for r in table]},
             "roofline_solo": solo,
@@ -756,11 +771,10 @@ def main():
             "predict_phase": predict_phase,
             # the coder is ONE dependent chain of 8 x block_size bit-steps per lane: its time does not shrink with the block count,
             # so it is the floor of a strong-scaled run (predict / APM / pack scale with the bytes per GPU)
-            "floors": {"coder_floor_ms": (sync_line["kernel_ms_per_step"]["coder_ms"] if sync_line else round(coder_ms, 3)) if path == 2 else None,
+            "floors": {"coder_floor_ms": coder_floor,
                        "coder_launch_ms_in_this_run": round(coder_ms, 3) if path == 2 else None,
                        "bit_steps_per_lane": steps_per_lane,
-                       "cycles_per_bit_step": (round((sync_line["kernel_ms_per_step"]["coder_ms"] if sync_line else coder_ms) * 1e-3 * SHADER_GHZ * 1e9 / steps_per_lane, 1)
-                                               if path == 2 else None),
+                       "cycles_per_bit_step": round(coder_floor * 1e-3 * SHADER_GHZ * 1e9 / steps_per_lane, 1) if coder_floor is not None else None,
                        "clock_ghz_assumed": SHADER_GHZ,
                        "note": "coder_floor_ms = the coder's launch with nothing beside it (synchronous call): 8 x block_size dependent steps per lane, it does not "
                                "shrink with the block count; with two encodes in flight its launch stretches beside the next step's rank kernels"},

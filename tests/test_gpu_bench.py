@@ -1,6 +1,6 @@
-"""bench.py's contract on a small input: ONE JSON line with the metric, the roofline of the time-dominant kernel, the CPU baseline
-(the driver parses exactly this), bit-exactness of the sampled blocks against the oracle and the full device round trip included;
-and the self-launch of the ranks for --gpus N."""
+"""bench.py's contract on a small input: ONE JSON line with the metric and the roofline of the time-dominant kernel; with --full
+also the CPU baseline, bit-exactness of the sampled blocks against the oracle and the full device round trip; a plain run without
+them; and the self-launch of the ranks for --gpus N."""
 import json
 import os
 import subprocess
@@ -23,7 +23,7 @@ def run_bench(*extra, gpus=1):
 
 @pytest.mark.gpu
 def test_bench_line_contract():
-    d = run_bench()
+    d = run_bench("--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
         assert k in d, k
     assert d["unit"] == "MiB/s" and d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True
@@ -61,6 +61,19 @@ def test_bench_line_contract():
     hp = d["host_path"]
     assert hp["calls_in_flight_pinned_MiBps"] > 0 and hp["one_call_pinned_MiBps"] > 0 and hp["one_call_pageable_MiBps"] > 0 and hp["h2d_pinned_ms"] > 0 and hp["calls_in_flight"] == 5
     assert d["config"]["host_path"]["calls_in_flight_pinned_MiBps"] == hp["calls_in_flight_pinned_MiBps"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean():
+    """Without --full the line holds the headline figure and what the timed steps themselves recorded, and nothing that takes a run
+    of its own after them."""
+    d = run_bench()
+    assert d["unit"] == "MiB/s" and d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True and d["dtype"] == "u32"
+    assert d["value"] > 0 and abs(d["value"] - 6000000 / (d["ms_per_step"] * 1e-3) / 2**20) / d["value"] < 0.02
+    assert d["roofline"]["avg_launch_ms"] == max(r["avg_launch_ms"] for r in d["roofline_kernels"]) and d["roofline"]["solo"] is None
+    assert d["floors"]["coder_floor_ms"] is None and d["floors"]["coder_launch_ms_in_this_run"] > 0   # (the floor takes a run of its own)
+    for k in ("cpu_baseline", "decode", "host_path", "one_call_at_a_time", "reference_stream_model", "small_inputs", "other_configs", "weak"):
+        assert k not in d and k not in d["config"], k
 
 
 @pytest.mark.gpu
@@ -137,9 +150,9 @@ def test_bench_self_launch_one_rank_with_exchange():
 def test_bench_two_ranks_rehearsal_both_readings():
     """The multi-rank control flow end to end on the 1-GPU box: `bench.py --gpus 2` starts two ranks ITSELF (WORLD_SIZE unset), they
     share the one GPU and exchange through gloo (--backend gloo: a rehearsal, its numbers mean nothing): strong reading = ONE stream
-    cut over the ranks, weak reading attached, the exchange's totals from both ranks in the line."""
+    cut over the ranks, weak reading attached (--full), the exchange's totals from both ranks in the line."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--size", "6000000", "--backend", "gloo"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--size", "6000000", "--backend", "gloo", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -149,6 +162,16 @@ def test_bench_two_ranks_rehearsal_both_readings():
     assert d["config"]["ranks_seen_by_rccl"] == 2 and "over 2 rank(s)" in d["config"]["exchange"]
     assert d["weak"]["bytes_total"] == 12000000 and d["weak"]["value"] > 0 and d["value"] > 0
     assert "cpu_baseline" not in d and "decode" not in d   # rank-0, N = 1 extras only
+
+
+def test_bench_full_is_opt_in():
+    """CPU: a plain run leaves every extra measurement out; --full brings them in, and the --no-* options still thin out a full run."""
+    import bench
+    assert bench.parse_args(["--steps", "5"]).full is False
+    a = bench.parse_args(["--full", "--no-decode"])
+    assert a.full and a.no_decode and not a.no_cpu_baseline
+    a = bench.parse_args(["--full", "--quick"])
+    assert a.full and a.no_cpu_baseline and a.no_ref_model and a.no_decode and a.no_other_configs and a.no_host_path
 
 
 def test_launcher_command_for_n_ranks():

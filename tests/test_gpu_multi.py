@@ -174,10 +174,10 @@ def test_two_devices_sharded_encode_over_rccl():
 
 @pytest.mark.skipif("n_devices() < 2", reason="needs two devices: bench.py --gpus 2 over RCCL")
 def test_two_devices_bench_over_rccl():
-    """`bench.py --gpus 2` as the driver runs it (the ranks started by bench.py itself, one per GPU, RCCL exchange): both readings in
-    the line, the exchange's totals from both ranks."""
+    """`bench.py --gpus 2 --full` (the ranks started by bench.py itself, one per GPU, RCCL exchange): both readings in the line,
+    the exchange's totals from both ranks."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--size", "20000000"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--size", "20000000", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -342,7 +342,7 @@ def test_sampled_verification_rotates_over_all_blocks(oracle):
     """The sample is max(16, nblocks / 256) blocks and ROTATES from call to call: a fault confined to ONE block that the first
     call's sample misses is met after a bounded number of calls (ceil(nblocks / sample): w3_verify.h; every block, whatever the block
     count, tests/test_gpu_lds_fault.py).  Until then the corrupted stream goes out —
-    the coverage limit of a sampled check, stated in w3hip.h; the full check is a decode of the output (bench.py, test_gpu_fullsize)."""
+    the coverage limit of a sampled check, stated in w3hip.h; the full check is a decode of the output (bench.py --full, test_gpu_fullsize)."""
     bs, nb = 1024, 400
     data = markov_text(bs * nb, seed=29)
     c = w3.Context(0)
