@@ -221,6 +221,32 @@ int w3_decode_blocks_device(w3_ctx *ctx, const w3_model_spec *spec,
                             const uint8_t *d_in, size_t in_len, const uint32_t *d_block_lens, size_t nblocks,
                             size_t block_size, uint64_t orig_len, uint8_t *d_out, void *stream);
 
+/* ---- random access: byte ranges of the block container -------------------------------------------------------------
+ * The reference has no counterpart (one stream per file, main.rs:89-144); build-defined on the block container above.  Blocks are
+ * coded independently, so a range needs only the blocks it touches, and each of those only up to the last requested byte in it
+ * (the arithmetic decoder does not have to reach the end of a stream).  The arguments describing the container are those of
+ * w3_decode_blocks / w3_decode_blocks_device; `ranges` (host memory, both variants) are {offset, len} byte ranges of the original
+ * data: overlapping, duplicate, unsorted and zero-length ranges are valid.  The output is the ranges' bytes concatenated in request
+ * order; *out_len = the sum of their lengths, set even on W3_E_NOSPACE (out_cap too small: nothing is decoded).
+ * W3_E_INVALID: nblocks != ceil(orig_len / block_size) (checked first), a range with offset + len > orig_len (u64 wrap included),
+ * or a job in flight.  W3_E_FORMAT: a length table that claims more compressed bytes than in_len.
+ *   w3_decode_ranges         host buffers; any orig_len and block count, like w3_decode_blocks.  Only the selected blocks' streams
+ *                            cross PCIe (gathered into one host staging buffer, one H2D copy), then one D2H copy of the packed output.
+ *                            A selection of more than 2 GiB worth of blocks is decoded in several device calls.
+ *   w3_decode_ranges_device  device buffers (d_in, d_block_lens, d_out on ctx's GPU; `stream` as in w3_decode_blocks_device); the
+ *                            per-call limit on orig_len of the device calls applies.
+ * Retained workspace of the context (grown on demand, released by w3_ctx_destroy): the staging buffer the blocks are decoded into
+ * (the sum of the blocks' decoded prefixes), the job table (16 bytes per selected block) and the gather's piece list (24 bytes per
+ * 64 KiB of output), plus, for the host variant, a pinned host buffer and a device buffer holding the selected streams and the compact
+ * length table, and a device buffer for the packed output.                                                                    */
+typedef struct w3_range { uint64_t offset; uint64_t len; } w3_range;
+int w3_decode_ranges(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t in_len, const uint32_t *block_lens,
+                     size_t nblocks, size_t block_size, uint64_t orig_len, const w3_range *ranges, size_t n_ranges,
+                     uint8_t *out, size_t out_cap, size_t *out_len);
+int w3_decode_ranges_device(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *d_in, size_t in_len, const uint32_t *d_block_lens,
+                            size_t nblocks, size_t block_size, uint64_t orig_len, const w3_range *ranges /* host */, size_t n_ranges,
+                            uint8_t *d_out, size_t out_cap, size_t *out_len, void *stream);
+
 /* ---- the same encode, asynchronous: two to four calls in flight per context --------------------------
  * The reference codes one bit at a time on one thread (main.rs:103-109); here a call is three phases with different
  * bottlenecks (predict: the store path; APM: LDS round trips; coder: one latency chain per lane on 239 of 256 CUs), and a

@@ -7,6 +7,9 @@
 // what the GPU path is for.  `W3_CONTAINER=w30i` selects the reference's own
 // single-stream container (main.rs:14-15,95-96) — one GPU lane, format parity.
 // Model: init_model() of main.rs:151 — OrderNEntropy(11,3,ACHistory(8,book1)).
+//
+// `w3 r <file.bin> <offset> <length>` (build-defined: random access, which the block container makes possible and the reference's one
+// stream per file does not) writes bytes [offset, offset + length) of the original to <stem>.part, decoding only the blocks they touch.
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -244,6 +247,40 @@ static int decompress(w3_ctx *ctx, const std::string &in, const std::string &out
     return write_file(out, o.data(), (size_t)orig) ? 0 : 1;
 }
 
+// w3 r: one byte range of a block-container file (w3_decode_ranges)
+static int extract(w3_ctx *ctx, const std::string &in, uint64_t offset, uint64_t length, const std::string &out) {
+    std::vector<uint8_t> data;
+    if (!read_file(in, data)) { perror(in.c_str()); return 1; }
+    if (data.size() >= 4 && !memcmp(data.data(), "w30i", 4)) {
+        fprintf(stderr, "%s is a w30i single-stream file: random access needs the block container (w3bk) — decompress it whole with `w3 d`\n", in.c_str());
+        return 1;
+    }
+    if (data.size() < 21 || memcmp(data.data(), "w3bk", 4) || data[4] != 1) {
+        fprintf(stderr, "Magic numbers don't match up - file wasn't compressed with (this version of) w3cli!\n");
+        return 1;
+    }
+    const uint64_t orig = get_be(data.data() + 5, 8);
+    const uint32_t bs = (uint32_t)get_be(data.data() + 13, 4), nb = (uint32_t)get_be(data.data() + 17, 4);
+    if (data.size() < 21 + 4ull * nb) return die(ctx, W3_E_FORMAT, "length table");
+    std::vector<uint32_t> lens(nb ? nb : 1);
+    for (uint32_t b = 0; b < nb; b++) lens[b] = (uint32_t)get_be(data.data() + 21 + 4ull * b, 4);
+    const w3_model_spec spec = init_model();
+    const w3_range r{offset, length};
+    std::vector<uint8_t> o((size_t)length + 1);
+    size_t len = 0;
+    const int rc = w3_decode_ranges(ctx, &spec, data.data() + 21 + 4ull * nb, data.size() - 21 - 4ull * nb, lens.data(), nb, bs, orig, &r, 1,
+                                    o.data(), (size_t)length, &len);
+    if (rc) return die(ctx, rc, "w3_decode_ranges");
+    return write_file(out, o.data(), len) ? 0 : 1;
+}
+
+static bool parse_u64(const char *s, uint64_t &v) {
+    char *end = nullptr;
+    if (!*s || *s == '-') return false;
+    v = strtoull(s, &end, 10);
+    return *end == 0;
+}
+
 static int run(w3_ctx *ctx, const std::string &path, char action) {  // main.rs:55-87
     auto t0 = std::chrono::steady_clock::now();
     int rc;
@@ -259,7 +296,28 @@ static void usage(const char *msg) {  // main.rs:154-161
     exit(1);
 }
 
+static void usage_r(const char *msg) {
+    printf("Usage: w3 r <file.bin> <offset> <length>\nwrites bytes [offset, offset + length) of the original of a block-container file to "
+           "<name>.part\n\n%s\n", msg);
+    exit(1);
+}
+
 int main(int argc, char **argv) {
+    if (argc == 5 && !strcmp(argv[1], "r")) {   // w3 r <file.bin> <offset> <length>
+        uint64_t offset = 0, length = 0;
+        if (!parse_u64(argv[3], offset) || !parse_u64(argv[4], length)) usage_r("<offset> and <length> must be non-negative integers!");
+        struct stat st;
+        if (stat(argv[2], &st) || !S_ISREG(st.st_mode)) { fprintf(stderr, "Path must be a file!\n"); return 1; }
+        w3_ctx *ctx = nullptr;
+        int rc = w3_ctx_create(0, &ctx);
+        if (rc) return die(nullptr, rc, "w3_ctx_create (an MI355X is required; there is no CPU path)");
+        const auto t0 = std::chrono::steady_clock::now();
+        const int ret = extract(ctx, argv[2], offset, length, out_path(argv[2], "part"));
+        if (!ret) printf("Extraction took: %.3fs\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+        w3_ctx_destroy(ctx);
+        return ret;
+    }
+    if (argc >= 2 && !strcmp(argv[1], "r")) usage_r("Random access takes 3 arguments.");
     if (argc != 3) usage("Invokation doesn't match usage! Provide 2 arguments.");
     char action = argv[1][0];
     if (strlen(argv[1]) != 1 || (action != 'c' && action != 'd' && action != 't')) usage("Unrecognized option -> <action>!");

@@ -35,6 +35,10 @@ class ModelSpec(C.Structure):
     _fields_ = [("n_nodes", C.c_uint32), ("nodes", Node * W3_MAX_NODES), ("n_huff", C.c_uint32), ("huff", C.POINTER(HuffTable))]
 
 
+class Range(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("len", C.c_uint64)]
+
+
 class Timing(C.Structure):
     _fields_ = [("predict_ms", C.c_float), ("coder_ms", C.c_float), ("pack_ms", C.c_float), ("generic_ms", C.c_float),
                 ("total_ms", C.c_float), ("path", C.c_uint32), ("n_coder_launches", C.c_uint32),
@@ -52,6 +56,7 @@ EXPORTS = [
     "w3_shard_range", "w3_encode_blocks_sharded", "w3_encode_blocks_sharded_device", "w3_encode_stats", "w3_encode_stats_device", "w3_sweep_ordern", "w3_sweep_ordern_device", "w3_export_counters",
     "w3_encode_host_submit", "w3_encode_host_wait", "w3_encode_host_max_in_flight", "w3_rccl_library", "w3_rccl_status",
     "w3_encode_sharded_submit", "w3_encode_sharded_wait", "w3_encode_sharded_max_in_flight",
+    "w3_decode_ranges", "w3_decode_ranges_device",
 ]
 
 _lib = None
@@ -121,6 +126,8 @@ def load():
     lib.w3_encode_sharded_wait.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, vp, sz, vp, C.POINTER(C.c_uint64), C.c_int]
     lib.w3_encode_sharded_max_in_flight.argtypes = [C.POINTER(ModelSpec), C.POINTER(sz), C.c_int, sz]
     lib.w3_encode_sharded_max_in_flight.restype = C.c_int
+    lib.w3_decode_ranges.argtypes = [vp, C.POINTER(ModelSpec), vp, sz, vp, sz, sz, C.c_uint64, C.POINTER(Range), sz, vp, sz, C.POINTER(sz)]
+    lib.w3_decode_ranges_device.argtypes = [vp, C.POINTER(ModelSpec), vp, sz, vp, sz, sz, C.c_uint64, C.POINTER(Range), sz, vp, sz, C.POINTER(sz), vp]
     lib.w3_rccl_library.argtypes = [C.c_char_p]
     lib.w3_rccl_status.argtypes = [C.c_char_p, sz]
     _lib = lib

@@ -28,6 +28,20 @@ def _host_ptr(buf):
     return buf.data_ptr(), buf.numel() * buf.element_size()
 
 
+def _ranges(ranges):
+    """(ctypes array of w3_range over the numbers, count, sum of the lengths) from a sequence of (offset, len) or an (n, 2) integer array"""
+    a = np.asarray(ranges)
+    if a.size == 0:
+        a = np.zeros((0, 2), dtype=np.uint64)
+    if a.dtype.kind not in "iu":
+        raise TypeError("ranges must be integers")
+    if a.dtype.kind == "i" and (a < 0).any():
+        raise ValueError("range offsets and lengths must be non-negative")
+    a = np.ascontiguousarray(a.reshape(-1, 2).astype(np.uint64))
+    arr = (L.Range * len(a)).from_buffer(a) if len(a) else (L.Range * 1)()   # (the array keeps `a` alive)
+    return arr, len(a), int(a[:, 1].sum()) if len(a) else 0
+
+
 class Context:
     def __init__(self, device=0):
         self.lib = L.load()
@@ -160,6 +174,20 @@ class Context:
         self._chk(rc)
         return out[:orig_len]
 
+    def decode_ranges(self, model, comp, block_lens, block_size, orig_len, ranges):
+        """Random access (w3_decode_ranges): the bytes of `ranges` — (offset, len) pairs or an (n, 2) integer array — of the original data,
+        concatenated in request order, decoding only the blocks they touch.  -> np.uint8[sum of the lengths]"""
+        spec = model.spec() if isinstance(model, Model) else model
+        a = _u8(comp)
+        lens = np.ascontiguousarray(block_lens, dtype=np.uint32)
+        rs, n, total = _ranges(ranges)
+        out = np.empty(max(total, 1), dtype=np.uint8)
+        olen = C.c_size_t()
+        rc = self.lib.w3_decode_ranges(self.h, C.byref(spec), a.ctypes.data_as(C.c_void_p), len(a), lens.ctypes.data_as(C.c_void_p), len(lens),
+                                       block_size, orig_len, rs, n, out.ctypes.data_as(C.c_void_p), total, C.byref(olen))
+        self._chk(rc)
+        return out[: olen.value]
+
     def encode_stats(self, model, data, block_size):
         """ACStats (helpers.rs:60-90) per block: the bit counts the reference's `csize = bits / 8` comes from.  -> np.uint32[nb]"""
         spec = model.spec() if isinstance(model, Model) else model
@@ -273,6 +301,19 @@ class Context:
         rc = self.lib.w3_decode_blocks_device(self.h, C.byref(spec), C.c_void_p(d_comp.data_ptr()), d_comp.numel(), C.c_void_p(d_lens.data_ptr()),
                                               d_lens.numel(), block_size, orig_len, C.c_void_p(d_out.data_ptr()), st)
         self._chk(rc)
+
+    def decode_ranges_device(self, model, d_comp, d_lens, block_size, orig_len, ranges, d_out, stream=None):
+        """w3_decode_ranges_device: the bytes of `ranges` ((offset, len) pairs or an (n, 2) integer array, host side) of the original data,
+        concatenated in request order into the torch.uint8 CUDA tensor d_out.  -> bytes written"""
+        spec = model.spec() if isinstance(model, Model) else model
+        st = C.c_void_p(stream) if stream else None
+        rs, n, _ = _ranges(ranges)
+        olen = C.c_size_t()
+        rc = self.lib.w3_decode_ranges_device(self.h, C.byref(spec), C.c_void_p(d_comp.data_ptr()), d_comp.numel(), C.c_void_p(d_lens.data_ptr()),
+                                              d_lens.numel(), block_size, orig_len, rs, n, C.c_void_p(d_out.data_ptr()), d_out.numel(),
+                                              C.byref(olen), st)
+        self._chk(rc)
+        return olen.value
 
 
 def encode_blocks_sharded_device(ctxs, model, d_ins, block_size, d_out, d_lens, root=0, transport="auto"):

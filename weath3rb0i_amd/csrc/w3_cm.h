@@ -131,9 +131,10 @@ __global__ void __launch_bounds__(64) k_cm(CmArgs a) {
     const GenericArgs &g = a.g;
     const uint32_t lane = blockIdx.x * blockDim.x + threadIdx.x;
     if (lane >= g.n_lanes) return;
-    const uint32_t b = g.first_block + lane;
-    const uint64_t off = (uint64_t)b * g.block_size;
-    const uint32_t len = (uint32_t)((g.n - off) < g.block_size ? (g.n - off) : g.block_size);
+    uint32_t b = g.first_block + lane;
+    uint64_t off = (uint64_t)b * g.block_size;
+    uint32_t len = (uint32_t)((g.n - off) < g.block_size ? (g.n - off) : g.block_size);
+    if (DECODE && g.jobs) { const DecodeJob jb = g.jobs[b]; b = jb.blk; len = jb.len; off = jb.dst; }   // (w3_generic.h)
     uint8_t *lane_tbl = g.tables + (uint64_t)lane * g.lane_stride;
 
     Encoder enc; Decoder dec;
@@ -308,9 +309,10 @@ __global__ void __launch_bounds__(64) k_cm_staged(CmArgs a) {
     const GenericArgs &g = a.g;
     const uint32_t lane = blockIdx.x * blockDim.x + threadIdx.x;
     if (lane >= g.n_lanes) return;
-    const uint32_t b = g.first_block + lane;
-    const uint64_t off = (uint64_t)b * g.block_size;
-    const uint32_t len = (uint32_t)((g.n - off) < g.block_size ? (g.n - off) : g.block_size);
+    uint32_t b = g.first_block + lane;
+    uint64_t off = (uint64_t)b * g.block_size;
+    uint32_t len = (uint32_t)((g.n - off) < g.block_size ? (g.n - off) : g.block_size);
+    if (DECODE && g.jobs) { const DecodeJob jb = g.jobs[b]; b = jb.blk; len = jb.len; off = jb.dst; }   // (w3_generic.h)
     uint8_t *lane_tbl = g.tables + (uint64_t)lane * g.lane_stride;
 
     Encoder enc; Decoder dec;
@@ -441,9 +443,10 @@ __global__ void __launch_bounds__(64) k_cm_nl(CmArgs a) {
     const GenericArgs &g = a.g;
     const uint32_t lane = blockIdx.x * blockDim.x + threadIdx.x;
     if (lane >= g.n_lanes) return;
-    const uint32_t b = g.first_block + lane;
-    const uint64_t off = (uint64_t)b * g.block_size;
-    const uint32_t len = (uint32_t)((g.n - off) < g.block_size ? (g.n - off) : g.block_size);
+    uint32_t b = g.first_block + lane;
+    uint64_t off = (uint64_t)b * g.block_size;
+    uint32_t len = (uint32_t)((g.n - off) < g.block_size ? (g.n - off) : g.block_size);
+    if (DECODE && g.jobs) { const DecodeJob jb = g.jobs[b]; b = jb.blk; len = jb.len; off = jb.dst; }   // (w3_generic.h)
     uint8_t *lane_tbl = g.tables + (uint64_t)lane * g.lane_stride;
     const LeafParam *lp = s_leaf;
     Encoder enc; Decoder dec;

@@ -188,9 +188,10 @@ __global__ void __launch_bounds__(64) k_decode_spec(CmArgs a) {
     const uint32_t bl = blockIdx.x * BPW + grp;              // block of this row of LPB lanes inside the batch
     const bool live = bl < g.n_lanes;
     const uint32_t blc = live ? bl : g.n_lanes - 1u;
-    const uint32_t b = g.first_block + blc;
-    const uint64_t off = (uint64_t)b * g.block_size;
+    uint32_t b = g.first_block + blc;
+    uint64_t off = (uint64_t)b * g.block_size;
     uint32_t len = (uint32_t)((g.n - off) < g.block_size ? (g.n - off) : g.block_size);
+    if (g.jobs) { const DecodeJob jb = g.jobs[b]; b = jb.blk; len = jb.len; off = jb.dst; }   // (w3_generic.h: the random-access decode)
     if (!live) len = 0u;
     uint8_t *blk_tbl = g.tables + (uint64_t)blc * g.lane_stride;
     // this lane's node of the group's tree

@@ -22,6 +22,10 @@ struct LeafParam {
     const uint4 *lut;        // ACHistory leaves: [65536][8] coder states after the 16 most recent history bits (k_achash_lut), or null
 };
 
+// A decode job of the random-access decode (w3_decode_ranges, w3_ranges.h): the lane that takes it decodes stream `blk` (index into
+// coffs / clens) for `len` bytes — a prefix of the block: the arithmetic decoder need not reach the end of a stream — to dout + dst.
+struct DecodeJob { uint32_t blk; uint32_t len; uint64_t dst; };
+
 struct GenericArgs {
     int       n_leaves;
     LeafParam leaf[W3_MAX_LEAVES];
@@ -47,6 +51,9 @@ struct GenericArgs {
     // HuffHistory leaves: the spec's table sets, copied to the device for the call
     const w3_huff_table *huff;
     int       n_huff;
+    // decode: null = lane i decodes block first_block + i whole, to its place in dout; else lane i takes jobs[first_block + i]
+    // (model tables stay indexed by the lane within the batch)
+    const DecodeJob *jobs;
 };
 
 // Context of a leaf at step t, given the lane's common 64-bit history (newest
@@ -134,9 +141,10 @@ __global__ void __launch_bounds__(64) k_generic(GenericArgs a) {
     stage_leaves(s_leaf, a);
     const uint32_t lane = blockIdx.x * blockDim.x + threadIdx.x;
     if (lane >= a.n_lanes) return;
-    const uint32_t b = a.first_block + lane;
-    const uint64_t off = (uint64_t)b * a.block_size;
-    const uint32_t len = (uint32_t)((a.n - off) < a.block_size ? (a.n - off) : a.block_size);
+    uint32_t b = a.first_block + lane;
+    uint64_t off = (uint64_t)b * a.block_size;
+    uint32_t len = (uint32_t)((a.n - off) < a.block_size ? (a.n - off) : a.block_size);
+    if (DECODE && a.jobs) { const DecodeJob jb = a.jobs[b]; b = jb.blk; len = jb.len; off = jb.dst; }
     uint8_t *lane_tbl = a.tables + (uint64_t)lane * a.lane_stride;
 
     Encoder enc; Decoder dec;
@@ -195,9 +203,10 @@ __global__ void __launch_bounds__(64) k_generic_nl(GenericArgs a) {
     stage_leaves(s_leaf, a);
     const uint32_t lane = blockIdx.x * blockDim.x + threadIdx.x;
     if (lane >= a.n_lanes) return;
-    const uint32_t b = a.first_block + lane;
-    const uint64_t off = (uint64_t)b * a.block_size;
-    const uint32_t len = (uint32_t)((a.n - off) < a.block_size ? (a.n - off) : a.block_size);
+    uint32_t b = a.first_block + lane;
+    uint64_t off = (uint64_t)b * a.block_size;
+    uint32_t len = (uint32_t)((a.n - off) < a.block_size ? (a.n - off) : a.block_size);
+    if (DECODE && a.jobs) { const DecodeJob jb = a.jobs[b]; b = jb.blk; len = jb.len; off = jb.dst; }
     uint8_t *lane_tbl = a.tables + (uint64_t)lane * a.lane_stride;
     const LeafParam *lp = s_leaf;   // (a register copy goes to scratch: ACHistory indexes lp.table dynamically)
 

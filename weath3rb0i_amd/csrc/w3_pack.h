@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "w3_ranges.h"
+
 namespace w3 {
 
 __device__ __forceinline__ uint64_t wave_incl_scan_u64(uint64_t v) {
@@ -56,6 +58,35 @@ __global__ void __launch_bounds__(256) k_pack(const uint8_t *stripes, uint64_t s
         uint8_t *dst = out + o;
         // bytewise, coalesced: consecutive lanes -> consecutive bytes
         for (uint32_t i = threadIdx.x; i < len; i += blockDim.x) dst[i] = src[i];
+    }
+}
+
+// The random-access decode's gather (w3_decode_ranges, w3_ranges.h): piece c copies staging[src, src + len) to out[dst, dst + len).  The
+// host cuts the ranges into pieces of at most 64 KiB, one workgroup each, and the grid strides over them (no launch counts more work-items
+// than a few thousand workgroups).  Bytewise up to out's first dword boundary and after the last; in between, one aligned dword store per
+// lane, its value funnel-shifted from the two aligned source dwords it straddles when source and destination are aligned differently.
+// Those source loads reach up to 3 bytes past the piece: the staging buffer is allocated 16 bytes longer than the pieces it holds.
+#define W3_GATHER_PIECE_MAX 65536u
+__global__ void __launch_bounds__(256) k_gather_pieces(const uint8_t *staging, const RangePiece *pieces, uint32_t n, uint8_t *out) {
+    for (uint32_t c = blockIdx.x; c < n; c += gridDim.x) {
+        const RangePiece pc = pieces[c];
+        const uint8_t *src = staging + pc.src;
+        uint8_t *dst = out + pc.dst;
+        const uint32_t len = (uint32_t)pc.len;
+        const uint32_t head = min(len, (uint32_t)(-(uintptr_t)dst & 3u));
+        if (threadIdx.x < head) dst[threadIdx.x] = src[threadIdx.x];
+        const uint32_t nd = (len - head) >> 2;
+        const uint8_t *s1 = src + head;
+        uint32_t *d1 = reinterpret_cast<uint32_t *>(dst + head);
+        const uint32_t sh = (uint32_t)((uintptr_t)s1 & 3u);
+        const uint32_t *sa = reinterpret_cast<const uint32_t *>(s1 - sh);
+        if (sh == 0u) {
+            for (uint32_t k = threadIdx.x; k < nd; k += blockDim.x) d1[k] = sa[k];
+        } else {
+            for (uint32_t k = threadIdx.x; k < nd; k += blockDim.x) d1[k] = (uint32_t)((((uint64_t)sa[k + 1] << 32) | sa[k]) >> (8u * sh));
+        }
+        const uint32_t done = head + 4u * nd;
+        if (threadIdx.x < len - done) dst[done + threadIdx.x] = src[done + threadIdx.x];
     }
 }
 

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -97,6 +98,10 @@ struct w3_ctx {
     hipEvent_t ev[W3_NEV]{};
     // workspace
     DevBuf tables, stripes, lens, offs, total, flag, io_in, io_out, coffs, misc, cm_luts, achash_luts, huff, bits, sweep;
+    // the random-access decode (w3_decode_ranges*): the staging buffer the jobs decode into, the job table + gather pieces (+ for the
+    // host variant the compact length table and the selected streams behind them), and the host variant's pinned host copy of those
+    DevBuf rg_stage, rg_meta;
+    void *h_rg = nullptr; size_t h_rg_cap = 0;
     TwoPhaseWs tp;
     // the second job of the submit / wait pipeline
     struct JobWs { TwoPhaseWs tp; DevBuf stripes, flag, bits, offs, huff; hipEvent_t ev[W3_NEV]{}; } jx[W3_MAX_JOBS - 1];
@@ -238,9 +243,11 @@ extern "C" void w3_ctx_destroy(w3_ctx *ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
     DevBuf *bufs[] = {&ctx->tables, &ctx->stripes, &ctx->lens, &ctx->offs, &ctx->total, &ctx->flag,
-                      &ctx->io_in, &ctx->io_out, &ctx->coffs, &ctx->misc, &ctx->cm_luts, &ctx->achash_luts, &ctx->huff, &ctx->bits, &ctx->sweep};
+                      &ctx->io_in, &ctx->io_out, &ctx->coffs, &ctx->misc, &ctx->cm_luts, &ctx->achash_luts, &ctx->huff, &ctx->bits, &ctx->sweep,
+                      &ctx->rg_stage, &ctx->rg_meta};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
+    if (ctx->h_rg) (void)hipHostFree(ctx->h_rg);
     ctx->tp.release();
     for (auto &x : ctx->jx) {
         x.tp.release();
@@ -569,13 +576,17 @@ static int generic_encode(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, cons
     return W3_OK;
 }
 
+// The decoders: every block of the length table d_lens[nb] whole (d_jobs == nullptr), or the n_jobs decode jobs of d_jobs (the
+// random-access decode: w3_ranges.h) — the lanes, and with them the table budget's batches, the table zero-fill, the APM tables'
+// initialisation and k_decode_spec's choices, then count jobs instead of blocks.
 static int generic_decode(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, const uint8_t *d_cin, const uint32_t *d_lens, uint32_t nb,
-                          size_t block_size, uint64_t orig_len, uint8_t *d_out) {
+                          size_t block_size, uint64_t orig_len, uint8_t *d_out, const DecodeJob *d_jobs = nullptr, uint32_t n_jobs = 0) {
     GenericArgs ga;
     memset(&ga, 0, sizeof ga);
     const uint64_t lane_stride = layout_generic(ps, block_size, ga);
+    const uint32_t nl = d_jobs ? n_jobs : nb;
     uint32_t lanes = 0;
-    int rc = table_budget(ctx, lane_stride, nb, lanes);
+    int rc = table_budget(ctx, lane_stride, nl, lanes);
     if (rc) return rc;
     if ((rc = prepare_achash_luts(ctx, s, ga))) return rc;
     ENSURE(ctx, ctx->tables, (size_t)lanes * lane_stride);
@@ -586,8 +597,9 @@ static int generic_decode(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, cons
     ga.huff = ctx->tp.huff; ga.n_huff = (int)ps.n_huff;
     ga.tables = (uint8_t *)ctx->tables.p; ga.lane_stride = lane_stride;
     ga.cin = d_cin; ga.coffs = (const uint64_t *)ctx->coffs.p; ga.clens = d_lens; ga.dout = d_out;
-    for (uint32_t first = 0; first < nb; first += lanes) {
-        uint32_t cnt = std::min(lanes, nb - first);
+    ga.jobs = d_jobs;
+    for (uint32_t first = 0; first < nl; first += lanes) {
+        uint32_t cnt = std::min(lanes, nl - first);
         ga.first_block = first; ga.n_lanes = cnt;
         HIPCHK(ctx, hipMemsetAsync(ctx->tables.p, 0, (size_t)cnt * lane_stride, s));
         {   // the nibble's context tree at once, sixteen lanes per block (w3_decode_spec.h), where it applies
@@ -711,7 +723,7 @@ static int cm_encode(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, const uin
 }
 
 static int cm_decode(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, const uint8_t *d_cin, const uint32_t *d_lens, uint32_t nb,
-                     size_t block_size, uint64_t orig_len, uint8_t *d_out) {
+                     size_t block_size, uint64_t orig_len, uint8_t *d_out, const DecodeJob *d_jobs = nullptr, uint32_t n_jobs = 0) {
     CmArgs ca;
     memset(&ca, 0, sizeof ca);
     const uint64_t lane_stride = layout_cm(ps, block_size, ca);
@@ -722,7 +734,8 @@ static int cm_decode(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, const uin
     ca.g.n = orig_len; ca.g.block_size = (uint32_t)block_size;
     ca.g.huff = ctx->tp.huff; ca.g.n_huff = (int)ps.n_huff;
     ca.g.cin = d_cin; ca.g.coffs = (const uint64_t *)ctx->coffs.p; ca.g.clens = d_lens; ca.g.dout = d_out;
-    return cm_run<true>(ctx, s, ca, lane_stride, nb, 0);
+    ca.g.jobs = d_jobs;
+    return cm_run<true>(ctx, s, ca, lane_stride, d_jobs ? n_jobs : nb, 0);   // (the lanes: blocks, or jobs)
 }
 
 // ---------------------------------------------------------------------------
@@ -1615,6 +1628,190 @@ extern "C" int w3_decode_blocks(w3_ctx *ctx, const w3_model_spec *spec, const ui
     if (rc) return rc;
     HIPCHK(ctx, hipMemcpy(out, ctx->io_out.p, (size_t)orig_len, hipMemcpyDeviceToHost));
     return W3_OK;
+}
+
+// ---------------------------------------------------------------------------
+// random access: byte ranges of the block container (w3_ranges.h plans them)
+// ---------------------------------------------------------------------------
+static_assert(sizeof(RangeJob) == sizeof(DecodeJob) && offsetof(RangeJob, dst) == offsetof(DecodeJob, dst), "w3_ranges.h jobs are the decoders' DecodeJob");
+static_assert(sizeof(w3_range) == 16, "ABI struct layout");
+
+static int ranges_invalid(w3_ctx *ctx, uint64_t orig_len, size_t block_size, size_t nblocks) {
+    ctx->err = (uint64_t)nblocks != (orig_len + block_size - 1) / block_size ? "nblocks does not match orig_len/block_size"
+                                                                            : "a range runs past orig_len";
+    return W3_E_INVALID;
+}
+
+// The job table and the gather's pieces of a plan, one after the other: jobs at 0, pieces at *chunks_off (16-byte aligned).
+static std::vector<uint8_t> ranges_meta(const std::vector<RangeJob> &jobs, const std::vector<RangePiece> &chunks, size_t &chunks_off) {
+    const size_t jb = jobs.size() * sizeof(RangeJob);
+    chunks_off = (jb + 15) / 16 * 16;
+    std::vector<uint8_t> m(chunks_off + chunks.size() * sizeof(RangePiece));
+    if (jb) memcpy(m.data(), jobs.data(), jb);
+    if (!chunks.empty()) memcpy(m.data() + chunks_off, chunks.data(), chunks.size() * sizeof(RangePiece));
+    return m;
+}
+
+// Decode the jobs (d_jobs[n_jobs], stream indices into d_lens[nb] / d_cin) into the staging buffer, then gather the pieces
+// (d_chunks[n_chunks], at most W3_GATHER_PIECE_MAX bytes each) into d_out.
+static int ranges_run(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, const uint8_t *d_cin, const uint32_t *d_lens, uint32_t nb, size_t block_size,
+                      uint64_t orig_len, const DecodeJob *d_jobs, uint32_t n_jobs, const RangePiece *d_chunks, uint32_t n_chunks, uint64_t staging,
+                      uint8_t *d_out) {
+    ENSURE(ctx, ctx->rg_stage, (size_t)staging + 16);   // (k_gather_pieces reads up to 3 bytes past a piece)
+    uint8_t *d_stage = (uint8_t *)ctx->rg_stage.p;
+    const int rc = ps.is_cm() ? cm_decode(ctx, s, ps, d_cin, d_lens, nb, block_size, orig_len, d_stage, d_jobs, n_jobs)
+                              : generic_decode(ctx, s, ps, d_cin, d_lens, nb, block_size, orig_len, d_stage, d_jobs, n_jobs);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_gather_pieces, dim3(std::min<uint32_t>(n_chunks, 4096u)), dim3(256), 0, s, (const uint8_t *)d_stage, d_chunks, n_chunks, d_out);
+    HIPCHK(ctx, hipGetLastError());
+    return W3_OK;
+}
+
+extern "C" int w3_decode_ranges_device(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *d_in, size_t in_len, const uint32_t *d_block_lens,
+                                       size_t nblocks, size_t block_size, uint64_t orig_len, const w3_range *ranges, size_t n_ranges,
+                                       uint8_t *d_out, size_t out_cap, size_t *out_len, void *stream) {
+    if (!ctx) return W3_E_INVALID;
+    if (out_len) *out_len = 0;
+    int rc = check_args(ctx, (size_t)orig_len, block_size);
+    if (rc) return rc;
+    if ((rc = jobs_idle(ctx))) return rc;   // (job 0's HuffHistory tables, length scan and model tables)
+    ParsedSpec ps;
+    if ((rc = parse_spec(spec, ps))) { ctx->err = "malformed model spec"; return rc; }
+    if (!out_len) return W3_E_INVALID;
+    RangePlan p;
+    if (plan_ranges(orig_len, block_size, nblocks, ranges, n_ranges, p)) return ranges_invalid(ctx, orig_len, block_size, nblocks);
+    *out_len = (size_t)p.out_len;
+    if (p.out_len > out_cap) { ctx->err = "out_cap too small"; return W3_E_NOSPACE; }
+    if (p.out_len == 0) return W3_OK;
+    if (!d_in || !d_block_lens || !d_out) return W3_E_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    if ((rc = stage_huff(ctx, s, ps))) return rc;
+    {   // the length table must not claim more than the caller's buffer holds (as w3_decode_blocks_device)
+        ENSURE(ctx, ctx->coffs, nblocks * 8);
+        ENSURE(ctx, ctx->total, 8);
+        hipLaunchKernelGGL(k_scan_lens, dim3(1), dim3(1024), 0, s, d_block_lens, (uint64_t *)ctx->coffs.p, (uint64_t *)ctx->total.p, (uint32_t)nblocks);
+        uint64_t total = 0;
+        HIPCHK(ctx, hipMemcpyAsync(&total, ctx->total.p, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        if (total > in_len) { ctx->err = "block length table claims " + std::to_string(total) + " compressed bytes, the buffer holds " + std::to_string(in_len); return W3_E_FORMAT; }
+    }
+    const std::vector<RangePiece> chunks = gather_chunks(p, W3_GATHER_PIECE_MAX);
+    size_t coff = 0;
+    const std::vector<uint8_t> meta = ranges_meta(p.jobs, chunks, coff);
+    ENSURE(ctx, ctx->rg_meta, meta.size());
+    HIPCHK(ctx, hipMemcpyAsync(ctx->rg_meta.p, meta.data(), meta.size(), hipMemcpyHostToDevice, s));
+    rc = ranges_run(ctx, s, ps, d_in, d_block_lens, (uint32_t)nblocks, block_size, orig_len, (const DecodeJob *)ctx->rg_meta.p, (uint32_t)p.jobs.size(),
+                    (const RangePiece *)((uint8_t *)ctx->rg_meta.p + coff), (uint32_t)chunks.size(), p.staging, d_out);
+    if (rc) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(s));   // (meta: pageable memory of this frame)
+    return W3_OK;
+}
+
+// One device call of the host variant: only the selected blocks' streams go over PCIe, with the compact length table, the jobs (naming
+// streams by their index in that table) and the gather's pieces — all in one pinned buffer, one H2D copy — then one D2H copy of the
+// packed output.  The ranges were validated by the caller; the length table's total was checked against in_len.
+static int ranges_host_one(w3_ctx *ctx, const ParsedSpec &ps, const uint8_t *in, const uint32_t *block_lens, size_t nblocks, size_t block_size,
+                           uint64_t orig_len, const w3_range *ranges, size_t n_ranges, uint8_t *out) {
+    RangePlan p;
+    if (plan_ranges(orig_len, block_size, nblocks, ranges, n_ranges, p)) return ranges_invalid(ctx, orig_len, block_size, nblocks);
+    if (p.out_len == 0) return W3_OK;
+    const size_t nd = p.blocks.size();
+    std::vector<uint64_t> soff(nd);   // the selected streams' offsets in `in`
+    {
+        uint64_t c = 0;
+        size_t k = 0;
+        for (size_t b = 0; b < nblocks && k < nd; b++) {
+            if (b == p.blocks[k]) soff[k++] = c;
+            c += block_lens[b];
+        }
+    }
+    uint64_t sbytes = 0;
+    for (size_t k = 0; k < nd; k++) sbytes += block_lens[p.blocks[k]];
+    const std::vector<RangePiece> chunks = gather_chunks(p, W3_GATHER_PIECE_MAX);
+    size_t coff = 0;
+    const std::vector<uint8_t> meta = ranges_meta(compact_jobs(p), chunks, coff);
+    const size_t lens_off = (meta.size() + 15) / 16 * 16, str_off = (lens_off + nd * 4 + 15) / 16 * 16;
+    const size_t bytes = str_off + (size_t)sbytes;
+    if (bytes > ctx->h_rg_cap) {
+        if (ctx->h_rg) { HIPCHK(ctx, hipHostFree(ctx->h_rg)); ctx->h_rg = nullptr; ctx->h_rg_cap = 0; }
+        const size_t want = std::max<size_t>(bytes, 1 << 20);
+        if (hipHostMalloc(&ctx->h_rg, want) != hipSuccess) { (void)hipGetLastError(); ctx->h_rg = nullptr; ctx->err = "hipHostMalloc(" + std::to_string(want) + ") failed"; return W3_E_NOMEM; }
+        ctx->h_rg_cap = want;
+    }
+    uint8_t *h = (uint8_t *)ctx->h_rg;
+    memcpy(h, meta.data(), meta.size());
+    uint32_t *hl = (uint32_t *)(h + lens_off);
+    uint64_t o = 0;
+    for (size_t k = 0; k < nd; k++) {
+        hl[k] = block_lens[p.blocks[k]];
+        memcpy(h + str_off + o, in + soff[k], hl[k]);
+        o += hl[k];
+    }
+    hipStream_t s = ctx->stream;
+    ENSURE(ctx, ctx->rg_meta, bytes);
+    ENSURE(ctx, ctx->io_out, (size_t)p.out_len);
+    uint8_t *d = (uint8_t *)ctx->rg_meta.p;
+    HIPCHK(ctx, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
+    int rc = stage_huff(ctx, s, ps);
+    if (rc) return rc;
+    rc = ranges_run(ctx, s, ps, d + str_off, (const uint32_t *)(d + lens_off), (uint32_t)nd, block_size, orig_len, (const DecodeJob *)d, (uint32_t)nd,
+                    (const RangePiece *)(d + coff), (uint32_t)chunks.size(), p.staging, (uint8_t *)ctx->io_out.p);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(out, ctx->io_out.p, (size_t)p.out_len, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return W3_OK;
+}
+
+extern "C" int w3_decode_ranges(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t in_len, const uint32_t *block_lens,
+                                size_t nblocks, size_t block_size, uint64_t orig_len, const w3_range *ranges, size_t n_ranges,
+                                uint8_t *out, size_t out_cap, size_t *out_len) {
+    if (!ctx) return W3_E_INVALID;
+    if (out_len) *out_len = 0;
+    int rc = check_args(ctx, (size_t)orig_len, block_size, false);   // (any length: a large selection goes through in several device calls)
+    if (rc) return rc;
+    if ((rc = jobs_idle(ctx))) return rc;
+    ParsedSpec ps;
+    if ((rc = parse_spec(spec, ps))) { ctx->err = "malformed model spec"; return rc; }
+    if (!out_len) return W3_E_INVALID;
+    RangePlan p;
+    if (plan_ranges(orig_len, block_size, nblocks, ranges, n_ranges, p)) return ranges_invalid(ctx, orig_len, block_size, nblocks);
+    *out_len = (size_t)p.out_len;
+    if (p.out_len > out_cap) { ctx->err = "out_cap too small"; return W3_E_NOSPACE; }
+    if (p.out_len == 0) return W3_OK;
+    if (!in || !block_lens || !out) return W3_E_INVALID;
+    uint64_t total = 0;
+    for (size_t b = 0; b < nblocks; b++) total += block_lens[b];
+    if (total > in_len) { ctx->err = "block length table claims " + std::to_string(total) + " compressed bytes, the buffer holds " + std::to_string(in_len); return W3_E_FORMAT; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // blocks per device call: 2 GiB worth (W3_OPT_HOST_CHUNK_BLOCKS: fewer, for tests), and at most as many bytes of packed output
+    const uint64_t capb = ctx->host_chunk_blocks ? (uint64_t)ctx->host_chunk_blocks : (uint64_t)host_call_cap_blocks(block_size);
+    if (p.blocks.size() <= capb && p.out_len <= capb * block_size)
+        return ranges_host_one(ctx, ps, in, block_lens, nblocks, block_size, orig_len, ranges, n_ranges, out);
+    // A larger selection: the ranges are cut into parts of at most capb / 2 blocks' worth (each touches at most capb / 2 + 1 blocks), and
+    // runs of consecutive parts go through one device call each while their blocks, counted part by part, and bytes stay within the cap.
+    // Consecutive parts are consecutive stretches of the output, so each call writes its packed output straight to its place in `out`.
+    const uint64_t part = std::max<uint64_t>(1, capb / 2) * block_size;
+    std::vector<w3_range> batch;
+    uint64_t bblocks = 0, bbytes = 0, dst = 0;
+    auto flush = [&]() -> int {
+        if (batch.empty()) return W3_OK;
+        const int r = ranges_host_one(ctx, ps, in, block_lens, nblocks, block_size, orig_len, batch.data(), batch.size(), out + dst);
+        dst += bbytes;
+        batch.clear(); bblocks = 0; bbytes = 0;
+        return r;
+    };
+    for (size_t q = 0; q < n_ranges; q++) {
+        const uint64_t end = ranges[q].offset + ranges[q].len;
+        for (uint64_t o = ranges[q].offset; o < end; o += part) {
+            const w3_range r{o, std::min(part, end - o)};
+            const uint64_t rb = (r.offset + r.len - 1) / block_size - r.offset / block_size + 1;
+            if (bblocks + rb > capb || bbytes + r.len > capb * block_size)
+                if ((rc = flush())) return rc;
+            batch.push_back(r); bblocks += rb; bbytes += r.len;
+        }
+    }
+    return flush();
 }
 
 // ---------------------------------------------------------------------------
