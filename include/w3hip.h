@@ -370,6 +370,61 @@ int w3_sweep_ordern(w3_ctx *ctx, const uint8_t *in, size_t n, size_t block_size,
 int w3_sweep_ordern_device(w3_ctx *ctx, const uint8_t *d_in, size_t n, size_t block_size, const uint8_t *bits, const uint8_t *aligns,
                            size_t ncfg, uint32_t *block_bits);
 
+/* ---- AC over Huffman (bin/ac-over-huffman/main.rs:46-89), the reference's best-ratio driver ------------------------------------
+ * compress() of that driver (:69-89): byte histogram -> package_merge(counts, huffman_size) -> canonical(code_lens) (:74-76); then
+ * every input byte's code is walked MSB first ((code >> i) & 1 for i = len-1 .. 0, :79-82) and each of those bits takes the usual step
+ * p = model.predict(); model.update(bit); ac.encode(bit, p) (:81-84) with model = OrderN::new(ctx_bits, 0) (:71); ac.flush (:87).  The
+ * context is the last ctx_bits bits of the HUFFMAN bit string (it runs across symbol boundaries).  The reference only runs this into
+ * ACStats (:72, :88), sweeping huffman_size 7..=15 x ctx_bits 8..=30 (:20-32), and has no decoder for it; here it is also a real
+ * encode AND decode on the block container.
+ *   Code table  w3_huff_code: canonical()'s output AS IS (not bit-reversed: that is w3_huff_table's form); len 0 = symbol absent, else
+ *     1..16.  w3_huff_code_table builds it as the driver does, from the histogram of the WHOLE buffer (:74); W3_E_INVALID for the
+ *     reference's three panics (no symbols, huffman_size > 32, too small for the alphabet) and for a huffman_size above 16 that yields
+ *     a length above 16 (codes are u16, package_merge.rs:87).  Equal counts / lengths are taken in ascending symbol order, as in
+ *     w3_huff_tables below; reference-identical tables for tied histograms are the caller's (pass the crate's own canonical()
+ *     output: INTEGRATION.md) — hence every entry point takes the TABLE, never huffman_size.  One distinct symbol gives all-zero
+ *     lengths, as in the reference (package_merge of one count is [0]): such a file codes zero bits.
+ *   Validation (host, before any launch; W3_E_INVALID otherwise): every len <= 16, code < 2^len, and the table equals canonical(len)
+ *     up to a permutation among the symbols of equal length (the codes of one length are one contiguous range: the decoder relies on it).
+ *   Model  OrderN(ctx_bits, 0), ctx_bits 1..31; history and first context 0; Model::update = adapt, then advance (models/mod.rs:28-31).
+ *   Block container as for every other model: block b is coded alone with a fresh model and coder, its stream byte aligned by flush,
+ *     streams concatenated, block_lens[] beside them.  The TABLE is global: one per call, as the driver's is one per file.
+ *   Counting sink: block_bits[b] as w3_encode_stats defines it; csize = sum / 8 (helpers.rs:70-73).
+ *   A byte whose len is 0: stats and sweep mirror the reference for any table (it contributes no bits); the ENCODE entry points return
+ *     W3_E_INVALID when the input holds one (checked on the device), because such output could not be decoded.  A container writer
+ *     turns the one-symbol table into len 1, code 0 for that symbol before it encodes (tools/w3cli.cpp, Context.aoh_compress).
+ *   Limits: block_size x max len < 2^32; n < 2^32 - 4096 per DEVICE call, the host-buffer encode / decode / stats take any length in
+ *     pieces of at most 2 GiB.  Other conventions as the neighbours': *out_len set even on W3_E_NOSPACE, W3_E_FORMAT for a length table
+ *     that claims more than in_len, W3_E_INVALID while a job is in flight.
+ *   W3_OPT_PATH: W3_PATH_AUTO and W3_PATH_GENERIC run the fused lane-per-block kernel k_aoh (csrc/w3_aoh.h); a two-phase form (predict
+ *     all steps in parallel, code from registers) is not built: W3_PATH_TWOPHASE returns W3_E_UNSUPPORTED for this family.
+ *     W3_OPT_TIMING fills generic_ms / pack_ms / total_ms (predict_ms and coder_ms stay 0).
+ * w3_aoh_max_compressed_size: upper bound on the concatenated streams (16 output bits per coded bit); 0 = block_size 0 or an INVALID
+ * table (needs no device: the way to validate a table).                                                                          */
+typedef struct w3_huff_code { uint16_t code[256]; uint8_t len[256]; } w3_huff_code;
+int    w3_huff_code_table(const uint8_t *buf, size_t n, uint8_t huffman_size, w3_huff_code *out);   /* host only */
+size_t w3_aoh_max_compressed_size(size_t n, size_t block_size, const w3_huff_code *code);
+int w3_aoh_encode_blocks(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *in, size_t n, size_t block_size,
+                         uint8_t *out, size_t out_cap, size_t *out_len, uint32_t *block_lens);
+int w3_aoh_encode_blocks_device(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *d_in, size_t n, size_t block_size,
+                                uint8_t *d_out, size_t out_cap, uint32_t *d_block_lens, uint64_t *d_total, void *stream);
+int w3_aoh_decode_blocks(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *in, size_t in_len,
+                         const uint32_t *block_lens, size_t nblocks, size_t block_size, uint64_t orig_len, uint8_t *out);
+int w3_aoh_decode_blocks_device(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *d_in, size_t in_len,
+                                const uint32_t *d_block_lens, size_t nblocks, size_t block_size, uint64_t orig_len, uint8_t *d_out,
+                                void *stream);
+int w3_aoh_encode_stats(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *in, size_t n, size_t block_size,
+                        uint32_t *block_bits);
+int w3_aoh_encode_stats_device(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *d_in, size_t n, size_t block_size,
+                               uint32_t *d_block_bits, void *stream);
+/* The driver's sweep (:20-32) in ONE call: configuration c = (codes[code_idx[c]], ctx_bits[c]); lanes = configurations x blocks,
+ * batched only when the Counter tables exceed the device memory.  block_bits (host memory) = [ncfg][nblocks], configuration-major.
+ * n_codes <= 64, ncfg <= 4096.  The driver around it (weath3rb0i_amd/sweep.py, --driver ac-huff) prints the reference's lines. */
+int w3_sweep_ac_over_huffman(w3_ctx *ctx, const uint8_t *in, size_t n, size_t block_size, const w3_huff_code *codes, size_t n_codes,
+                             const uint8_t *code_idx, const uint8_t *ctx_bits, size_t ncfg, uint32_t *block_bits);
+int w3_sweep_ac_over_huffman_device(w3_ctx *ctx, const uint8_t *d_in, size_t n, size_t block_size, const w3_huff_code *codes,
+                                    size_t n_codes, const uint8_t *code_idx, const uint8_t *ctx_bits, size_t ncfg, uint32_t *block_bits);
+
 /* ---- context statistics export (README.md:9: "output stats from contexts for use by external neural nets") --------
  * The Counter table (`stats`, models/ordern.rs:5 / ordern_entropy.rs:6) of a one-leaf adaptive model after it has seen
  * `in` as ONE stream, i.e. the state the reference's model is in when compress() returns: counters[ctx] = n0 | n1 << 16

@@ -7,6 +7,8 @@
 // what the GPU path is for.  `W3_CONTAINER=w30i` selects the reference's own
 // single-stream container (main.rs:14-15,95-96) — one GPU lane, format parity.
 // Model: init_model() of main.rs:151 — OrderNEntropy(11,3,ACHistory(8,book1)).
+// W3_MODEL=aoh or aoh:<hsize>,<ctx> codes with the reference's best-ratio research driver, AC over Huffman
+// (bin/ac-over-huffman/main.rs:69-89), into version 2 of the block container (below).
 //
 // `w3 r <file.bin> <offset> <length>` (build-defined: random access, which the block container makes possible and the reference's one
 // stream per file does not) writes bytes [offset, offset + length) of the original to <stem>.part, decoding only the blocks they touch.
@@ -41,7 +43,8 @@ static w3_model_spec init_model() {
     w3_model_spec s;
     memset(&s, 0, sizeof s);
     const char *m = getenv("W3_MODEL");
-    const std::string name = m ? m : "default";
+    std::string name = m ? m : "default";
+    if (name.compare(0, 3, "aoh") == 0) name = "default";   // (AC over Huffman is not a model spec: aoh_model() below; the spec is unused then)
     if (name == "default") {
         push(s, W3_NODE_ORDERN, 11, 3, 8);
         s.nodes[0].history = W3_HIST_AC;
@@ -57,6 +60,22 @@ static w3_model_spec init_model() {
     if (name != "order012") push(s, W3_NODE_APM, 0, W3_APM_ORDER0, 7);
     if (name == "fullcm") push(s, W3_NODE_APM, 0, W3_APM_ORDER1, 6);
     return s;
+}
+
+// W3_MODEL=aoh[:<hsize>,<ctx>] — AC over Huffman (bin/ac-over-huffman/main.rs): OrderN(ctx, 0) over the bits of the bytes' canonical
+// Huffman codes of at most hsize bits.  Default hsize 13, ctx 24: the reference's best published configuration for enwik7.
+struct AohModel { bool on = false; int hsize = 13, ctx = 24; };
+static AohModel aoh_model() {
+    AohModel a;
+    const char *m = getenv("W3_MODEL");
+    if (!m || strncmp(m, "aoh", 3)) return a;
+    a.on = true;
+    if (m[3] == 0) return a;
+    if (m[3] != ':' || sscanf(m + 4, "%d,%d", &a.hsize, &a.ctx) != 2 || a.hsize < 1 || a.hsize > 16 || a.ctx < 1 || a.ctx > 31) {
+        fprintf(stderr, "W3_MODEL=aoh:<hsize 1..16>,<ctx 1..31>\n");
+        exit(1);
+    }
+    return a;
 }
 
 static bool read_file(const std::string &p, std::vector<uint8_t> &out) {
@@ -93,7 +112,8 @@ static int die(w3_ctx *ctx, int rc, const char *what) {
     return 1;
 }
 
-static bool write_block_container(const std::string &out, size_t orig, const std::vector<uint32_t> &lens, size_t nb, const uint8_t *body, size_t blen);
+static bool write_block_container(const std::string &out, size_t orig, const std::vector<uint32_t> &lens, size_t nb, const uint8_t *body, size_t blen,
+                                  const w3_huff_code *code = nullptr, uint8_t ctx_bits = 0);
 // bytes per w3_encode_blocks / w3_decode_blocks call: a multiple of the block size below the library's 4 GiB limit
 static size_t call_max() {
     size_t m = (size_t)1 << 31;
@@ -118,6 +138,24 @@ static int compress(w3_ctx *ctx, const std::string &in, const std::string &out) 
     std::vector<uint32_t> lens(nb ? nb : 1);
     size_t blen = 0;
     int rc;
+    const AohModel am = aoh_model();
+    if (am.on) {   // version 2 of the container: the table is the file's (histogram of the whole file, main.rs:74), the library takes any length
+        w3_huff_code code;
+        memset(&code, 0, sizeof code);
+        if (!data.empty()) {
+            rc = w3_huff_code_table(data.data(), data.size(), (uint8_t)am.hsize, &code);
+            if (rc) { fprintf(stderr, "w3_huff_code_table: hsize %d does not fit this file's alphabet\n", am.hsize); return 1; }
+            bool any = false;
+            for (int s = 0; s < 256; s++) any |= code.len[s] != 0;
+            // One distinct symbol: the reference's table is all zero (such a file codes zero bits), which no decoder could read back.
+            // The container writer gives that symbol len 1, code 0 before it encodes.
+            if (!any) code.len[data[0]] = 1;
+        }
+        rc = w3_aoh_encode_blocks(ctx, &code, (uint8_t)am.ctx, data.data(), data.size(), kBlock, body.data(), body.size(), &blen, lens.data());
+        if (rc == W3_E_NOSPACE) { body.resize(blen); rc = w3_aoh_encode_blocks(ctx, &code, (uint8_t)am.ctx, data.data(), data.size(), kBlock, body.data(), body.size(), &blen, lens.data()); }
+        if (rc) return die(ctx, rc, "w3_aoh_encode_blocks");
+        return write_block_container(out, data.size(), lens, nb, body.data(), blen, &code, (uint8_t)am.ctx) ? 0 : 1;
+    }
     // W3_SHARDS=k: the blocks as k contiguous ranges on k contexts, one per GPU (round robin over the devices present) —
     // w3_encode_blocks_sharded, the single-process form of BASELINE configs[3]; same container bytes as one context
     const char *sh = getenv("W3_SHARDS");
@@ -151,9 +189,18 @@ static int compress(w3_ctx *ctx, const std::string &in, const std::string &out) 
     return write_block_container(out, data.size(), lens, nb, body.data(), blen) ? 0 : 1;
 }
 
-static bool write_block_container(const std::string &out, size_t orig, const std::vector<uint32_t> &lens, size_t nb, const uint8_t *body, size_t blen) {
-    std::vector<uint8_t> file = {'w', '3', 'b', 'k', 1};
+// "w3bk" + version + u64 length + u32 block size + u32 block count (version 1); version 2 (AC over Huffman) then holds ctx_bits (1 byte)
+// and the code table (256 codes of 2 bytes, then 256 lengths); then, in both, the length table and the streams.
+static const size_t kHeader = 21, kAohExtra = 1 + 512 + 256;
+static bool write_block_container(const std::string &out, size_t orig, const std::vector<uint32_t> &lens, size_t nb, const uint8_t *body, size_t blen,
+                                  const w3_huff_code *code, uint8_t ctx_bits) {
+    std::vector<uint8_t> file = {'w', '3', 'b', 'k', (uint8_t)(code ? 2 : 1)};
     put_be(file, orig, 8); put_be(file, kBlock, 4); put_be(file, nb, 4);
+    if (code) {
+        file.push_back(ctx_bits);
+        for (int s = 0; s < 256; s++) put_be(file, code->code[s], 2);
+        for (int s = 0; s < 256; s++) file.push_back(code->len[s]);
+    }
     for (size_t b = 0; b < nb; b++) put_be(file, lens[b], 4);
     file.insert(file.end(), body, body + blen);
     return write_file(out, file.data(), file.size());
@@ -219,19 +266,30 @@ static int decompress(w3_ctx *ctx, const std::string &in, const std::string &out
         if (rc) return die(ctx, rc, "w3_decompress_stream");
         return write_file(out, o.data(), len) ? 0 : 1;
     }
-    if (data.size() < 21 || memcmp(data.data(), "w3bk", 4) || data[4] != 1) {  // main.rs:123-124 asserts the magic
+    if (data.size() < kHeader || memcmp(data.data(), "w3bk", 4) || (data[4] != 1 && data[4] != 2)) {  // main.rs:123-124 asserts the magic
         fprintf(stderr, "Magic numbers don't match up - file wasn't compressed with (this version of) w3cli!\n");
         return 1;
     }
+    const bool v2 = data[4] == 2;
+    const size_t hdr = kHeader + (v2 ? kAohExtra : 0);
     uint64_t orig = get_be(data.data() + 5, 8);
     uint32_t bs = (uint32_t)get_be(data.data() + 13, 4), nb = (uint32_t)get_be(data.data() + 17, 4);
-    if (data.size() < 21 + 4ull * nb) return die(ctx, W3_E_FORMAT, "length table");
+    if (data.size() < hdr + 4ull * nb) return die(ctx, W3_E_FORMAT, "length table");
     std::vector<uint32_t> lens(nb ? nb : 1);
     uint64_t total = 0;
-    for (uint32_t b = 0; b < nb; b++) { lens[b] = (uint32_t)get_be(data.data() + 21 + 4ull * b, 4); total += lens[b]; }
-    if (data.size() < 21 + 4ull * nb + total) return die(ctx, W3_E_FORMAT, "streams");
+    for (uint32_t b = 0; b < nb; b++) { lens[b] = (uint32_t)get_be(data.data() + hdr + 4ull * b, 4); total += lens[b]; }
+    if (data.size() < hdr + 4ull * nb + total) return die(ctx, W3_E_FORMAT, "streams");
     std::vector<uint8_t> o((size_t)orig + 1);
-    const uint8_t *body = data.data() + 21 + 4ull * nb;
+    const uint8_t *body = data.data() + hdr + 4ull * nb;
+    if (v2) {   // AC over Huffman: the model is in the file (ctx_bits and the table), whatever W3_MODEL says
+        w3_huff_code code;
+        const uint8_t ctx_bits = data[kHeader];
+        for (int s = 0; s < 256; s++) code.code[s] = (uint16_t)get_be(data.data() + kHeader + 1 + 2 * s, 2);
+        memcpy(code.len, data.data() + kHeader + 1 + 512, 256);
+        int rc = w3_aoh_decode_blocks(ctx, &code, ctx_bits, body, (size_t)total, lens.data(), nb, bs, orig, o.data());
+        if (rc) return die(ctx, rc, "w3_aoh_decode_blocks");
+        return write_file(out, o.data(), (size_t)orig) ? 0 : 1;
+    }
     const size_t per_call = bs ? std::max<size_t>(1, call_max() / bs) : nb;   // blocks per call (compress() above)
     uint64_t coff = 0;
     for (size_t b0 = 0; b0 < nb || b0 == 0; b0 += per_call) {
@@ -253,6 +311,10 @@ static int extract(w3_ctx *ctx, const std::string &in, uint64_t offset, uint64_t
     if (!read_file(in, data)) { perror(in.c_str()); return 1; }
     if (data.size() >= 4 && !memcmp(data.data(), "w30i", 4)) {
         fprintf(stderr, "%s is a w30i single-stream file: random access needs the block container (w3bk) — decompress it whole with `w3 d`\n", in.c_str());
+        return 1;
+    }
+    if (data.size() >= kHeader && !memcmp(data.data(), "w3bk", 4) && data[4] == 2) {
+        fprintf(stderr, "%s is a version-2 block container (AC over Huffman): random access is not implemented for these streams — decompress it whole with `w3 d`\n", in.c_str());
         return 1;
     }
     if (data.size() < 21 || memcmp(data.data(), "w3bk", 4) || data[4] != 1) {
@@ -338,7 +400,7 @@ int main(int argc, char **argv) {
         if (d) closedir(d);
         const char *cont = getenv("W3_CONTAINER"), *sh = getenv("W3_SHARDS"), *serial = getenv("W3_SERIAL");
         const bool block_container = !(cont && !strcmp(cont, "w30i")) && !(sh && atoi(sh) > 1);
-        if (action == 'c' && block_container && !serial) ret = compress_dir_in_flight(ctx, files);   // files in flight (W3_SERIAL=1: one after the other)
+        if (action == 'c' && block_container && !serial && !aoh_model().on) ret = compress_dir_in_flight(ctx, files);   // files in flight (W3_SERIAL=1: one after the other)
         else for (const std::string &p : files) ret |= run(ctx, p, action);
     } else {
         ret = run(ctx, argv[2], action);

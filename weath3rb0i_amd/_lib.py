@@ -31,6 +31,11 @@ class HuffTable(C.Structure):
     _fields_ = [("code", C.c_uint16 * 256), ("len", C.c_uint8 * 256), ("rem_code", C.c_uint16 * 256), ("rem_len", C.c_uint8 * 256)]
 
 
+class HuffCode(C.Structure):
+    """w3_huff_code: canonical()'s (code, len) per byte value, not bit-reversed (AC over Huffman)"""
+    _fields_ = [("code", C.c_uint16 * 256), ("len", C.c_uint8 * 256)]
+
+
 class ModelSpec(C.Structure):
     _fields_ = [("n_nodes", C.c_uint32), ("nodes", Node * W3_MAX_NODES), ("n_huff", C.c_uint32), ("huff", C.POINTER(HuffTable))]
 
@@ -57,6 +62,9 @@ EXPORTS = [
     "w3_encode_host_submit", "w3_encode_host_wait", "w3_encode_host_max_in_flight", "w3_rccl_library", "w3_rccl_status",
     "w3_encode_sharded_submit", "w3_encode_sharded_wait", "w3_encode_sharded_max_in_flight",
     "w3_decode_ranges", "w3_decode_ranges_device",
+    "w3_huff_code_table", "w3_aoh_max_compressed_size", "w3_aoh_encode_blocks", "w3_aoh_encode_blocks_device", "w3_aoh_decode_blocks",
+    "w3_aoh_decode_blocks_device", "w3_aoh_encode_stats", "w3_aoh_encode_stats_device", "w3_sweep_ac_over_huffman",
+    "w3_sweep_ac_over_huffman_device",
 ]
 
 _lib = None
@@ -128,6 +136,18 @@ def load():
     lib.w3_encode_sharded_max_in_flight.restype = C.c_int
     lib.w3_decode_ranges.argtypes = [vp, C.POINTER(ModelSpec), vp, sz, vp, sz, sz, C.c_uint64, C.POINTER(Range), sz, vp, sz, C.POINTER(sz)]
     lib.w3_decode_ranges_device.argtypes = [vp, C.POINTER(ModelSpec), vp, sz, vp, sz, sz, C.c_uint64, C.POINTER(Range), sz, vp, sz, C.POINTER(sz), vp]
+    hc, u8 = C.POINTER(HuffCode), C.c_uint8
+    lib.w3_huff_code_table.argtypes = [vp, sz, u8, hc]
+    lib.w3_aoh_max_compressed_size.restype = sz
+    lib.w3_aoh_max_compressed_size.argtypes = [sz, sz, hc]
+    lib.w3_aoh_encode_blocks.argtypes = [vp, hc, u8, vp, sz, sz, vp, sz, C.POINTER(sz), vp]
+    lib.w3_aoh_encode_blocks_device.argtypes = [vp, hc, u8, vp, sz, sz, vp, sz, vp, vp, vp]
+    lib.w3_aoh_decode_blocks.argtypes = [vp, hc, u8, vp, sz, vp, sz, sz, C.c_uint64, vp]
+    lib.w3_aoh_decode_blocks_device.argtypes = [vp, hc, u8, vp, sz, vp, sz, sz, C.c_uint64, vp, vp]
+    lib.w3_aoh_encode_stats.argtypes = [vp, hc, u8, vp, sz, sz, vp]
+    lib.w3_aoh_encode_stats_device.argtypes = [vp, hc, u8, vp, sz, sz, vp, vp]
+    lib.w3_sweep_ac_over_huffman.argtypes = [vp, vp, sz, sz, vp, sz, vp, vp, sz, vp]
+    lib.w3_sweep_ac_over_huffman_device.argtypes = [vp, vp, sz, sz, vp, sz, vp, vp, sz, vp]
     lib.w3_rccl_library.argtypes = [C.c_char_p]
     lib.w3_rccl_status.argtypes = [C.c_char_p, sz]
     _lib = lib

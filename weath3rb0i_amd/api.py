@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from .models import Model, W3Error, init_model
+from .models import HuffCode, Model, W3Error, init_model
 
 MAGIC_STR = b"w30i"  # main.rs:14
 
@@ -227,6 +227,75 @@ class Context:
                                              p.ctypes.data_as(C.c_void_p)))
         return p[: len(a) * 8]
 
+    # ---- AC over Huffman (bin/ac-over-huffman/main.rs:46-89; include/w3hip.h w3_aoh_*) ----
+    def aoh_encode_blocks(self, code, ctx_bits, data, block_size, out_cap=None):
+        """OrderN(ctx_bits, 0) over the bits of the bytes' Huffman codes (`code`: a HuffCode), block container.
+        -> (concatenated streams: np.uint8[], block_lens: np.uint32[])"""
+        a = _u8(data)
+        n = len(a)
+        nb = (n + block_size - 1) // block_size if block_size else 0
+        if out_cap is None:
+            out_cap = 2 * n + 64 * nb + 64
+        while True:
+            out = np.empty(max(out_cap, 1), dtype=np.uint8)
+            lens = np.zeros(max(nb, 1), dtype=np.uint32)
+            olen = C.c_size_t()
+            rc = self.lib.w3_aoh_encode_blocks(self.h, C.byref(code.table), ctx_bits, a.ctypes.data_as(C.c_void_p), n, block_size,
+                                               out.ctypes.data_as(C.c_void_p), out_cap, C.byref(olen), lens.ctypes.data_as(C.c_void_p))
+            if rc == L.W3_E_NOSPACE and olen.value > out_cap:
+                out_cap = olen.value
+                continue
+            self._chk(rc)
+            return out[: olen.value], lens[:nb]
+
+    def aoh_decode_blocks(self, code, ctx_bits, comp, block_lens, block_size, orig_len):
+        a = _u8(comp)
+        lens = np.ascontiguousarray(block_lens, dtype=np.uint32)
+        out = np.empty(max(orig_len, 1), dtype=np.uint8)
+        rc = self.lib.w3_aoh_decode_blocks(self.h, C.byref(code.table), ctx_bits, a.ctypes.data_as(C.c_void_p), len(a), lens.ctypes.data_as(C.c_void_p),
+                                           len(lens), block_size, orig_len, out.ctypes.data_as(C.c_void_p))
+        self._chk(rc)
+        return out[:orig_len]
+
+    def aoh_encode_stats(self, code, ctx_bits, data, block_size):
+        """ACStats bit counts per block (what the driver's csize = bits / 8 comes from, :72, :88).  -> np.uint32[nb]"""
+        a = _u8(data)
+        nb = (len(a) + block_size - 1) // block_size if block_size else 0
+        bits = np.zeros(max(nb, 1), dtype=np.uint32)
+        self._chk(self.lib.w3_aoh_encode_stats(self.h, C.byref(code.table), ctx_bits, a.ctypes.data_as(C.c_void_p), len(a), block_size,
+                                               bits.ctypes.data_as(C.c_void_p)))
+        return bits[:nb]
+
+    @staticmethod
+    def _aoh_cfgs(codes, configs):
+        tabs = (L.HuffCode * max(len(codes), 1))(*[c.table for c in codes])
+        ci = np.array([c[0] for c in configs], dtype=np.uint8)
+        cb = np.array([c[1] for c in configs], dtype=np.uint8)
+        return tabs, ci, cb
+
+    def sweep_ac_over_huffman(self, data, block_size, codes, configs):
+        """The driver's sweep (:20-32) in one call: `codes` = HuffCode list, `configs` = (index into codes, ctx_bits) pairs.
+        -> np.uint32[len(configs)][nb] ACStats bit counts."""
+        a = _u8(data)
+        nb = (len(a) + block_size - 1) // block_size if block_size else 0
+        tabs, ci, cb = self._aoh_cfgs(codes, configs)
+        out = np.zeros((len(configs), max(nb, 1)), dtype=np.uint32)
+        self._chk(self.lib.w3_sweep_ac_over_huffman(self.h, a.ctypes.data_as(C.c_void_p), len(a), block_size, tabs, len(codes),
+                                                    ci.ctypes.data_as(C.c_void_p), cb.ctypes.data_as(C.c_void_p), len(configs),
+                                                    out.ctypes.data_as(C.c_void_p)))
+        return out[:, :nb]
+
+    def aoh_compress(self, data, huffman_size=13, ctx_bits=24, block_size=65536):
+        """Container writer's form: the table of `data` (HuffCode.new), encode.  A one-symbol input gives the all-zero table, as in the
+        reference, where such a file codes zero bits; it is turned into len 1, code 0 for that symbol HERE, before encoding, so that
+        the streams can be decoded.  -> (HuffCode used, streams, block_lens)"""
+        a = _u8(data)
+        code = HuffCode.new(a, huffman_size)
+        if len(a) and not any(code.lens):
+            code = code.with_single_symbol(int(a[0]))
+        out, lens = self.aoh_encode_blocks(code, ctx_bits, a, block_size)
+        return code, out, lens
+
     # ---- reference container (main.rs:89-144) ------------------------------
     def compress(self, data, model=None):
         """compress(): b"w30i" + u64 BE len + one stream."""
@@ -314,6 +383,37 @@ class Context:
                                               C.byref(olen), st)
         self._chk(rc)
         return olen.value
+
+
+    def aoh_encode_blocks_device(self, code, ctx_bits, d_in, block_size, d_out, d_lens, d_total, stream=None):
+        """w3_aoh_encode_blocks_device: tensors as encode_blocks_device."""
+        st = C.c_void_p(stream) if stream else None
+        self._chk(self.lib.w3_aoh_encode_blocks_device(self.h, C.byref(code.table), ctx_bits, C.c_void_p(d_in.data_ptr()), d_in.numel(), block_size,
+                                                       C.c_void_p(d_out.data_ptr()), d_out.numel(), C.c_void_p(d_lens.data_ptr()),
+                                                       C.c_void_p(d_total.data_ptr()), st))
+
+    def aoh_decode_blocks_device(self, code, ctx_bits, d_comp, d_lens, block_size, orig_len, d_out, stream=None):
+        st = C.c_void_p(stream) if stream else None
+        self._chk(self.lib.w3_aoh_decode_blocks_device(self.h, C.byref(code.table), ctx_bits, C.c_void_p(d_comp.data_ptr()), d_comp.numel(),
+                                                       C.c_void_p(d_lens.data_ptr()), d_lens.numel(), block_size, orig_len,
+                                                       C.c_void_p(d_out.data_ptr()), st))
+
+    def aoh_encode_stats_device(self, code, ctx_bits, d_in, block_size, d_bits, stream=None):
+        """d_bits: int32/uint32[nb] CUDA tensor receiving the ACStats bit counts."""
+        st = C.c_void_p(stream) if stream else None
+        self._chk(self.lib.w3_aoh_encode_stats_device(self.h, C.byref(code.table), ctx_bits, C.c_void_p(d_in.data_ptr()), d_in.numel(), block_size,
+                                                      C.c_void_p(d_bits.data_ptr()), st))
+
+    def sweep_ac_over_huffman_device(self, d_in, block_size, codes, configs):
+        """sweep_ac_over_huffman on a torch.uint8 CUDA tensor.  -> np.uint32[len(configs)][nb] (host)"""
+        n = d_in.numel()
+        nb = (n + block_size - 1) // block_size if block_size else 0
+        tabs, ci, cb = self._aoh_cfgs(codes, configs)
+        out = np.zeros((len(configs), max(nb, 1)), dtype=np.uint32)
+        self._chk(self.lib.w3_sweep_ac_over_huffman_device(self.h, C.c_void_p(d_in.data_ptr()), n, block_size, tabs, len(codes),
+                                                           ci.ctypes.data_as(C.c_void_p), cb.ctypes.data_as(C.c_void_p), len(configs),
+                                                           out.ctypes.data_as(C.c_void_p)))
+        return out[:, :nb]
 
 
 def encode_blocks_sharded_device(ctxs, model, d_ins, block_size, d_out, d_lens, root=0, transport="auto"):

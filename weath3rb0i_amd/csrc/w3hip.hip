@@ -23,6 +23,7 @@
 #include "w3_twophase.h"
 #include "w3_selftest.h"
 #include "w3_sweep.h"
+#include "w3_aoh.h"
 #include "w3_rccl.h"
 
 using namespace w3;
@@ -98,6 +99,7 @@ struct w3_ctx {
     hipEvent_t ev[W3_NEV]{};
     // workspace
     DevBuf tables, stripes, lens, offs, total, flag, io_in, io_out, coffs, misc, cm_luts, achash_luts, huff, bits, sweep;
+    DevBuf aoh;   // AC over Huffman (w3_aoh.h): code tables in device form, configurations, block bit lengths, maxima and flags
     // the random-access decode (w3_decode_ranges*): the staging buffer the jobs decode into, the job table + gather pieces (+ for the
     // host variant the compact length table and the selected streams behind them), and the host variant's pinned host copy of those
     DevBuf rg_stage, rg_meta;
@@ -243,7 +245,7 @@ extern "C" void w3_ctx_destroy(w3_ctx *ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
     DevBuf *bufs[] = {&ctx->tables, &ctx->stripes, &ctx->lens, &ctx->offs, &ctx->total, &ctx->flag,
-                      &ctx->io_in, &ctx->io_out, &ctx->coffs, &ctx->misc, &ctx->cm_luts, &ctx->achash_luts, &ctx->huff, &ctx->bits, &ctx->sweep,
+                      &ctx->io_in, &ctx->io_out, &ctx->coffs, &ctx->misc, &ctx->cm_luts, &ctx->achash_luts, &ctx->huff, &ctx->bits, &ctx->sweep, &ctx->aoh,
                       &ctx->rg_stage, &ctx->rg_meta};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
@@ -2378,6 +2380,423 @@ extern "C" int w3_sweep_ordern(w3_ctx *ctx, const uint8_t *in, size_t n, size_t 
     ENSURE(ctx, ctx->io_in, n);
     HIPCHK(ctx, hipMemcpy(ctx->io_in.p, in, n, hipMemcpyHostToDevice));
     return w3_sweep_ordern_device(ctx, (const uint8_t *)ctx->io_in.p, n, block_size, bits, aligns, ncfg, block_bits);
+}
+
+// ---------------------------------------------------------------------------
+// AC over Huffman (w3_aoh.h; bin/ac-over-huffman/main.rs:46-89): OrderN(ctx_bits, 0) over the bits of the input's canonical Huffman
+// codes.  One fused lane-per-block kernel for the counting sink, the sweep, encode and decode.
+// ---------------------------------------------------------------------------
+extern "C" int w3_huff_code_table(const uint8_t *buf, size_t n, uint8_t huffman_size, w3_huff_code *out) {
+    if ((!buf && n) || !out) return W3_E_INVALID;
+    uint64_t c64[256] = {0};
+    for (size_t i = 0; i < n; i++) c64[buf[i]]++;                      // histogram (helpers.rs:30-36) of the WHOLE buffer (:74)
+    uint32_t counts[256];
+    for (int s = 0; s < 256; s++) {
+        if (c64[s] > 0xFFFFFFFFull) return W3_E_UNSUPPORTED;           // (the reference counts in u32 too)
+        counts[s] = (uint32_t)c64[s];
+    }
+    uint8_t lens[256];
+    if (!w3huff::code_lengths(counts, 256, huffman_size, lens)) return W3_E_INVALID;   // package_merge's three asserts (:75)
+    for (int s = 0; s < 256; s++)
+        if (lens[s] > 16) return W3_E_INVALID;                          // codes are u16 (package_merge.rs:87)
+    w3aoh::canonical(lens, out);                                        // :76
+    return W3_OK;
+}
+
+extern "C" size_t w3_aoh_max_compressed_size(size_t n, size_t block_size, const w3_huff_code *code) {
+    if (block_size == 0 || !w3aoh::valid(code)) return 0;
+    const size_t nb = (n + block_size - 1) / block_size;
+    return 2 * (size_t)w3aoh::max_len(code) * n + 8 * nb + 8;           // 16 output bits per coded bit, flush bytes per block
+}
+
+// argument checks shared by the family; *max_len_out = the longest code of the (first) table
+static int aoh_check(w3_ctx *ctx, const w3_huff_code *codes, size_t n_codes, const uint8_t *ctx_bits, size_t ncfg, size_t n, size_t block_size,
+                     bool one_device) {
+    int rc = check_args(ctx, n, block_size, one_device);
+    if (rc) return rc;
+    if ((rc = jobs_idle(ctx))) return rc;
+    if (ctx->opt_path == W3_PATH_TWOPHASE) { ctx->err = "AC over Huffman has no two-phase path: W3_PATH_AUTO or W3_PATH_GENERIC"; return W3_E_UNSUPPORTED; }
+    if (!codes || !ctx_bits) { ctx->err = "null code table or ctx_bits"; return W3_E_INVALID; }
+    for (size_t k = 0; k < n_codes; k++) {
+        if (!w3aoh::valid(codes + k)) { ctx->err = "code table " + std::to_string(k) + " is not a canonical code (w3hip.h: Validation)"; return W3_E_INVALID; }
+        if ((uint64_t)block_size * w3aoh::max_len(codes + k) >= (1ull << 32)) { ctx->err = "block_size x max code length must be below 2^32"; return W3_E_INVALID; }
+    }
+    for (size_t c = 0; c < ncfg; c++)   // OrderN::new(ctx_bits, 0): masks are u32, bits - align <= 31 (ordern.rs:35-43)
+        if (ctx_bits[c] < 1 || ctx_bits[c] > 31) { ctx->err = "ctx_bits must be in 1..31"; return W3_E_INVALID; }
+    return W3_OK;
+}
+
+struct AohPrep {
+    AohDev *d_codes = nullptr; AohCfg *d_cfg = nullptr;
+    uint32_t *d_L = nullptr, *d_max = nullptr, *d_flags = nullptr;
+    std::vector<uint32_t> max_l, flags;   // per code table: the call's largest L_b; 1 = the input holds a byte with len 0
+};
+
+// Code tables to the device; with d_in, the length pre-pass (k_aoh_lens).  Synchronises the stream.
+static int aoh_prepare(w3_ctx *ctx, hipStream_t s, const w3_huff_code *codes, size_t n_codes, size_t ncfg, uint32_t nb, const uint8_t *d_in, size_t n,
+                       size_t block_size, AohPrep &P) {
+    auto up16 = [](size_t v) { return (v + 15) / 16 * 16; };
+    const size_t o_cfg = up16(n_codes * sizeof(AohDev)), o_L = o_cfg + up16(ncfg * sizeof(AohCfg)), o_max = o_L + up16(n_codes * (size_t)nb * 4),
+                 o_flags = o_max + up16(n_codes * 4), total = o_flags + up16(n_codes * 4);
+    ENSURE(ctx, ctx->aoh, total);
+    uint8_t *base = (uint8_t *)ctx->aoh.p;
+    P.d_codes = (AohDev *)base; P.d_cfg = (AohCfg *)(base + o_cfg); P.d_L = (uint32_t *)(base + o_L);
+    P.d_max = (uint32_t *)(base + o_max); P.d_flags = (uint32_t *)(base + o_flags);
+    std::vector<AohDev> h(n_codes);
+    for (size_t k = 0; k < n_codes; k++) w3aoh::to_device_form(codes + k, &h[k]);
+    HIPCHK(ctx, hipMemcpyAsync(P.d_codes, h.data(), n_codes * sizeof(AohDev), hipMemcpyHostToDevice, s));
+    P.max_l.assign(n_codes, 0); P.flags.assign(n_codes, 0);
+    if (d_in) {
+        HIPCHK(ctx, hipMemsetAsync(P.d_max, 0, total - o_max, s));
+        hipLaunchKernelGGL(k_aoh_lens, dim3(std::min<uint32_t>(nb, 4096u), (unsigned)n_codes), dim3(64), 0, s, d_in, (uint64_t)n, (uint32_t)block_size, nb,
+                           (const AohDev *)P.d_codes, P.d_L, P.d_max, P.d_flags);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(P.max_l.data(), P.d_max, n_codes * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(P.flags.data(), P.d_flags, n_codes * 4, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(s));   // (h is host memory of this frame)
+    return W3_OK;
+}
+
+// Launch k_aoh<MODE> for configurations cfg[] (ctx_bits and code_idx set) x blocks [0, nb): per lane a direct Counter table of
+// 4 << ctx_bits bytes or, when that is smaller, the exact map with next_pow2(2 x steps[c]) slots of 8 bytes (steps[c]: the most
+// steps one lane of configuration c can take).  As many whole configurations per launch as fit the memory budget (the batching of
+// w3_sweep_ordern_device); a configuration whose tables alone exceed it goes in batches of blocks.  Tables are zero-filled per batch.
+template <int MODE>
+static int aoh_launch(w3_ctx *ctx, hipStream_t s, AohArgs a, AohPrep &P, std::vector<AohCfg> &cfg, const std::vector<uint64_t> &steps, uint32_t nb) {
+    const size_t ncfg = cfg.size();
+    for (size_t c = 0; c < ncfg; c++) {
+        const uint64_t slots = std::max<uint64_t>(1024, next_pow2(2 * steps[c])), hash_bytes = slots * 8, direct = 4ull << cfg[c].ctx_bits;
+        AohCfg &cf = cfg[c];
+        cf.use_hash = direct > hash_bytes; cf.pad = 0;
+        cf.hash_mask = (uint32_t)(slots - 1); cf.ctx_mask = (uint32_t)((1ull << cf.ctx_bits) - 1ull);
+        cf.stride = cf.use_hash ? hash_bytes : std::max<uint64_t>(direct, 16);
+    }
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(ctx, hipMemGetInfo(&free_b, &total_b));
+    uint64_t budget = std::min<uint64_t>((uint64_t)(free_b + ctx->tables.cap) * 3 / 4, 200ull << 30);
+    struct Batch { size_t c0, c1; uint32_t first_block, n_lanes; uint64_t used; };
+    std::vector<Batch> plan;
+    for (;;) {
+        plan.clear();
+        uint64_t need = 0;
+        bool fits = true;
+        for (size_t c0 = 0; c0 < ncfg && fits;) {
+            if (cfg[c0].stride * nb <= budget) {                       // whole configurations
+                uint64_t used = 0;
+                size_t c1 = c0;
+                for (; c1 < ncfg && used + cfg[c1].stride * nb <= budget; c1++) { cfg[c1].base = used; used += cfg[c1].stride * nb; }
+                plan.push_back({c0, c1, 0u, nb, used});
+                need = std::max(need, used);
+                c0 = c1;
+            } else {                                                   // one configuration, batches of blocks
+                uint64_t lanes = budget / cfg[c0].stride;
+                if (lanes >= 64) lanes = lanes / 64 * 64;
+                if (lanes == 0) { fits = false; break; }
+                cfg[c0].base = 0;
+                for (uint32_t b0 = 0; b0 < nb; b0 += (uint32_t)lanes) {
+                    const uint32_t cnt = (uint32_t)std::min<uint64_t>(lanes, nb - b0);
+                    plan.push_back({c0, c0 + 1, b0, cnt, cfg[c0].stride * cnt});
+                    need = std::max(need, cfg[c0].stride * cnt);
+                }
+                c0++;
+            }
+        }
+        if (!fits) { ctx->err = "the Counter table of one lane does not fit the device budget"; return W3_E_NOMEM; }
+        const int rc = ensure(ctx, ctx->tables, (size_t)need);
+        if (rc == W3_OK) break;
+        if (rc != W3_E_NOMEM || budget < (1ull << 20)) return rc;
+        budget /= 2;   // (one hipMalloc of that size can fail although hipMemGetInfo calls the memory free: table_budget)
+    }
+    HIPCHK(ctx, hipMemcpy(P.d_cfg, cfg.data(), ncfg * sizeof(AohCfg), hipMemcpyHostToDevice));
+    a.cfg = P.d_cfg; a.codes = P.d_codes; a.tables = (uint8_t *)ctx->tables.p; a.nblocks = nb;
+    for (const Batch &bt : plan) {
+        HIPCHK(ctx, hipMemsetAsync(ctx->tables.p, 0, (size_t)bt.used, s));
+        a.first_cfg = (uint32_t)bt.c0; a.first_block = bt.first_block; a.n_lanes = bt.n_lanes; a.waves_per_cfg = (bt.n_lanes + 63) / 64;
+        hipLaunchKernelGGL(k_aoh<MODE>, dim3((unsigned)((bt.c1 - bt.c0) * a.waves_per_cfg)), dim3(64), 0, s, a);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    return W3_OK;
+}
+
+// Code blocks [0, nb) of d_in into ctx->stripes (stride cap_out), lengths to d_lens; d_bits (or null) gets the ACStats bit counts.
+static int aoh_encode_stripes(w3_ctx *ctx, hipStream_t s, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *d_in, size_t n, size_t block_size,
+                              uint32_t nb, uint32_t *d_lens, uint32_t *d_bits, uint32_t &cap_out) {
+    AohPrep P;
+    int rc = aoh_prepare(ctx, s, code, 1, 1, nb, d_in, n, block_size, P);
+    if (rc) return rc;
+    if (P.flags[0]) { ctx->err = "the input holds a byte whose code length is 0: the output could not be decoded"; return W3_E_INVALID; }
+    // a Counter-coded stream rarely exceeds the Huffman bits it codes; 16 output bits per coded bit is the hard bound (retry size)
+    const uint64_t l_bytes = ((uint64_t)P.max_l[0] + 7) / 8;
+    const uint64_t worst = (16 * l_bytes + 16 + 15) / 16 * 16;
+    if (worst > 0xFFFFFFF0ull) { ctx->err = "block too large for the worst-case stripe"; return W3_E_UNSUPPORTED; }
+    uint64_t cap = std::min<uint64_t>((2 * l_bytes + 64 + 15) / 16 * 16, worst);
+    ENSURE(ctx, ctx->flag, 16);
+    std::vector<AohCfg> cfg(1);
+    std::vector<uint64_t> steps(1, P.max_l[0]);
+    for (int attempt = 0; attempt < 2; attempt++) {
+        ENSURE(ctx, ctx->stripes, (size_t)nb * cap);
+        HIPCHK(ctx, hipMemsetAsync(ctx->flag.p, 0, 16, s));
+        memset(&cfg[0], 0, sizeof cfg[0]);
+        cfg[0].ctx_bits = ctx_bits; cfg[0].code_idx = 0;
+        AohArgs a;
+        memset(&a, 0, sizeof a);
+        a.in = d_in; a.n = n; a.block_size = (uint32_t)block_size;
+        a.stripes = (uint8_t *)ctx->stripes.p; a.stripe_cap = (uint32_t)cap; a.out_len = d_lens; a.overflow = (uint32_t *)ctx->flag.p; a.out_bits = d_bits;
+        if ((rc = aoh_launch<AOH_ENCODE>(ctx, s, a, P, cfg, steps, nb))) return rc;
+        uint32_t fl = 0;
+        HIPCHK(ctx, hipMemcpyAsync(&fl, ctx->flag.p, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        if (!fl) { cap_out = (uint32_t)cap; return W3_OK; }
+        if (cap == worst) break;
+        cap = worst;
+    }
+    ctx->err = "stripe overflow at the worst-case bound (internal error)";
+    return W3_E_HIP;
+}
+
+static void aoh_timing(w3_ctx *ctx, bool packed) {
+    ctx->timing.path = W3_PATH_GENERIC; ctx->timing.n_parts = 1;
+    if (!ctx->opt_timing) return;
+    ctx->timing.generic_ms = elapsed_ev(ctx->ev, W3_EV_PREDICT);
+    ctx->timing.pack_ms = packed ? elapsed_ev(ctx->ev, W3_EV_PACK) : 0.f;
+    ctx->timing.total_ms = elapsed_ev(ctx->ev, W3_EV_TOTAL);
+}
+
+extern "C" int w3_aoh_encode_blocks_device(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *d_in, size_t n, size_t block_size,
+                                           uint8_t *d_out, size_t out_cap, uint32_t *d_block_lens, uint64_t *d_total, void *stream) {
+    int rc = aoh_check(ctx, code, 1, &ctx_bits, 1, n, block_size, true);
+    if (rc) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    const uint32_t nb = (uint32_t)((n + block_size - 1) / block_size);
+    memset(&ctx->timing, 0, sizeof ctx->timing);
+    ENSURE(ctx, ctx->total, 8);
+    uint64_t *total_p = d_total ? d_total : (uint64_t *)ctx->total.p;
+    if (nb == 0) {
+        HIPCHK(ctx, hipMemsetAsync(total_p, 0, 8, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        return W3_OK;
+    }
+    if (!d_in || !d_block_lens || !d_out) return W3_E_INVALID;
+    hipEvent_t *evp = ctx->opt_timing ? ctx->ev : nullptr;
+    if (evp) { HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_TOTAL], s)); HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_PREDICT], s)); }
+    uint32_t cap = 0;
+    if ((rc = aoh_encode_stripes(ctx, s, code, ctx_bits, d_in, n, block_size, nb, d_block_lens, nullptr, cap))) return rc;
+    if (evp) { HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_PREDICT + 1], s)); HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_PACK], s)); }
+    JobRef J = jobref(ctx, 0);
+    if ((rc = run_pack(ctx, J, s, (const uint8_t *)ctx->stripes.p, cap, d_block_lens, nb, d_out, out_cap, total_p))) return rc;
+    if (evp) { HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_PACK + 1], s)); HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_TOTAL + 1], s)); }
+    uint64_t total = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&total, total_p, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    aoh_timing(ctx, true);
+    if (total > out_cap) { ctx->err = "out_cap too small"; return W3_E_NOSPACE; }
+    return W3_OK;
+}
+
+extern "C" int w3_aoh_encode_blocks(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *in, size_t n, size_t block_size,
+                                    uint8_t *out, size_t out_cap, size_t *out_len, uint32_t *block_lens) {
+    int rc = aoh_check(ctx, code, 1, &ctx_bits, 1, n, block_size, false);
+    if (rc) return rc;
+    if (out_len) *out_len = 0;
+    const size_t nb = (n + block_size - 1) / block_size;
+    if (nb == 0) return W3_OK;
+    if (!in || !block_lens || !out_len) return W3_E_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    memset(&ctx->timing, 0, sizeof ctx->timing);
+    const size_t run = host_call_cap_blocks(block_size);   // any length: device calls of at most 2 GiB of input, one after the other
+    JobRef J = jobref(ctx, 0);
+    size_t off = 0;
+    uint32_t parts = 0;
+    for (size_t b0 = 0; b0 < nb; b0 += run, parts++) {
+        const size_t b1 = std::min(nb, b0 + run), lo = b0 * block_size, hi = std::min(n, b1 * block_size);
+        const uint32_t pnb = (uint32_t)(b1 - b0);
+        ENSURE(ctx, ctx->io_in, hi - lo);
+        ENSURE(ctx, ctx->lens, (size_t)pnb * 4);
+        ENSURE(ctx, ctx->total, 8);
+        HIPCHK(ctx, hipMemcpyAsync(ctx->io_in.p, in + lo, hi - lo, hipMemcpyHostToDevice, s));
+        uint32_t cap = 0;
+        if ((rc = aoh_encode_stripes(ctx, s, code, ctx_bits, (const uint8_t *)ctx->io_in.p, hi - lo, block_size, pnb, (uint32_t *)ctx->lens.p, nullptr, cap))) return rc;
+        // the piece's size first (the packed buffer is sized from it), then the pack
+        ENSURE(ctx, J.offs, (size_t)pnb * 8);
+        hipLaunchKernelGGL(k_scan_lens, dim3(1), dim3(1024), 0, s, (const uint32_t *)ctx->lens.p, (uint64_t *)J.offs.p, (uint64_t *)ctx->total.p, pnb);
+        uint64_t total = 0;
+        HIPCHK(ctx, hipMemcpyAsync(&total, ctx->total.p, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(block_lens + b0, ctx->lens.p, (size_t)pnb * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        if (out && off + total <= out_cap) {   // (once the caller's buffer is full the later pieces are still coded: *out_len must hold the need)
+            ENSURE(ctx, ctx->io_out, (size_t)total);
+            if ((rc = run_pack(ctx, J, s, (const uint8_t *)ctx->stripes.p, cap, (const uint32_t *)ctx->lens.p, pnb, (uint8_t *)ctx->io_out.p, (size_t)total, (uint64_t *)ctx->total.p))) return rc;
+            HIPCHK(ctx, hipMemcpyAsync(out + off, ctx->io_out.p, (size_t)total, hipMemcpyDeviceToHost, s));
+            HIPCHK(ctx, hipStreamSynchronize(s));
+        }
+        off += (size_t)total;
+    }
+    ctx->timing.path = W3_PATH_GENERIC; ctx->timing.n_parts = parts;
+    *out_len = off;
+    if (off > out_cap || !out) { ctx->err = "out_cap too small"; return W3_E_NOSPACE; }
+    return W3_OK;
+}
+
+extern "C" int w3_aoh_decode_blocks_device(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *d_in, size_t in_len,
+                                           const uint32_t *d_block_lens, size_t nblocks, size_t block_size, uint64_t orig_len, uint8_t *d_out, void *stream) {
+    int rc = aoh_check(ctx, code, 1, &ctx_bits, 1, (size_t)orig_len, block_size, true);
+    if (rc) return rc;
+    const uint64_t nb = (orig_len + block_size - 1) / block_size;
+    if (nb != nblocks) { ctx->err = "nblocks does not match orig_len/block_size"; return W3_E_INVALID; }
+    if (nb == 0) return W3_OK;
+    if (!d_in || !d_block_lens || !d_out) return W3_E_INVALID;
+    const unsigned max_len = w3aoh::max_len(code);
+    if (max_len == 0) { ctx->err = "a table without symbols decodes nothing"; return W3_E_INVALID; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    {   // the length table must not claim more than the caller's buffer holds (w3_decode_blocks_device)
+        ENSURE(ctx, ctx->coffs, (size_t)nb * 8);
+        ENSURE(ctx, ctx->total, 8);
+        hipLaunchKernelGGL(k_scan_lens, dim3(1), dim3(1024), 0, s, d_block_lens, (uint64_t *)ctx->coffs.p, (uint64_t *)ctx->total.p, (uint32_t)nb);
+        uint64_t total = 0;
+        HIPCHK(ctx, hipMemcpyAsync(&total, ctx->total.p, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        if (total > in_len) { ctx->err = "block length table claims " + std::to_string(total) + " compressed bytes, the buffer holds " + std::to_string(in_len); return W3_E_FORMAT; }
+    }
+    AohPrep P;
+    if ((rc = aoh_prepare(ctx, s, code, 1, 1, (uint32_t)nb, nullptr, (size_t)orig_len, block_size, P))) return rc;
+    std::vector<AohCfg> cfg(1);
+    memset(&cfg[0], 0, sizeof cfg[0]);
+    cfg[0].ctx_bits = ctx_bits;
+    // the decoder does not know a block's bit count before it has decoded it: the map is sized for the most steps a block can take
+    std::vector<uint64_t> steps(1, (uint64_t)std::min<uint64_t>(block_size, orig_len) * max_len);
+    AohArgs a;
+    memset(&a, 0, sizeof a);
+    a.n = orig_len; a.block_size = (uint32_t)block_size;
+    a.cin = d_in; a.coffs = (const uint64_t *)ctx->coffs.p; a.clens = d_block_lens; a.dout = d_out;
+    if ((rc = aoh_launch<AOH_DECODE>(ctx, s, a, P, cfg, steps, (uint32_t)nb))) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return W3_OK;
+}
+
+extern "C" int w3_aoh_decode_blocks(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *in, size_t in_len, const uint32_t *block_lens,
+                                    size_t nblocks, size_t block_size, uint64_t orig_len, uint8_t *out) {
+    int rc = aoh_check(ctx, code, 1, &ctx_bits, 1, (size_t)orig_len, block_size, false);
+    if (rc) return rc;
+    if ((uint64_t)nblocks != (orig_len + block_size - 1) / block_size) { ctx->err = "nblocks does not match orig_len/block_size"; return W3_E_INVALID; }
+    if (nblocks == 0) return W3_OK;
+    if (!in || !block_lens || !out) return W3_E_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t run = host_call_cap_blocks(block_size);
+    uint64_t coff = 0;
+    for (size_t b0 = 0; b0 < nblocks; b0 += run) {
+        const size_t b1 = std::min(nblocks, b0 + run);
+        uint64_t clen = 0;
+        for (size_t b = b0; b < b1; b++) clen += block_lens[b];
+        if (coff + clen > in_len) { ctx->err = "block length table claims more compressed bytes than the buffer holds"; return W3_E_FORMAT; }
+        const uint64_t o0 = (uint64_t)b0 * block_size, o1 = std::min<uint64_t>(orig_len, (uint64_t)b1 * block_size);
+        ENSURE(ctx, ctx->io_in, std::max<size_t>((size_t)clen, 16));
+        ENSURE(ctx, ctx->io_out, (size_t)(o1 - o0));
+        ENSURE(ctx, ctx->lens, (b1 - b0) * 4);
+        HIPCHK(ctx, hipMemcpy(ctx->io_in.p, in + coff, (size_t)clen, hipMemcpyHostToDevice));
+        HIPCHK(ctx, hipMemcpy(ctx->lens.p, block_lens + b0, (b1 - b0) * 4, hipMemcpyHostToDevice));
+        rc = w3_aoh_decode_blocks_device(ctx, code, ctx_bits, (const uint8_t *)ctx->io_in.p, (size_t)clen, (const uint32_t *)ctx->lens.p, b1 - b0, block_size,
+                                         o1 - o0, (uint8_t *)ctx->io_out.p, ctx->stream);
+        if (rc) return rc;
+        HIPCHK(ctx, hipMemcpy(out + o0, ctx->io_out.p, (size_t)(o1 - o0), hipMemcpyDeviceToHost));
+        coff += clen;
+    }
+    return W3_OK;
+}
+
+// the counting sink for configurations (codes[code_idx[c]], ctx_bits[c]) on a device-resident input: d_bits[ncfg][nb] (device)
+static int aoh_stats_run(w3_ctx *ctx, hipStream_t s, const uint8_t *d_in, size_t n, size_t block_size, uint32_t nb, const w3_huff_code *codes, size_t n_codes,
+                         const uint8_t *code_idx, const uint8_t *ctx_bits, size_t ncfg, uint32_t *d_bits) {
+    AohPrep P;
+    int rc = aoh_prepare(ctx, s, codes, n_codes, ncfg, nb, d_in, n, block_size, P);
+    if (rc) return rc;
+    std::vector<AohCfg> cfg(ncfg);
+    std::vector<uint64_t> steps(ncfg);
+    for (size_t c = 0; c < ncfg; c++) {
+        memset(&cfg[c], 0, sizeof cfg[c]);
+        cfg[c].ctx_bits = ctx_bits[c]; cfg[c].code_idx = code_idx ? code_idx[c] : 0;
+        steps[c] = P.max_l[cfg[c].code_idx];
+    }
+    AohArgs a;
+    memset(&a, 0, sizeof a);
+    a.in = d_in; a.n = n; a.block_size = (uint32_t)block_size; a.out_bits = d_bits;
+    return aoh_launch<AOH_STATS>(ctx, s, a, P, cfg, steps, nb);
+}
+
+extern "C" int w3_aoh_encode_stats_device(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *d_in, size_t n, size_t block_size,
+                                          uint32_t *d_block_bits, void *stream) {
+    int rc = aoh_check(ctx, code, 1, &ctx_bits, 1, n, block_size, true);
+    if (rc) return rc;
+    const size_t nb = (n + block_size - 1) / block_size;
+    if (nb == 0) return W3_OK;
+    if (!d_in || !d_block_bits) return W3_E_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    memset(&ctx->timing, 0, sizeof ctx->timing);
+    hipEvent_t *evp = ctx->opt_timing ? ctx->ev : nullptr;
+    if (evp) { HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_TOTAL], s)); HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_PREDICT], s)); }
+    if ((rc = aoh_stats_run(ctx, s, d_in, n, block_size, (uint32_t)nb, code, 1, nullptr, &ctx_bits, 1, d_block_bits))) return rc;
+    if (evp) { HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_PREDICT + 1], s)); HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_TOTAL + 1], s)); }
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    aoh_timing(ctx, false);
+    return W3_OK;
+}
+
+extern "C" int w3_aoh_encode_stats(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *in, size_t n, size_t block_size,
+                                   uint32_t *block_bits) {
+    int rc = aoh_check(ctx, code, 1, &ctx_bits, 1, n, block_size, false);
+    if (rc) return rc;
+    const size_t nb = (n + block_size - 1) / block_size;
+    if (nb == 0) return W3_OK;
+    if (!in || !block_bits) return W3_E_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t run = host_call_cap_blocks(block_size);
+    for (size_t b0 = 0; b0 < nb; b0 += run) {
+        const size_t b1 = std::min(nb, b0 + run), lo = b0 * block_size, hi = std::min(n, b1 * block_size);
+        ENSURE(ctx, ctx->io_in, hi - lo);
+        ENSURE(ctx, ctx->bits, (b1 - b0) * 4);
+        HIPCHK(ctx, hipMemcpy(ctx->io_in.p, in + lo, hi - lo, hipMemcpyHostToDevice));
+        if ((rc = w3_aoh_encode_stats_device(ctx, code, ctx_bits, (const uint8_t *)ctx->io_in.p, hi - lo, block_size, (uint32_t *)ctx->bits.p, ctx->stream))) return rc;
+        HIPCHK(ctx, hipMemcpy(block_bits + b0, ctx->bits.p, (b1 - b0) * 4, hipMemcpyDeviceToHost));
+    }
+    return W3_OK;
+}
+
+// the driver's main (:13-44) as one call: every (huffman table, ctx_bits) x block through the counting sink
+extern "C" int w3_sweep_ac_over_huffman_device(w3_ctx *ctx, const uint8_t *d_in, size_t n, size_t block_size, const w3_huff_code *codes, size_t n_codes,
+                                               const uint8_t *code_idx, const uint8_t *ctx_bits, size_t ncfg, uint32_t *block_bits) {
+    if (!ctx) return W3_E_INVALID;
+    if (n_codes == 0 || n_codes > 64 || ncfg > 4096 || (ncfg && !code_idx)) { ctx->err = "1..64 code tables, at most 4096 configurations"; return W3_E_INVALID; }
+    int rc = aoh_check(ctx, codes, n_codes, ctx_bits, ncfg, n, block_size, true);
+    if (rc) return rc;
+    for (size_t c = 0; c < ncfg; c++)
+        if (code_idx[c] >= n_codes) { ctx->err = "code_idx out of range"; return W3_E_INVALID; }
+    const uint32_t nb = (uint32_t)((n + block_size - 1) / block_size);
+    if (nb == 0 || ncfg == 0) return W3_OK;
+    if (!d_in || !block_bits) return W3_E_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    ENSURE(ctx, ctx->sweep, ncfg * (size_t)nb * 4);
+    if ((rc = aoh_stats_run(ctx, s, d_in, n, block_size, nb, codes, n_codes, code_idx, ctx_bits, ncfg, (uint32_t *)ctx->sweep.p))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(block_bits, ctx->sweep.p, ncfg * (size_t)nb * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return W3_OK;
+}
+
+extern "C" int w3_sweep_ac_over_huffman(w3_ctx *ctx, const uint8_t *in, size_t n, size_t block_size, const w3_huff_code *codes, size_t n_codes,
+                                        const uint8_t *code_idx, const uint8_t *ctx_bits, size_t ncfg, uint32_t *block_bits) {
+    int rc = check_args(ctx, n, block_size);
+    if (rc) return rc;
+    if ((rc = jobs_idle(ctx))) return rc;
+    if (n == 0 || ncfg == 0) return W3_OK;
+    if (!in) return W3_E_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ENSURE(ctx, ctx->io_in, n);
+    HIPCHK(ctx, hipMemcpy(ctx->io_in.p, in, n, hipMemcpyHostToDevice));
+    return w3_sweep_ac_over_huffman_device(ctx, (const uint8_t *)ctx->io_in.p, n, block_size, codes, n_codes, code_idx, ctx_bits, ncfg, block_bits);
 }
 
 // ---------------------------------------------------------------------------

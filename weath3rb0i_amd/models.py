@@ -119,6 +119,50 @@ class HuffHistory:
         return o
 
 
+class HuffCode:
+    """The code table of the AC-over-Huffman driver (bin/ac-over-huffman/main.rs:74-76): canonical(package_merge(histogram(buf),
+    huffman_size)), codes NOT bit-reversed, len 0 = symbol absent.  new() builds it on the host (w3_huff_code_table: histogram of the
+    whole buffer; among equal counts / lengths ascending symbol order, as HuffHistory); from_tables() takes ready (code, len) lists,
+    e.g. the crate's own canonical() output."""
+
+    def __init__(self, data, huffman_size):
+        a = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+        self.table = L.HuffCode()
+        rc = L.load().w3_huff_code_table(a.ctypes.data_as(C.c_void_p), len(a), huffman_size, C.byref(self.table))
+        if rc:
+            raise W3Error(rc, "package_merge: no symbols, or max length too big / too small for the alphabet")
+
+    @classmethod
+    def new(cls, data, huffman_size):
+        return cls(data, huffman_size)
+
+    @classmethod
+    def from_tables(cls, codes, lens):
+        o = cls.__new__(cls)
+        o.table = L.HuffCode()
+        for i in range(256):
+            o.table.code[i], o.table.len[i] = codes[i], lens[i]
+        return o
+
+    @property
+    def codes(self):
+        return list(self.table.code)
+
+    @property
+    def lens(self):
+        return list(self.table.len)
+
+    def valid(self):
+        """w3hip.h "Validation" (w3_aoh_max_compressed_size returns 0 for a table the entry points would refuse)"""
+        return L.load().w3_aoh_max_compressed_size(1, 1, C.byref(self.table)) != 0
+
+    def with_single_symbol(self, symbol):
+        """len 1, code 0 for `symbol`, every other symbol absent"""
+        lens = [0] * 256
+        lens[symbol] = 1
+        return HuffCode.from_tables([0] * 256, lens)
+
+
 class Model:
     """trait Model (models/mod.rs:12-15), as a spec tree."""
     _tls = threading.local()   # .huff_index: HuffHistory object -> slot in w3_model_spec::huff while spec() walks the tree (per thread:

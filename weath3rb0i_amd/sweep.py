@@ -1,6 +1,7 @@
 """Parameter sweeps on the device — the reference's research drivers `src/bin/ordern/main.rs:9-58` (one launch for every
 configuration), `src/bin/entropy-hashing-ac/main.rs` and `src/bin/entropy-hashing-huff/main.rs` (one counting-sink encode per
-configuration: every one of them runs on the two-phase path since round 3).
+configuration: every one of them runs on the two-phase path since round 3) and `src/bin/ac-over-huffman/main.rs` (one call for every
+configuration: `w3_sweep_ac_over_huffman`).
 
 The reference runs `OrderN::new(ctx_bits, alignment_bits)` over one file for ctx_bits 8..=30 x alignment_bits 0..=4,
 three times each, prints `[ordern] [ctx: B, align: A] csize: N (ratio: r), ctime: t (t/bit per bit)` for the fastest run
@@ -153,13 +154,65 @@ def sweep_entropy_huff(ctx, data, block_size=65536, rem_huff_sizes=range(7, 13),
     return best[0], params[0], table
 
 
+def sweep_ac_over_huffman(ctx, data, block_size=65536, huffman_sizes=range(7, 16), ctx_bits=range(8, 31), repeats=1, out=print):
+    """`src/bin/ac-over-huffman/main.rs:13-67`: OrderN(ctx_bits, 0) over the bits of the input's canonical Huffman codes
+    (package_merge(histogram(buf), huffman_size), :74-76) for huffman_size 7..=15 x ctx_bits 8..=30 through the counting sink — ALL
+    configurations in one device call (`w3_sweep_ac_over_huffman`: lanes = configurations x blocks), fastest of `repeats`; ctime is the
+    call's time divided by the number of configurations.  The reference's lines (:33-41, :57-65) and tie rule (:25-31: a later
+    configuration replaces the best on equality).  A huffman_size too small for the alphabet (the reference panics in package_merge)
+    prints a line and is skipped.  Returns (global best csize, (huffman_size, ctx_bits), {(H, B): csize})."""
+    levels = 2
+    best = [len(data)] * levels
+    params = [(0, 0)] * levels
+    table = {}
+    codes, sizes = [], []
+    for h in huffman_sizes:
+        try:
+            codes.append(models.HuffCode.new(data, h))
+            sizes.append(h)
+        except models.W3Error:
+            pass
+    ctx_bits = list(ctx_bits)
+    configs = [(k, b) for k in range(len(codes)) for b in ctx_bits]
+    pre = {}
+    if configs:
+        dt_best = None
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            bits = ctx.sweep_ac_over_huffman(data, block_size, codes, configs)
+            dt = time.perf_counter() - t0
+            dt_best = dt if dt_best is None else min(dt_best, dt)
+        for (k, b), row in zip(configs, bits):
+            pre[(sizes[k], b)] = (int(row.astype("uint64").sum()) // 8, dt_best / len(configs))   # ACStats::result(): bits / 8 (helpers.rs:70-73)
+    for h in huffman_sizes:
+        best[1] = len(data)
+        params[1] = (0, 0)
+        if h not in sizes:
+            out("[ac-over-huff] [hsize: %2d] length limit too small for the alphabet" % h)
+            continue
+        for b in ctx_bits:
+            res, dt = pre[(h, b)]
+            out("[ac-over-huff] [hsize: %2d, ctx: %2d, align: 0] csize: %d (ratio: %.3f), ctime: %.3fms (%.3fns per bit)"
+                % (h, b, res, res / max(1, len(data)), dt * 1e3, dt * 1e9 / max(1, len(data) * 8)))
+            table[(h, b)] = res
+            for i in range(levels):
+                if res > best[i]:
+                    continue
+                best[i] = res
+                params[i] = (h, b)
+        out("-> best: %d for [hsize: %d] when [ctx: %d, align: 0]" % (best[1], params[1][0], params[1][1]))
+    out("-> gloabl best: %d for [hsize: %d, ctx: %d, align: 0]" % (best[0], params[0][0], params[0][1]))   # (sic, main.rs:39)
+    return best[0], params[0], table
+
+
 def main(argv=None):
     import argparse
     from .api import Context
     ap = argparse.ArgumentParser(description="parameter sweeps of the reference's research drivers on the GPU, block container: "
-                                             "ordern (bin/ordern), eh-ac (bin/entropy-hashing-ac), eh-huff (bin/entropy-hashing-huff)")
+                                             "ordern (bin/ordern), eh-ac (bin/entropy-hashing-ac), eh-huff (bin/entropy-hashing-huff), "
+                                             "ac-huff (bin/ac-over-huffman)")
     ap.add_argument("path")
-    ap.add_argument("--driver", default="ordern", choices=["ordern", "eh-ac", "eh-huff"])
+    ap.add_argument("--driver", default="ordern", choices=["ordern", "eh-ac", "eh-huff", "ac-huff"])
     ap.add_argument("--block-size", type=int, default=65536)
     ap.add_argument("--ctx-bits", default="8:30", help="lo:hi inclusive")
     ap.add_argument("--align-bits", default="0:4", help="lo:hi inclusive")
@@ -174,6 +227,8 @@ def main(argv=None):
             sweep_ordern(ctx, data, args.block_size, range(lo, hi + 1), range(alo, ahi + 1), args.repeats)
         elif args.driver == "eh-ac":
             sweep_entropy_ac(ctx, data, args.block_size, range(lo, hi + 1), range(alo, ahi + 1), args.repeats)
+        elif args.driver == "ac-huff":
+            sweep_ac_over_huffman(ctx, data, args.block_size, ctx_bits=range(lo, hi + 1), repeats=args.repeats)
         else:
             sweep_entropy_huff(ctx, data, args.block_size, ctx_bits=range(lo, hi + 1), repeats=args.repeats)
     finally:
