@@ -169,9 +169,11 @@ enum {
     W3_OPT_FAULT_BLOCK = 10, /* test hook, with W3_OPT_VARIANT bit 32: the one block the injected fault hits (-1 = every block, default) */
     W3_OPT_HOST_CHUNK_BLOCKS = 12, /* w3_encode_blocks: blocks per pipelined piece of a host-buffer call (0 = default: equal pieces of at most
                            4,096 blocks; tests use small values to get ragged pieces) */
-    W3_OPT_FAULT_KERNELS = 13 /* test hook, with W3_OPT_VARIANT bit 32: bit mask (1 .. 7) of the kernels whose returning LDS adds the injected
+    W3_OPT_FAULT_KERNELS = 13, /* test hook, with W3_OPT_VARIANT bit 32: bit mask (1 .. 7) of the kernels whose returning LDS adds the injected
                            fault mis-orders — 1 = k_predict_small's rounds (default), 2 = k_rank_sorted's rounds, 4 = k_partition8's
                            cursor adds (two records of one bin swap their slots in the tile: a permutation, never another index) */
+    W3_OPT_AOH_BATCH_BLOCKS = 14 /* test hook in the manner of W3_OPT_HOST_CHUNK_BLOCKS: most blocks per batch of the two-phase form of AC over
+                           Huffman (0 = default: as many whole blocks as the device memory budget holds; the output is the same) */
 };
 enum { W3_PATH_AUTO = 0, W3_PATH_GENERIC = 1, W3_PATH_TWOPHASE = 2 };
 int         w3_ctx_set_option(w3_ctx *ctx, int opt, int64_t value);
@@ -396,9 +398,17 @@ int w3_sweep_ordern_device(w3_ctx *ctx, const uint8_t *d_in, size_t n, size_t bl
  *   Limits: block_size x max len < 2^32; n < 2^32 - 4096 per DEVICE call, the host-buffer encode / decode / stats take any length in
  *     pieces of at most 2 GiB.  Other conventions as the neighbours': *out_len set even on W3_E_NOSPACE, W3_E_FORMAT for a length table
  *     that claims more than in_len, W3_E_INVALID while a job is in flight.
- *   W3_OPT_PATH: W3_PATH_AUTO and W3_PATH_GENERIC run the fused lane-per-block kernel k_aoh (csrc/w3_aoh.h); a two-phase form (predict
- *     all steps in parallel, code from registers) is not built: W3_PATH_TWOPHASE returns W3_E_UNSUPPORTED for this family.
- *     W3_OPT_TIMING fills generic_ms / pack_ms / total_ms (predict_ms and coder_ms stay 0).
+ *   W3_OPT_PATH, for w3_aoh_encode_blocks[_device] and w3_aoh_encode_stats[_device]: W3_PATH_GENERIC runs the fused lane-per-block
+ *     kernel k_aoh (csrc/w3_aoh.h).  W3_PATH_TWOPHASE runs the two-phase form, for every valid input (never W3_E_UNSUPPORTED):
+ *     k_aoh_pack writes every block's Huffman bit string, k_aoh_predict predicts all its steps with a wavefront per block (64
+ *     time-ordered steps per round, the Counter table private to the resident wavefront), k_aoh_coder codes a block per lane from the
+ *     stored probabilities; workspace = the strings + 2 bytes per coded bit + one table per resident wavefront, a call that exceeds
+ *     the device memory budget goes in batches of whole blocks (W3_OPT_AOH_BATCH_BLOCKS caps a batch, for tests).  The output of the
+ *     two forms is identical.  W3_PATH_AUTO takes the form its rule names (W3_AOH_AUTO_* in csrc/w3_aoh.h: the fused kernel for
+ *     every shape until the two-phase form has been timed); w3_timing.path tells which.  Decode and the sweep IGNORE the option and run k_aoh: the decoder cannot look ahead (a step's
+ *     context is known only when the step before it is decoded), and the sweep already has configurations x blocks lanes.
+ *     W3_OPT_TIMING: the fused form fills generic_ms / pack_ms / total_ms (predict_ms and coder_ms stay 0); the two-phase form fills
+ *     predict_ms (k_aoh_pack + k_aoh_predict), coder_ms, pack_ms, total_ms, predict_bytes and coder_bytes (generic_ms stays 0).
  * w3_aoh_max_compressed_size: upper bound on the concatenated streams (16 output bits per coded bit); 0 = block_size 0 or an INVALID
  * table (needs no device: the way to validate a table).                                                                          */
 typedef struct w3_huff_code { uint16_t code[256]; uint8_t len[256]; } w3_huff_code;

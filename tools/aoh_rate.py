@@ -1,6 +1,7 @@
 """AC-over-Huffman rates (w3_aoh_*; bin/ac-over-huffman/main.rs) on a device-resident enwik-shaped corpus synthesised as bench.py does
 (tools/synth.c seed 1), 64 KiB blocks, at the reference's two best published configurations (hsize 13 / ctx 24 and hsize 12 / ctx 19):
-encode and decode MiB/s on every path that is built, the counting sink, the compressed size beside order012's and OrderN(32, 1)'s on the
+encode and decode MiB/s on every path that is built and under W3_PATH_AUTO (with timing.path, the form it took, and the phases'
+milliseconds of one more call with W3_OPT_TIMING), the counting sink, the compressed size beside order012's and OrderN(32, 1)'s on the
 same input; the wall time of the driver's full sweep (huffman_size 7..15 x ctx_bits 8..30, one call) on 20 MB; and the rate of the tests'
 CPU truth (tests/host/aoh_ref.c, a C restatement of the driver's loop — not the reference) on 16 threads.  Every shape is warmed up
 first; each figure is the median (and min / max) of --runs timed calls, host clock after a synchronise.
@@ -93,13 +94,28 @@ def main():
             d_total = torch.zeros(1, dtype=torch.int64, device="cuda")
             d_bits = torch.zeros(nb, dtype=torch.int32, device="cuda")
             d_back = torch.empty(n, dtype=torch.uint8, device="cuda")
-            for path in paths(ctx, code):
+            ref = None
+            for path in paths(ctx, code) + ["auto"]:
                 ctx.set_path(path)
                 r["encode_" + path] = rate(timed(lambda: ctx.aoh_encode_blocks_device(code, cb, d_in, BS, d_comp, d_lens, d_total), a.runs), n)
                 total = int(d_total.item())
                 r["stats_" + path] = rate(timed(lambda: ctx.aoh_encode_stats_device(code, cb, d_in, BS, d_bits), a.runs), n)
-                r["decode_" + path] = rate(timed(lambda: ctx.aoh_decode_blocks_device(code, cb, d_comp[:total], d_lens, BS, n, d_back), a.runs), n)
-                assert bool((d_back == d_in).all())
+                # one more call of each with W3_OPT_TIMING: the form taken (timing.path) and the phases' milliseconds
+                ctx.set_timing(True)
+                for what, fn in (("encode_", lambda: ctx.aoh_encode_blocks_device(code, cb, d_in, BS, d_comp, d_lens, d_total)),
+                                 ("stats_", lambda: ctx.aoh_encode_stats_device(code, cb, d_in, BS, d_bits))):
+                    fn()
+                    tm = ctx.timing()
+                    r[what + path]["timing"] = {k: (round(tm[k], 3) if isinstance(tm[k], float) else tm[k])
+                                                for k in ("path", "predict_ms", "coder_ms", "pack_ms", "generic_ms", "total_ms", "predict_bytes", "coder_bytes")}
+                ctx.set_timing(False)
+                if path != "auto":   # (decode ignores the option)
+                    r["decode_" + path] = rate(timed(lambda: ctx.aoh_decode_blocks_device(code, cb, d_comp[:total], d_lens, BS, n, d_back), a.runs), n)
+                    assert bool((d_back == d_in).all())
+                # every path writes the same streams
+                sig = (total, int(d_lens.to(torch.int64).sum().item()), int(d_bits.to(torch.int64).sum().item()), int(d_comp[:total].to(torch.int64).sum().item()))
+                ref = ref or sig
+                assert sig == ref, (path, sig, ref)
                 ctx.set_path("auto")
             r["compressed_bytes"] = total
             r["csize"] = int(d_bits.cpu().numpy().view(np.uint32).astype(np.uint64).sum()) // 8

@@ -113,6 +113,10 @@ class Context:
         """W3_OPT_HOST_CHUNK_BLOCKS: blocks per pipelined piece of a host-buffer call (0 = default)."""
         self._chk(self.lib.w3_ctx_set_option(self.h, L.W3_OPT_HOST_CHUNK_BLOCKS, int(blocks)))
 
+    def set_aoh_batch_blocks(self, blocks):
+        """W3_OPT_AOH_BATCH_BLOCKS: most blocks per batch of the two-phase form of AC over Huffman (0 = from the memory budget)."""
+        self._chk(self.lib.w3_ctx_set_option(self.h, L.W3_OPT_AOH_BATCH_BLOCKS, int(blocks)))
+
     def set_timing(self, on=True):
         self._chk(self.lib.w3_ctx_set_option(self.h, L.W3_OPT_TIMING, int(on)))
 

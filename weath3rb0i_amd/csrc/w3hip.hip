@@ -121,6 +121,7 @@ struct w3_ctx {
     hipStream_t s_h2d_own = nullptr, s_d2h_own = nullptr;
     uint64_t hseq = 0;
     uint32_t host_chunk_blocks = 0;                 // W3_OPT_HOST_CHUNK_BLOCKS (0 = auto)
+    uint32_t aoh_batch_blocks = 0;                  // W3_OPT_AOH_BATCH_BLOCKS (0 = from the memory budget)
     // the sampled verification's rotation (w3_verify.h): a number per call, counted per input shape, whichever job slot the call lands
     // on; vcall_pin >= 0: the number the call being made now takes (a redo, or a piece of a host call) instead of a new one
     w3::VerifyCalls vcalls;
@@ -346,6 +347,10 @@ extern "C" int w3_ctx_set_option(w3_ctx *ctx, int opt, int64_t value) {
     case W3_OPT_HOST_CHUNK_BLOCKS:
         if (value < 0 || value > 0x7FFFFFFF) return W3_E_INVALID;
         ctx->host_chunk_blocks = (uint32_t)value;
+        return W3_OK;
+    case W3_OPT_AOH_BATCH_BLOCKS:
+        if (value < 0 || value > 0x7FFFFFFF) return W3_E_INVALID;
+        ctx->aoh_batch_blocks = (uint32_t)value;
         return W3_OK;
     default: return W3_E_INVALID;
     }
@@ -2384,7 +2389,8 @@ extern "C" int w3_sweep_ordern(w3_ctx *ctx, const uint8_t *in, size_t n, size_t 
 
 // ---------------------------------------------------------------------------
 // AC over Huffman (w3_aoh.h; bin/ac-over-huffman/main.rs:46-89): OrderN(ctx_bits, 0) over the bits of the input's canonical Huffman
-// codes.  One fused lane-per-block kernel for the counting sink, the sweep, encode and decode.
+// codes.  One fused lane-per-block kernel for the counting sink, the sweep, encode and decode; encode and the counting sink of one
+// configuration also in the two-phase form (W3_OPT_PATH; aoh_twophase_run).
 // ---------------------------------------------------------------------------
 extern "C" int w3_huff_code_table(const uint8_t *buf, size_t n, uint8_t huffman_size, w3_huff_code *out) {
     if ((!buf && n) || !out) return W3_E_INVALID;
@@ -2415,7 +2421,6 @@ static int aoh_check(w3_ctx *ctx, const w3_huff_code *codes, size_t n_codes, con
     int rc = check_args(ctx, n, block_size, one_device);
     if (rc) return rc;
     if ((rc = jobs_idle(ctx))) return rc;
-    if (ctx->opt_path == W3_PATH_TWOPHASE) { ctx->err = "AC over Huffman has no two-phase path: W3_PATH_AUTO or W3_PATH_GENERIC"; return W3_E_UNSUPPORTED; }
     if (!codes || !ctx_bits) { ctx->err = "null code table or ctx_bits"; return W3_E_INVALID; }
     for (size_t k = 0; k < n_codes; k++) {
         if (!w3aoh::valid(codes + k)) { ctx->err = "code table " + std::to_string(k) + " is not a canonical code (w3hip.h: Validation)"; return W3_E_INVALID; }
@@ -2519,13 +2524,106 @@ static int aoh_launch(w3_ctx *ctx, hipStream_t s, AohArgs a, AohPrep &P, std::ve
     return W3_OK;
 }
 
+// The Counter table of one resident wavefront of k_aoh_predict: direct [2^ctx_bits] where that is no larger than the exact map of
+// k_predict_wave's form (twice as many slots as the call's longest block has steps, and ctx 0's own slot behind them).
+struct AohWaveTable { bool use_hash; uint64_t slots, stride; };
+static AohWaveTable aoh_wave_table(uint8_t ctx_bits, uint64_t max_l) {
+    const uint64_t slots = std::max<uint64_t>(1024, next_pow2(2 * max_l)), hash_bytes = 8 * slots + 16, direct = std::max<uint64_t>(4ull << ctx_bits, 16);
+    AohWaveTable t;
+    t.use_hash = direct > hash_bytes; t.slots = slots; t.stride = t.use_hash ? hash_bytes : direct;
+    return t;
+}
+
+// which form a call takes (W3_OPT_PATH; W3_PATH_AUTO by the measured rule of w3_aoh.h)
+static bool aoh_takes_twophase(const w3_ctx *ctx, uint32_t nb, uint8_t ctx_bits, uint64_t max_l) {
+    if (ctx->opt_path != W3_PATH_AUTO) return ctx->opt_path == W3_PATH_TWOPHASE;
+    return aoh_auto_twophase(nb, ctx_bits, aoh_wave_table(ctx_bits, max_l).use_hash);
+}
+
+// The two-phase form (w3_aoh.h) of encode (STATS = false: into the stripes, as aoh_launch<AOH_ENCODE>) and of the counting sink, one
+// configuration: per batch of whole blocks (w3_aoh_plan.h) k_aoh_pack, k_aoh_predict, k_aoh_coder.  ONE allocation (ctx->tables) holds
+// the plan's offsets, the Counter tables of the resident wavefronts, P and the strings; the budget rule is aoh_launch's, a call whose
+// workspace exceeds it goes in batches (W3_OPT_AOH_BATCH_BLOCKS: the tests' cap on a batch).  With W3_OPT_TIMING the phases' times
+// are added to ctx->timing batch by batch.
+template <bool STATS>
+static int aoh_twophase_run(w3_ctx *ctx, hipStream_t s, AohTwoArgs a, AohPrep &P, uint8_t ctx_bits, uint32_t nb) {
+    std::vector<uint32_t> L(nb);
+    HIPCHK(ctx, hipMemcpyAsync(L.data(), P.d_L, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    const AohWaveTable tk = aoh_wave_table(ctx_bits, P.max_l[0]);
+    auto up256 = [](uint64_t v) { return (v + 255) / 256 * 256; };
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(ctx, hipMemGetInfo(&free_b, &total_b));
+    uint64_t budget = std::min<uint64_t>((uint64_t)(free_b + ctx->tables.cap) * 3 / 4, 200ull << 30);
+    const uint64_t meta = up256((uint64_t)nb * 16);
+    uint64_t resident = 256 * 32;
+    {
+        int per_cu = 0, cus = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_aoh_predict, 64, 0) == hipSuccess && per_cu > 0 &&
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) == hipSuccess && cus > 0)
+            resident = (uint64_t)per_cu * (uint64_t)cus;
+        else (void)hipGetLastError();
+    }
+    AohPlan plan;
+    uint64_t waves = 0, o_P = 0, o_str = 0;
+    for (;;) {
+        // latency-bound: as many wavefronts as the chip holds of this kernel (more would queue behind them with tables of their own), their
+        // tables within half the budget
+        waves = std::min<uint64_t>(std::min<uint64_t>(nb, resident), budget / 2 / tk.stride);
+        if (waves == 0) { ctx->err = "the Counter table of one block (" + std::to_string(tk.stride) + " B) does not fit the device budget"; return W3_E_NOMEM; }
+        o_P = meta + up256(waves * tk.stride);
+        if (o_P + 256 >= budget || !aoh_plan(L.data(), nb, budget - o_P - 256, ctx->aoh_batch_blocks, plan)) {
+            ctx->err = "the bit string and probabilities of one block do not fit the device budget";
+            return W3_E_NOMEM;
+        }
+        o_str = o_P + up256(2 * plan.max_p_steps);
+        const int rc = ensure(ctx, ctx->tables, (size_t)(o_str + plan.max_str_bytes));
+        if (rc == W3_OK) break;
+        if (rc != W3_E_NOMEM || budget < (1ull << 20)) return rc;
+        budget /= 2;   // (one hipMalloc of that size can fail although hipMemGetInfo calls the memory free: table_budget)
+    }
+    uint8_t *base = (uint8_t *)ctx->tables.p;
+    HIPCHK(ctx, hipMemcpy(base, plan.str_off.data(), (size_t)nb * 8, hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(base + (size_t)nb * 8, plan.p_off.data(), (size_t)nb * 8, hipMemcpyHostToDevice));
+    a.code = P.d_codes; a.L = P.d_L;
+    a.str_off = (const uint64_t *)base; a.p_off = a.str_off + nb;
+    a.tables = base + meta; a.table_stride = tk.stride;
+    a.ctx_mask = (uint32_t)((1ull << ctx_bits) - 1ull); a.use_hash = tk.use_hash; a.hash_slots = tk.use_hash ? (uint32_t)tk.slots : 0u;
+    a.P = (uint16_t *)(base + o_P); a.str = base + o_str;
+    hipEvent_t *evp = ctx->opt_timing ? ctx->ev : nullptr;
+    for (const AohBatch &bt : plan.batches) {   // (the batches share the string area and P: stream order keeps them apart)
+        a.first_block = bt.first; a.count = bt.count;
+        if (evp) HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_PREDICT], s));
+        hipLaunchKernelGGL(k_aoh_pack, dim3(std::min<uint32_t>(bt.count, 256u * 32u)), dim3(64), 0, s, a);
+        hipLaunchKernelGGL(k_aoh_predict, dim3((unsigned)std::min<uint64_t>(bt.count, waves)), dim3(64), 0, s, a);
+        if (evp) { HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_PREDICT + 1], s)); HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_CODER], s)); }
+        hipLaunchKernelGGL(k_aoh_coder<STATS>, dim3((bt.count + 63u) / 64u), dim3(64), 0, s, a);
+        HIPCHK(ctx, hipGetLastError());
+        if (evp) {
+            HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_CODER + 1], s));
+            HIPCHK(ctx, hipStreamSynchronize(s));
+            ctx->timing.predict_ms += elapsed_ev(evp, W3_EV_PREDICT); ctx->timing.coder_ms += elapsed_ev(evp, W3_EV_CODER);
+        }
+        // algorithmic bytes: pack reads the input and writes the string; predict reads it, reads and writes one Counter per step and
+        // writes 2 bytes of P; the coder reads P and the string
+        const uint64_t in_bytes = std::min<uint64_t>(a.n, (uint64_t)(bt.first + bt.count) * a.block_size) - (uint64_t)bt.first * a.block_size;
+        ctx->timing.predict_bytes += in_bytes + 2 * bt.str_bytes + bt.p_steps * (2 + 8);
+        ctx->timing.coder_bytes += 2 * bt.p_steps + bt.str_bytes;
+        ctx->timing.n_coder_launches++;
+    }
+    return W3_OK;
+}
+
 // Code blocks [0, nb) of d_in into ctx->stripes (stride cap_out), lengths to d_lens; d_bits (or null) gets the ACStats bit counts.
+// two: the form the call took (aoh_takes_twophase).
 static int aoh_encode_stripes(w3_ctx *ctx, hipStream_t s, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *d_in, size_t n, size_t block_size,
-                              uint32_t nb, uint32_t *d_lens, uint32_t *d_bits, uint32_t &cap_out) {
+                              uint32_t nb, uint32_t *d_lens, uint32_t *d_bits, uint32_t &cap_out, bool &two) {
     AohPrep P;
     int rc = aoh_prepare(ctx, s, code, 1, 1, nb, d_in, n, block_size, P);
     if (rc) return rc;
     if (P.flags[0]) { ctx->err = "the input holds a byte whose code length is 0: the output could not be decoded"; return W3_E_INVALID; }
+    two = aoh_takes_twophase(ctx, nb, ctx_bits, P.max_l[0]);
+    const w3_timing tm0 = ctx->timing;   // (a retry at the worst-case bound starts the call's sums again)
     // a Counter-coded stream rarely exceeds the Huffman bits it codes; 16 output bits per coded bit is the hard bound (retry size)
     const uint64_t l_bytes = ((uint64_t)P.max_l[0] + 7) / 8;
     const uint64_t worst = (16 * l_bytes + 16 + 15) / 16 * 16;
@@ -2537,13 +2635,22 @@ static int aoh_encode_stripes(w3_ctx *ctx, hipStream_t s, const w3_huff_code *co
     for (int attempt = 0; attempt < 2; attempt++) {
         ENSURE(ctx, ctx->stripes, (size_t)nb * cap);
         HIPCHK(ctx, hipMemsetAsync(ctx->flag.p, 0, 16, s));
-        memset(&cfg[0], 0, sizeof cfg[0]);
-        cfg[0].ctx_bits = ctx_bits; cfg[0].code_idx = 0;
-        AohArgs a;
-        memset(&a, 0, sizeof a);
-        a.in = d_in; a.n = n; a.block_size = (uint32_t)block_size;
-        a.stripes = (uint8_t *)ctx->stripes.p; a.stripe_cap = (uint32_t)cap; a.out_len = d_lens; a.overflow = (uint32_t *)ctx->flag.p; a.out_bits = d_bits;
-        if ((rc = aoh_launch<AOH_ENCODE>(ctx, s, a, P, cfg, steps, nb))) return rc;
+        if (two) {
+            ctx->timing = tm0;
+            AohTwoArgs t;
+            memset(&t, 0, sizeof t);
+            t.in = d_in; t.n = n; t.block_size = (uint32_t)block_size;
+            t.stripes = (uint8_t *)ctx->stripes.p; t.stripe_cap = (uint32_t)cap; t.out_len = d_lens; t.overflow = (uint32_t *)ctx->flag.p; t.out_bits = d_bits;
+            if ((rc = aoh_twophase_run<false>(ctx, s, t, P, ctx_bits, nb))) return rc;
+        } else {
+            memset(&cfg[0], 0, sizeof cfg[0]);
+            cfg[0].ctx_bits = ctx_bits; cfg[0].code_idx = 0;
+            AohArgs a;
+            memset(&a, 0, sizeof a);
+            a.in = d_in; a.n = n; a.block_size = (uint32_t)block_size;
+            a.stripes = (uint8_t *)ctx->stripes.p; a.stripe_cap = (uint32_t)cap; a.out_len = d_lens; a.overflow = (uint32_t *)ctx->flag.p; a.out_bits = d_bits;
+            if ((rc = aoh_launch<AOH_ENCODE>(ctx, s, a, P, cfg, steps, nb))) return rc;
+        }
         uint32_t fl = 0;
         HIPCHK(ctx, hipMemcpyAsync(&fl, ctx->flag.p, 4, hipMemcpyDeviceToHost, s));
         HIPCHK(ctx, hipStreamSynchronize(s));
@@ -2555,10 +2662,11 @@ static int aoh_encode_stripes(w3_ctx *ctx, hipStream_t s, const w3_huff_code *co
     return W3_E_HIP;
 }
 
-static void aoh_timing(w3_ctx *ctx, bool packed) {
-    ctx->timing.path = W3_PATH_GENERIC; ctx->timing.n_parts = 1;
+// (two: predict_ms / coder_ms and the byte counts are aoh_twophase_run's sums; generic_ms stays 0)
+static void aoh_timing(w3_ctx *ctx, bool packed, bool two) {
+    ctx->timing.path = two ? W3_PATH_TWOPHASE : W3_PATH_GENERIC; ctx->timing.n_parts = 1;
     if (!ctx->opt_timing) return;
-    ctx->timing.generic_ms = elapsed_ev(ctx->ev, W3_EV_PREDICT);
+    ctx->timing.generic_ms = two ? 0.f : elapsed_ev(ctx->ev, W3_EV_PREDICT);
     ctx->timing.pack_ms = packed ? elapsed_ev(ctx->ev, W3_EV_PACK) : 0.f;
     ctx->timing.total_ms = elapsed_ev(ctx->ev, W3_EV_TOTAL);
 }
@@ -2582,7 +2690,8 @@ extern "C" int w3_aoh_encode_blocks_device(w3_ctx *ctx, const w3_huff_code *code
     hipEvent_t *evp = ctx->opt_timing ? ctx->ev : nullptr;
     if (evp) { HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_TOTAL], s)); HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_PREDICT], s)); }
     uint32_t cap = 0;
-    if ((rc = aoh_encode_stripes(ctx, s, code, ctx_bits, d_in, n, block_size, nb, d_block_lens, nullptr, cap))) return rc;
+    bool two = false;
+    if ((rc = aoh_encode_stripes(ctx, s, code, ctx_bits, d_in, n, block_size, nb, d_block_lens, nullptr, cap, two))) return rc;
     if (evp) { HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_PREDICT + 1], s)); HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_PACK], s)); }
     JobRef J = jobref(ctx, 0);
     if ((rc = run_pack(ctx, J, s, (const uint8_t *)ctx->stripes.p, cap, d_block_lens, nb, d_out, out_cap, total_p))) return rc;
@@ -2590,7 +2699,7 @@ extern "C" int w3_aoh_encode_blocks_device(w3_ctx *ctx, const w3_huff_code *code
     uint64_t total = 0;
     HIPCHK(ctx, hipMemcpyAsync(&total, total_p, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
-    aoh_timing(ctx, true);
+    aoh_timing(ctx, true, two);
     if (total > out_cap) { ctx->err = "out_cap too small"; return W3_E_NOSPACE; }
     return W3_OK;
 }
@@ -2610,6 +2719,7 @@ extern "C" int w3_aoh_encode_blocks(w3_ctx *ctx, const w3_huff_code *code, uint8
     JobRef J = jobref(ctx, 0);
     size_t off = 0;
     uint32_t parts = 0;
+    bool two = false;
     for (size_t b0 = 0; b0 < nb; b0 += run, parts++) {
         const size_t b1 = std::min(nb, b0 + run), lo = b0 * block_size, hi = std::min(n, b1 * block_size);
         const uint32_t pnb = (uint32_t)(b1 - b0);
@@ -2618,7 +2728,7 @@ extern "C" int w3_aoh_encode_blocks(w3_ctx *ctx, const w3_huff_code *code, uint8
         ENSURE(ctx, ctx->total, 8);
         HIPCHK(ctx, hipMemcpyAsync(ctx->io_in.p, in + lo, hi - lo, hipMemcpyHostToDevice, s));
         uint32_t cap = 0;
-        if ((rc = aoh_encode_stripes(ctx, s, code, ctx_bits, (const uint8_t *)ctx->io_in.p, hi - lo, block_size, pnb, (uint32_t *)ctx->lens.p, nullptr, cap))) return rc;
+        if ((rc = aoh_encode_stripes(ctx, s, code, ctx_bits, (const uint8_t *)ctx->io_in.p, hi - lo, block_size, pnb, (uint32_t *)ctx->lens.p, nullptr, cap, two))) return rc;
         // the piece's size first (the packed buffer is sized from it), then the pack
         ENSURE(ctx, J.offs, (size_t)pnb * 8);
         hipLaunchKernelGGL(k_scan_lens, dim3(1), dim3(1024), 0, s, (const uint32_t *)ctx->lens.p, (uint64_t *)J.offs.p, (uint64_t *)ctx->total.p, pnb);
@@ -2634,7 +2744,7 @@ extern "C" int w3_aoh_encode_blocks(w3_ctx *ctx, const w3_huff_code *code, uint8
         }
         off += (size_t)total;
     }
-    ctx->timing.path = W3_PATH_GENERIC; ctx->timing.n_parts = parts;
+    ctx->timing.path = two ? W3_PATH_TWOPHASE : W3_PATH_GENERIC; ctx->timing.n_parts = parts;
     *out_len = off;
     if (off > out_cap || !out) { ctx->err = "out_cap too small"; return W3_E_NOSPACE; }
     return W3_OK;
@@ -2707,12 +2817,19 @@ extern "C" int w3_aoh_decode_blocks(w3_ctx *ctx, const w3_huff_code *code, uint8
     return W3_OK;
 }
 
-// the counting sink for configurations (codes[code_idx[c]], ctx_bits[c]) on a device-resident input: d_bits[ncfg][nb] (device)
+// the counting sink for configurations (codes[code_idx[c]], ctx_bits[c]) on a device-resident input: d_bits[ncfg][nb] (device).
+// two (or null: the sweep, which stays on k_aoh whatever W3_OPT_PATH says): the form a one-configuration call took.
 static int aoh_stats_run(w3_ctx *ctx, hipStream_t s, const uint8_t *d_in, size_t n, size_t block_size, uint32_t nb, const w3_huff_code *codes, size_t n_codes,
-                         const uint8_t *code_idx, const uint8_t *ctx_bits, size_t ncfg, uint32_t *d_bits) {
+                         const uint8_t *code_idx, const uint8_t *ctx_bits, size_t ncfg, uint32_t *d_bits, bool *two) {
     AohPrep P;
     int rc = aoh_prepare(ctx, s, codes, n_codes, ncfg, nb, d_in, n, block_size, P);
     if (rc) return rc;
+    if (two && (*two = ncfg == 1 && aoh_takes_twophase(ctx, nb, ctx_bits[0], P.max_l[0]))) {
+        AohTwoArgs t;
+        memset(&t, 0, sizeof t);
+        t.in = d_in; t.n = n; t.block_size = (uint32_t)block_size; t.out_bits = d_bits;
+        return aoh_twophase_run<true>(ctx, s, t, P, ctx_bits[0], nb);
+    }
     std::vector<AohCfg> cfg(ncfg);
     std::vector<uint64_t> steps(ncfg);
     for (size_t c = 0; c < ncfg; c++) {
@@ -2738,10 +2855,11 @@ extern "C" int w3_aoh_encode_stats_device(w3_ctx *ctx, const w3_huff_code *code,
     memset(&ctx->timing, 0, sizeof ctx->timing);
     hipEvent_t *evp = ctx->opt_timing ? ctx->ev : nullptr;
     if (evp) { HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_TOTAL], s)); HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_PREDICT], s)); }
-    if ((rc = aoh_stats_run(ctx, s, d_in, n, block_size, (uint32_t)nb, code, 1, nullptr, &ctx_bits, 1, d_block_bits))) return rc;
+    bool two = false;
+    if ((rc = aoh_stats_run(ctx, s, d_in, n, block_size, (uint32_t)nb, code, 1, nullptr, &ctx_bits, 1, d_block_bits, &two))) return rc;
     if (evp) { HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_PREDICT + 1], s)); HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_TOTAL + 1], s)); }
     HIPCHK(ctx, hipStreamSynchronize(s));
-    aoh_timing(ctx, false);
+    aoh_timing(ctx, false, two);
     return W3_OK;
 }
 
@@ -2780,7 +2898,7 @@ extern "C" int w3_sweep_ac_over_huffman_device(w3_ctx *ctx, const uint8_t *d_in,
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     ENSURE(ctx, ctx->sweep, ncfg * (size_t)nb * 4);
-    if ((rc = aoh_stats_run(ctx, s, d_in, n, block_size, nb, codes, n_codes, code_idx, ctx_bits, ncfg, (uint32_t *)ctx->sweep.p))) return rc;
+    if ((rc = aoh_stats_run(ctx, s, d_in, n, block_size, nb, codes, n_codes, code_idx, ctx_bits, ncfg, (uint32_t *)ctx->sweep.p, nullptr))) return rc;
     HIPCHK(ctx, hipMemcpyAsync(block_bits, ctx->sweep.p, ncfg * (size_t)nb * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
     return W3_OK;
