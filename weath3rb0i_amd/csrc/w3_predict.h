@@ -582,33 +582,46 @@ __global__ void __launch_bounds__(64) k_partition(PredictArgs a) {
 // k_partition8<MODE>: the same stable partition in ONE 8-bit pass per key byte.  256 open output runs per wave would turn
 // every 8-byte record store into its own memory transaction (the reason for the 4-bit passes above), so records go through
 // LDS tiles: a tile of 2048 records is counting-sorted by the digit inside LDS — the slot of a record is ONE returning LDS add
-// on its bin's cursor, stable because the adds are lane-ordered (atomic_round's property, same self-test) and the rounds are
+// on its bin's counter, stable because the adds are lane-ordered (atomic_round's property, same self-test) and the rounds are
 // issued in time order — and then copied out bin run by bin run, consecutive lanes to consecutive addresses.
+// A full tile (every tile but a block's ragged last one) needs no lane predicate, so each of its phases is a batch of 32
+// independent LDS operations behind ONE wait: the counting add itself returns the record's rank in its bin (slot = tstart[d] +
+// rank, a plain read after the scan), and the copy-out reads one word per record (gdelta[d] = gcur[d] - tstart[d]).  The ragged
+// tile keeps the predicated rounds: a count pass, then a second returning add on a cursor per record, one LDS round trip each.
 //   MODE 1: records from the input, key c1 (Order1).   MODE 3: records from a.rec_src (sorted by c1), key c2 (order 2 refined).
 // ---------------------------------------------------------------------------
 #define W3_P8_TILE 2048u
 #define W3_P8_ROUNDS (W3_P8_TILE / 64u)
 
-__device__ __forceinline__ void wave_excl_scan_256(uint32_t *cnt, uint32_t *excl, uint32_t *excl2) {
-    // 256 counts, 4 consecutive bins per lane
+// excl = the exclusive scan of 256 counts (excl2: a second copy).  With base / delta (a full tile of k_partition8): delta = base - excl,
+// what turns a slot of the sorted tile into the record's place in the block's output (mod 2^32)
+__device__ __forceinline__ void wave_excl_scan_256(const uint32_t *cnt, uint32_t *excl, uint32_t *excl2, const uint32_t *base = nullptr, uint32_t *delta = nullptr) {
+    // 4 consecutive bins per lane
     const int lane = threadIdx.x & 63;
     const uint32_t c0 = cnt[4 * lane], c1 = cnt[4 * lane + 1], c2 = cnt[4 * lane + 2], c3 = cnt[4 * lane + 3];
+    uint32_t g[4] = {0u, 0u, 0u, 0u};
+    if (delta) for (int k = 0; k < 4; k++) g[k] = base[4 * lane + k];
     uint32_t tot;
-    const uint32_t base = wave_excl_scan_u32(c0 + c1 + c2 + c3, &tot);
-    excl[4 * lane] = base; excl[4 * lane + 1] = base + c0; excl[4 * lane + 2] = base + c0 + c1; excl[4 * lane + 3] = base + c0 + c1 + c2;
-    if (excl2) { excl2[4 * lane] = base; excl2[4 * lane + 1] = base + c0; excl2[4 * lane + 2] = base + c0 + c1; excl2[4 * lane + 3] = base + c0 + c1 + c2; }
+    const uint32_t e0 = wave_excl_scan_u32(c0 + c1 + c2 + c3, &tot);
+    const uint32_t e[4] = {e0, e0 + c0, e0 + c0 + c1, e0 + c0 + c1 + c2};
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        excl[4 * lane + k] = e[k];
+        if (excl2) excl2[4 * lane + k] = e[k];
+        if (delta) delta[4 * lane + k] = g[k] - e[k];
+    }
 }
 
 // FAULT: the instance with the test hook of the sampled verification (dbg_flags bit 5; the production instances carry no trace of it)
 template <int MODE, int NW = 1, bool FAULT = false>
 __global__ void __launch_bounds__(64 * NW) k_partition8(PredictArgs a) {
     __shared__ uint2 tile_[NW][W3_P8_TILE];
-    __shared__ uint32_t cnt_[NW][4][256];   // gcur, tcnt, tstart, tcur
+    __shared__ uint32_t cnt_[NW][4][256];   // gcur, tcnt, tstart, gdelta (full tiles) / tcur (the ragged tile)
     W3_HALF_CU_PAD(NW, sizeof(tile_) + sizeof(cnt_))
     const int lane = threadIdx.x & 63;
     const uint32_t wv = threadIdx.x >> 6;
     uint2 *tile = tile_[wv];
-    uint32_t *gcur = cnt_[wv][0], *tcnt = cnt_[wv][1], *tstart = cnt_[wv][2], *tcur = cnt_[wv][3];
+    uint32_t *gcur = cnt_[wv][0], *tcnt = cnt_[wv][1], *tstart = cnt_[wv][2], *gdelta = cnt_[wv][3], *tcur = cnt_[wv][3];
     constexpr uint32_t KSH = MODE == 1 ? 8u : 16u;   // digit = window byte c1 / c2
     for (uint32_t b = blockIdx.x * NW + wv; b < a.nblocks; b += gridDim.x * NW) {
         const uint64_t off = (uint64_t)b * a.block_size;
@@ -668,51 +681,112 @@ __global__ void __launch_bounds__(64 * NW) k_partition8(PredictArgs a) {
         W3_STAMP(0);
         for (uint32_t t0 = 0; t0 < len; t0 += W3_P8_TILE) {
             const uint32_t tlen = min(W3_P8_TILE, len - t0);
-            uint2 rec[W3_P8_ROUNDS];   // (loading a tile ahead, while the one before is sorted and copied out, changes nothing: measured)
+            if (tlen == W3_P8_TILE) {
+                // full tile: record r * 64 + lane of the tile is position t0 + r * 64 + lane (MODE 1: not held in a register).
+                // (Loading the next tile ahead of this one's copy-out only moves the wait from the loads to the stores, the per-block
+                //  sum stays: measured again with these batches, profiles/p8_batched/README.md)
+                uint32_t rx[MODE == 3 ? W3_P8_ROUNDS : 1u], ry[W3_P8_ROUNDS], rk[W3_P8_ROUNDS];
 #pragma unroll
-            for (uint32_t r = 0; r < W3_P8_ROUNDS; r++) {
-                const uint32_t e = min(t0 + r * 64u + lane, last);
-                if constexpr (MODE == 1) rec[r] = make_uint2(e, load_window(blk, e, first)); else rec[r] = src[e];
-            }
-#pragma unroll
-            for (int k = 0; k < 4; k++) tcnt[k * 64 + lane] = 0u;
-            __asm__ volatile("" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (uint32_t r = 0; r < W3_P8_ROUNDS; r++)
-                if (r * 64u + lane < tlen) __hip_atomic_fetch_add(&tcnt[(rec[r].y >> KSH) & 0xFFu], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            __asm__ volatile("" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
-            wave_excl_scan_256(tcnt, tstart, tcur);
-            __asm__ volatile("" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
-            W3_STAMP(1);
-            // stable scatter into the tile: rounds in time order, lanes in order inside the returning add
-#pragma unroll
-            for (uint32_t r = 0; r < W3_P8_ROUNDS; r++) {
-                if (r * 64u + lane < tlen) {
-                    uint32_t slot = __hip_atomic_fetch_add(&tcur[(rec[r].y >> KSH) & 0xFFu], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    // (test hook: a mis-ordered add in round 1 of the block's first tile — all 64 lanes active there; two lanes
-                    //  of the same bin exchange their slots, so the tile's slots stay a permutation and the bin runs stay in place)
-                    if (FAULT && r == 1u && t0 == 0u && tlen >= 128u && (a.fault_block == 0xFFFFFFFFu || a.fault_block == b)) {
-                        const uint32_t d = (rec[r].y >> KSH) & 0xFFu;
-                        const uint32_t d_x = (uint32_t)__shfl_xor((int)d, 1, 64), slot_x = (uint32_t)__shfl_xor((int)slot, 1, 64);
-                        if (d_x == d) slot = slot_x;
-                    }
-                    tile[slot] = rec[r];
+                for (uint32_t r = 0; r < W3_P8_ROUNDS; r++) {
+                    const uint32_t e = t0 + r * 64u + lane;
+                    if constexpr (MODE == 1) ry[r] = load_window(blk, e, first); else { const uint2 v = src[e]; rx[r] = v.x; ry[r] = v.y; }
                 }
-            }
-            __asm__ volatile("" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
-            W3_STAMP(2);
-            // copy out: element k of the sorted tile belongs to bin d at run offset k - tstart[d]
 #pragma unroll
-            for (uint32_t r = 0; r < W3_P8_ROUNDS; r++) {
-                const uint32_t k = r * 64u + lane;
-                if (k < tlen) {
-                    const uint2 rc = tile[k];
-                    const uint32_t d = (rc.y >> KSH) & 0xFFu;
-                    out[gcur[d] + (k - tstart[d])] = rc;
+                for (int k = 0; k < 4; k++) tcnt[k * 64 + lane] = 0u;
+                __asm__ volatile("" ::: "memory");
+                __builtin_amdgcn_wave_barrier();
+                // count AND rank in one returning add per record: rounds in time order, lanes in order inside the add, so rk is the
+                // record's stable rank in its bin.  Nothing reads a rank before the scan: the 32 adds are in flight together
+#pragma unroll
+                for (uint32_t r = 0; r < W3_P8_ROUNDS; r++)
+                    rk[r] = __hip_atomic_fetch_add(&tcnt[(ry[r] >> KSH) & 0xFFu], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                // (test hook: a mis-ordered add in round 1 of the block's first tile; two lanes of the same bin exchange their
+                //  ranks, so the tile's slots stay a permutation and the bin runs stay in place)
+                if (FAULT && t0 == 0u && (a.fault_block == 0xFFFFFFFFu || a.fault_block == b)) {
+                    const uint32_t d = (ry[1] >> KSH) & 0xFFu;
+                    const uint32_t d_x = (uint32_t)__shfl_xor((int)d, 1, 64), rk_x = (uint32_t)__shfl_xor((int)rk[1], 1, 64);
+                    if (d_x == d) rk[1] = rk_x;
+                }
+                __asm__ volatile("" ::: "memory");
+                __builtin_amdgcn_wave_barrier();
+                wave_excl_scan_256(tcnt, tstart, nullptr, gcur, gdelta);
+                __asm__ volatile("" ::: "memory");
+                __builtin_amdgcn_wave_barrier();
+                W3_STAMP(1);
+                // stable scatter into the tile: 32 reads of the bins' starts (lanes of one bin read one address: a broadcast),
+                // one wait, 32 writes
+                uint32_t ts[W3_P8_ROUNDS];
+#pragma unroll
+                for (uint32_t r = 0; r < W3_P8_ROUNDS; r++) ts[r] = tstart[(ry[r] >> KSH) & 0xFFu];
+                __asm__ volatile("" ::: "memory");
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (uint32_t r = 0; r < W3_P8_ROUNDS; r++)
+                    tile[ts[r] + rk[r]] = make_uint2(MODE == 1 ? t0 + r * 64u + lane : rx[r], ry[r]);
+                __asm__ volatile("" ::: "memory");
+                __builtin_amdgcn_wave_barrier();
+                W3_STAMP(2);
+                // copy out: element k of the sorted tile goes to out[gdelta[d] + k].  32 tile reads, one wait, 32 reads of the
+                // bins' deltas, one wait, 32 stores
+                uint2 rc[W3_P8_ROUNDS];
+#pragma unroll
+                for (uint32_t r = 0; r < W3_P8_ROUNDS; r++) rc[r] = tile[r * 64u + lane];
+                __asm__ volatile("" ::: "memory");
+                __builtin_amdgcn_sched_barrier(0);
+                uint32_t gd[W3_P8_ROUNDS];
+#pragma unroll
+                for (uint32_t r = 0; r < W3_P8_ROUNDS; r++) gd[r] = gdelta[(rc[r].y >> KSH) & 0xFFu];
+                __asm__ volatile("" ::: "memory");
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (uint32_t r = 0; r < W3_P8_ROUNDS; r++) out[gd[r] + (r * 64u + lane)] = rc[r];
+            } else {
+                uint2 rec[W3_P8_ROUNDS];
+#pragma unroll
+                for (uint32_t r = 0; r < W3_P8_ROUNDS; r++) {
+                    const uint32_t e = min(t0 + r * 64u + lane, last);
+                    if constexpr (MODE == 1) rec[r] = make_uint2(e, load_window(blk, e, first)); else rec[r] = src[e];
+                }
+#pragma unroll
+                for (int k = 0; k < 4; k++) tcnt[k * 64 + lane] = 0u;
+                __asm__ volatile("" ::: "memory");
+                __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                for (uint32_t r = 0; r < W3_P8_ROUNDS; r++)
+                    if (r * 64u + lane < tlen) __hip_atomic_fetch_add(&tcnt[(rec[r].y >> KSH) & 0xFFu], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __asm__ volatile("" ::: "memory");
+                __builtin_amdgcn_wave_barrier();
+                wave_excl_scan_256(tcnt, tstart, tcur);
+                __asm__ volatile("" ::: "memory");
+                __builtin_amdgcn_wave_barrier();
+                W3_STAMP(1);
+                // stable scatter into the tile: rounds in time order, lanes in order inside the returning add
+#pragma unroll
+                for (uint32_t r = 0; r < W3_P8_ROUNDS; r++) {
+                    if (r * 64u + lane < tlen) {
+                        uint32_t slot = __hip_atomic_fetch_add(&tcur[(rec[r].y >> KSH) & 0xFFu], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        // (test hook: a mis-ordered add in round 1 of the block's first tile — all 64 lanes active there; two lanes
+                        //  of the same bin exchange their slots, so the tile's slots stay a permutation and the bin runs stay in place)
+                        if (FAULT && r == 1u && t0 == 0u && tlen >= 128u && (a.fault_block == 0xFFFFFFFFu || a.fault_block == b)) {
+                            const uint32_t d = (rec[r].y >> KSH) & 0xFFu;
+                            const uint32_t d_x = (uint32_t)__shfl_xor((int)d, 1, 64), slot_x = (uint32_t)__shfl_xor((int)slot, 1, 64);
+                            if (d_x == d) slot = slot_x;
+                        }
+                        tile[slot] = rec[r];
+                    }
+                }
+                __asm__ volatile("" ::: "memory");
+                __builtin_amdgcn_wave_barrier();
+                W3_STAMP(2);
+                // copy out: element k of the sorted tile belongs to bin d at run offset k - tstart[d]
+#pragma unroll
+                for (uint32_t r = 0; r < W3_P8_ROUNDS; r++) {
+                    const uint32_t k = r * 64u + lane;
+                    if (k < tlen) {
+                        const uint2 rc = tile[k];
+                        const uint32_t d = (rc.y >> KSH) & 0xFFu;
+                        out[gcur[d] + (k - tstart[d])] = rc;
+                    }
                 }
             }
             __asm__ volatile("" ::: "memory");
