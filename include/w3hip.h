@@ -136,7 +136,9 @@ enum {
                            kernel shapes of the submit / wait pipeline, 128 = submitted calls use the plain shapes, 256 = slot-state
                            leaves always on k_slot (lane per block, hash map in HBM), 512 = always on the sorted replay (wavefront per
                            block, no table; default: the replay below 7,000 blocks, k_slot from there on), 1024 = decode on the
-                           lane-per-block kernels only (default: sixteen lanes per block where k_decode_spec applies).  0 = defaults.
+                           lane-per-block kernels only (default: sixteen lanes per block where k_decode_spec applies; AC over Huffman: k_aoh in
+                           place of k_aoh_decode_spec), 2048 = AC over Huffman: the full decode w3_aoh_decode_blocks[_device] too runs the
+                           sixteen-lane decoder where it covers (the ranges calls do by default).  0 = defaults.
                            32 = FAULT INJECTION (test hook of the sampled verification): one LDS-add round of every block returns two
                            lanes each other's value (in the kernels W3_OPT_FAULT_KERNELS names); refused (W3_E_INVALID) unless
                            W3_OPT_VERIFY is on, so it cannot corrupt output */
@@ -173,9 +175,12 @@ enum {
                            fault mis-orders — 1 = k_predict_small's rounds (default), 2 = k_rank_sorted's rounds, 4 = k_partition8's
                            cursor adds (two records of one bin swap their slots in the tile: a permutation, never another index) */
     W3_OPT_AOH_BATCH_BLOCKS = 14 /* test hook in the manner of W3_OPT_HOST_CHUNK_BLOCKS: most blocks per batch of the two-phase form of AC over
-                           Huffman (0 = default: as many whole blocks as the device memory budget holds; the output is the same) */
+                           Huffman, and most jobs per batch of its ranges calls and of the sixteen-lane full decode (0 = default: as many
+                           as the device memory budget holds; the output is the same) */
 };
-enum { W3_PATH_AUTO = 0, W3_PATH_GENERIC = 1, W3_PATH_TWOPHASE = 2 };
+enum { W3_PATH_AUTO = 0, W3_PATH_GENERIC = 1, W3_PATH_TWOPHASE = 2,
+       W3_PATH_SPEC = 3 /* reported only (w3_timing.path of the AC-over-Huffman decode and ranges calls that took the sixteen-lane decoder);
+                           W3_OPT_PATH does not accept it */ };
 int         w3_ctx_set_option(w3_ctx *ctx, int opt, int64_t value);
 
 /* Upper bound on the concatenated block streams for n input bytes. */
@@ -405,7 +410,7 @@ int w3_sweep_ordern_device(w3_ctx *ctx, const uint8_t *d_in, size_t n, size_t bl
  *     stored probabilities; workspace = the strings + 2 bytes per coded bit + one table per resident wavefront, a call that exceeds
  *     the device memory budget goes in batches of whole blocks (W3_OPT_AOH_BATCH_BLOCKS caps a batch, for tests).  The output of the
  *     two forms is identical.  W3_PATH_AUTO takes the form its rule names (W3_AOH_AUTO_* in csrc/w3_aoh.h: the fused kernel for
- *     every shape until the two-phase form has been timed); w3_timing.path tells which.  Decode and the sweep IGNORE the option and run k_aoh: the decoder cannot look ahead (a step's
+ *     every shape until the two-phase form has been timed); w3_timing.path tells which.  Decode and the sweep IGNORE the option (the full decode and the sweep run k_aoh): the decoder cannot look ahead (a step's
  *     context is known only when the step before it is decoded), and the sweep already has configurations x blocks lanes.
  *     W3_OPT_TIMING: the fused form fills generic_ms / pack_ms / total_ms (predict_ms and coder_ms stay 0); the two-phase form fills
  *     predict_ms (k_aoh_pack + k_aoh_predict), coder_ms, pack_ms, total_ms, predict_bytes and coder_bytes (generic_ms stays 0).
@@ -423,6 +428,28 @@ int w3_aoh_decode_blocks(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits
 int w3_aoh_decode_blocks_device(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *d_in, size_t in_len,
                                 const uint32_t *d_block_lens, size_t nblocks, size_t block_size, uint64_t orig_len, uint8_t *d_out,
                                 void *stream);
+/* Random access on these streams: w3_decode_ranges / w3_decode_ranges_device (above) for this family — the same conventions, word for
+ * word: overlapping, duplicate, unsorted and zero-length ranges are valid; the output is the ranges concatenated in request order;
+ * *out_len is set even on W3_E_NOSPACE (nothing is decoded then); W3_E_INVALID for nblocks != ceil(orig_len / block_size) (checked
+ * first), a range past orig_len (u64 wrap included), an invalid table or ctx_bits, or a job in flight; W3_E_FORMAT for a length table
+ * that claims more than in_len.  The host variant sends only the selected blocks' streams over PCIe (one pinned buffer, one H2D copy,
+ * one D2H copy) and cuts selections above 2 GiB worth of blocks into several device calls; the workspace is w3_decode_ranges'.
+ * The decoder: one decode job per selected block, served by k_aoh_decode_spec (csrc/w3_aoh_spec.h) — SIXTEEN lanes per job: the 15
+ * contexts the next four coded bits can reach are loaded in one round trip, the four steps run in registers with the nibble's own
+ * updates forwarded, one store per distinct context — where w3_aoh_decode_spec_covers(ctx_bits) is 1: ctx_bits <= 24, a zero-filled
+ * direct table of 4 << ctx_bits bytes per job, jobs in batches under the device memory budget.  Otherwise (ctx_bits 25 .. 31), and
+ * under W3_OPT_VARIANT bit 1024, the lane-per-job kernel k_aoh, its exact map sized for the longest job.  W3_OPT_VARIANT bit 2048
+ * makes the full decode w3_aoh_decode_blocks[_device] take the sixteen-lane decoder too (without it the full decode runs what it
+ * always ran).  w3_timing.path after a decode or ranges call of the family: W3_PATH_SPEC when the sixteen-lane decoder ran,
+ * W3_PATH_GENERIC otherwise.  Both decoders read a stream the same way: a stream that is not one of ours decodes to the same bytes. */
+int w3_aoh_decode_ranges(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *in, size_t in_len,
+                         const uint32_t *block_lens, size_t nblocks, size_t block_size, uint64_t orig_len,
+                         const w3_range *ranges, size_t n_ranges, uint8_t *out, size_t out_cap, size_t *out_len);
+int w3_aoh_decode_ranges_device(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *d_in, size_t in_len,
+                                const uint32_t *d_block_lens, size_t nblocks, size_t block_size, uint64_t orig_len,
+                                const w3_range *ranges /* host */, size_t n_ranges, uint8_t *d_out, size_t out_cap, size_t *out_len,
+                                void *stream);
+int w3_aoh_decode_spec_covers(uint8_t ctx_bits);   /* host only: 1 where the sixteen-lane decoder takes the call */
 int w3_aoh_encode_stats(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *in, size_t n, size_t block_size,
                         uint32_t *block_bits);
 int w3_aoh_encode_stats_device(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *d_in, size_t n, size_t block_size,

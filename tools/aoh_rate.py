@@ -1,6 +1,7 @@
 """AC-over-Huffman rates (w3_aoh_*; bin/ac-over-huffman/main.rs) on a device-resident enwik-shaped corpus synthesised as bench.py does
 (tools/synth.c seed 1), 64 KiB blocks, at the reference's two best published configurations (hsize 13 / ctx 24 and hsize 12 / ctx 19):
-encode and decode MiB/s on every path that is built and under W3_PATH_AUTO (with timing.path, the form it took, and the phases'
+encode and decode MiB/s on every path that is built and under W3_PATH_AUTO (the decode also on the sixteen-lane decoder, W3_OPT_VARIANT
+aoh_decode_spec) (with timing.path, the form it took, and the phases'
 milliseconds of one more call with W3_OPT_TIMING), the counting sink, the compressed size beside order012's and OrderN(32, 1)'s on the
 same input; the wall time of the driver's full sweep (huffman_size 7..15 x ctx_bits 8..30, one call) on 20 MB; and the rate of the tests'
 CPU truth (tests/host/aoh_ref.c, a C restatement of the driver's loop — not the reference) on 16 threads.  Every shape is warmed up
@@ -112,6 +113,13 @@ def main():
                 if path != "auto":   # (decode ignores the option)
                     r["decode_" + path] = rate(timed(lambda: ctx.aoh_decode_blocks_device(code, cb, d_comp[:total], d_lens, BS, n, d_back), a.runs), n)
                     assert bool((d_back == d_in).all())
+                    if path == "generic":   # the same decode on the sixteen-lane decoder (W3_OPT_VARIANT aoh_decode_spec; timing.path tells what ran)
+                        ctx.set_variant("aoh_decode_spec")
+                        d_back.zero_()
+                        r["decode_aoh_decode_spec"] = rate(timed(lambda: ctx.aoh_decode_blocks_device(code, cb, d_comp[:total], d_lens, BS, n, d_back), a.runs), n)
+                        r["decode_aoh_decode_spec"]["path"] = ctx.timing()["path"]
+                        ctx.set_variant()
+                        assert bool((d_back == d_in).all())
                 # every path writes the same streams
                 sig = (total, int(d_lens.to(torch.int64).sum().item()), int(d_bits.to(torch.int64).sum().item()), int(d_comp[:total].to(torch.int64).sum().item()))
                 ref = ref or sig

@@ -17,9 +17,9 @@ W3_OK, W3_E_INVALID, W3_E_NOSPACE, W3_E_HIP, W3_E_UNSUPPORTED, W3_E_NOMEM, W3_E_
 W3_OPT_PATH, W3_OPT_TIMING, W3_OPT_CODER, W3_OPT_ACC_LIMIT, W3_OPT_DEBUG_STAMPS, W3_OPT_VARIANT, W3_OPT_SLOT_BUDGET_MB, W3_OPT_VERIFY, W3_OPT_FAULT_BLOCK, W3_OPT_TUNE, W3_OPT_HOST_CHUNK_BLOCKS, W3_OPT_FAULT_KERNELS, W3_OPT_AOH_BATCH_BLOCKS = 1, 2, 3, 4, 5, 7, 8, 9, 10, 11, 12, 13, 14
 W3_VAR_NO_LDS_ATOMICS, W3_VAR_PARTITION4, W3_VAR_NO_CHAINED_PARTITION, W3_VAR_CM_UNSTAGED, W3_VAR_NO_SIDE_STREAM, W3_VAR_INJECT_LDS_FAULT = 1, 2, 4, 8, 16, 32
 W3_VAR_HALF_CU, W3_VAR_FULL_CU = 64, 128
-W3_VAR_SLOT_TABLE, W3_VAR_SLOT_SORTED, W3_VAR_DECODE_LANE = 256, 512, 1024
+W3_VAR_SLOT_TABLE, W3_VAR_SLOT_SORTED, W3_VAR_DECODE_LANE, W3_VAR_AOH_DECODE_SPEC = 256, 512, 1024, 2048
 W3_GATHER_AUTO, W3_GATHER_RCCL, W3_GATHER_PEER_COPY = 0, 1, 2
-W3_PATH_AUTO, W3_PATH_GENERIC, W3_PATH_TWOPHASE = 0, 1, 2
+W3_PATH_AUTO, W3_PATH_GENERIC, W3_PATH_TWOPHASE, W3_PATH_SPEC = 0, 1, 2, 3
 
 
 class Node(C.Structure):
@@ -64,7 +64,7 @@ EXPORTS = [
     "w3_decode_ranges", "w3_decode_ranges_device",
     "w3_huff_code_table", "w3_aoh_max_compressed_size", "w3_aoh_encode_blocks", "w3_aoh_encode_blocks_device", "w3_aoh_decode_blocks",
     "w3_aoh_decode_blocks_device", "w3_aoh_encode_stats", "w3_aoh_encode_stats_device", "w3_sweep_ac_over_huffman",
-    "w3_sweep_ac_over_huffman_device",
+    "w3_sweep_ac_over_huffman_device", "w3_aoh_decode_ranges", "w3_aoh_decode_ranges_device", "w3_aoh_decode_spec_covers",
 ]
 
 _lib = None
@@ -144,6 +144,10 @@ def load():
     lib.w3_aoh_encode_blocks_device.argtypes = [vp, hc, u8, vp, sz, sz, vp, sz, vp, vp, vp]
     lib.w3_aoh_decode_blocks.argtypes = [vp, hc, u8, vp, sz, vp, sz, sz, C.c_uint64, vp]
     lib.w3_aoh_decode_blocks_device.argtypes = [vp, hc, u8, vp, sz, vp, sz, sz, C.c_uint64, vp, vp]
+    lib.w3_aoh_decode_ranges.argtypes = [vp, hc, u8, vp, sz, vp, sz, sz, C.c_uint64, C.POINTER(Range), sz, vp, sz, C.POINTER(sz)]
+    lib.w3_aoh_decode_ranges_device.argtypes = [vp, hc, u8, vp, sz, vp, sz, sz, C.c_uint64, C.POINTER(Range), sz, vp, sz, C.POINTER(sz), vp]
+    lib.w3_aoh_decode_spec_covers.argtypes = [u8]
+    lib.w3_aoh_decode_spec_covers.restype = C.c_int
     lib.w3_aoh_encode_stats.argtypes = [vp, hc, u8, vp, sz, sz, vp]
     lib.w3_aoh_encode_stats_device.argtypes = [vp, hc, u8, vp, sz, sz, vp, vp]
     lib.w3_sweep_ac_over_huffman.argtypes = [vp, vp, sz, sz, vp, sz, vp, vp, sz, vp]

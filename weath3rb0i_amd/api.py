@@ -76,10 +76,12 @@ class Context:
         """Cross-check hook (W3_OPT_VARIANT): alternative bit-exact implementations, by name: no_lds_atomics, partition4,
         no_chained_partition, cm_unstaged, no_side_stream, half_cu (synchronous calls in the pipeline's kernel shapes), full_cu
         (submitted calls in the plain shapes), slot_table / slot_sorted (slot-state leaves on k_slot / on the sorted replay whatever
-        the block count), decode_lane (decode on the lane-per-block kernels, not k_decode_spec).  No names = defaults."""
+        the block count), decode_lane (decode on the lane-per-block kernels, not k_decode_spec / k_aoh_decode_spec), aoh_decode_spec (AC
+        over Huffman: the full decode too runs the sixteen-lane decoder where it covers).  No names = defaults."""
         bits = {"no_lds_atomics": L.W3_VAR_NO_LDS_ATOMICS, "partition4": L.W3_VAR_PARTITION4, "no_chained_partition": L.W3_VAR_NO_CHAINED_PARTITION,
                 "cm_unstaged": L.W3_VAR_CM_UNSTAGED, "no_side_stream": L.W3_VAR_NO_SIDE_STREAM, "inject_lds_fault": L.W3_VAR_INJECT_LDS_FAULT,
-                "half_cu": L.W3_VAR_HALF_CU, "full_cu": L.W3_VAR_FULL_CU, "slot_table": L.W3_VAR_SLOT_TABLE, "slot_sorted": L.W3_VAR_SLOT_SORTED, "decode_lane": L.W3_VAR_DECODE_LANE}
+                "half_cu": L.W3_VAR_HALF_CU, "full_cu": L.W3_VAR_FULL_CU, "slot_table": L.W3_VAR_SLOT_TABLE, "slot_sorted": L.W3_VAR_SLOT_SORTED, "decode_lane": L.W3_VAR_DECODE_LANE,
+                "aoh_decode_spec": L.W3_VAR_AOH_DECODE_SPEC}
         v = 0
         for nm in names:
             v |= bits[nm]
@@ -114,7 +116,8 @@ class Context:
         self._chk(self.lib.w3_ctx_set_option(self.h, L.W3_OPT_HOST_CHUNK_BLOCKS, int(blocks)))
 
     def set_aoh_batch_blocks(self, blocks):
-        """W3_OPT_AOH_BATCH_BLOCKS: most blocks per batch of the two-phase form of AC over Huffman (0 = from the memory budget)."""
+        """W3_OPT_AOH_BATCH_BLOCKS: most blocks per batch of the two-phase form of AC over Huffman, and most jobs per batch of its
+        ranges calls and of the sixteen-lane full decode (0 = from the memory budget)."""
         self._chk(self.lib.w3_ctx_set_option(self.h, L.W3_OPT_AOH_BATCH_BLOCKS, int(blocks)))
 
     def set_timing(self, on=True):
@@ -261,6 +264,23 @@ class Context:
         self._chk(rc)
         return out[:orig_len]
 
+    def aoh_decode_ranges(self, code, ctx_bits, comp, block_lens, block_size, orig_len, ranges):
+        """Random access on AC-over-Huffman streams (w3_aoh_decode_ranges): the bytes of `ranges` — (offset, len) pairs or an (n, 2) integer
+        array — of the original data, concatenated in request order, decoding only the blocks they touch.  -> np.uint8[sum of the lengths]"""
+        a = _u8(comp)
+        lens = np.ascontiguousarray(block_lens, dtype=np.uint32)
+        rs, n, total = _ranges(ranges)
+        out = np.empty(max(total, 1), dtype=np.uint8)
+        olen = C.c_size_t()
+        rc = self.lib.w3_aoh_decode_ranges(self.h, C.byref(code.table), ctx_bits, a.ctypes.data_as(C.c_void_p), len(a), lens.ctypes.data_as(C.c_void_p),
+                                           len(lens), block_size, orig_len, rs, n, out.ctypes.data_as(C.c_void_p), total, C.byref(olen))
+        self._chk(rc)
+        return out[: olen.value]
+
+    def aoh_decode_spec_covers(self, ctx_bits):
+        """w3_aoh_decode_spec_covers: whether the sixteen-lane decoder takes a call with this ctx_bits"""
+        return bool(self.lib.w3_aoh_decode_spec_covers(int(ctx_bits)))
+
     def aoh_encode_stats(self, code, ctx_bits, data, block_size):
         """ACStats bit counts per block (what the driver's csize = bits / 8 comes from, :72, :88).  -> np.uint32[nb]"""
         a = _u8(data)
@@ -402,6 +422,18 @@ class Context:
                                                        C.c_void_p(d_lens.data_ptr()), d_lens.numel(), block_size, orig_len,
                                                        C.c_void_p(d_out.data_ptr()), st))
 
+    def aoh_decode_ranges_device(self, code, ctx_bits, d_comp, d_lens, block_size, orig_len, ranges, d_out, stream=None):
+        """w3_aoh_decode_ranges_device: the bytes of `ranges` (host side, as aoh_decode_ranges) concatenated in request order into the
+        torch.uint8 CUDA tensor d_out.  -> bytes written"""
+        st = C.c_void_p(stream) if stream else None
+        rs, n, _ = _ranges(ranges)
+        olen = C.c_size_t()
+        rc = self.lib.w3_aoh_decode_ranges_device(self.h, C.byref(code.table), ctx_bits, C.c_void_p(d_comp.data_ptr()), d_comp.numel(),
+                                                  C.c_void_p(d_lens.data_ptr()), d_lens.numel(), block_size, orig_len, rs, n,
+                                                  C.c_void_p(d_out.data_ptr()), d_out.numel(), C.byref(olen), st)
+        self._chk(rc)
+        return olen.value
+
     def aoh_encode_stats_device(self, code, ctx_bits, d_in, block_size, d_bits, stream=None):
         """d_bits: int32/uint32[nb] CUDA tensor receiving the ACStats bit counts."""
         st = C.c_void_p(stream) if stream else None
@@ -418,6 +450,30 @@ class Context:
                                                            ci.ctypes.data_as(C.c_void_p), cb.ctypes.data_as(C.c_void_p), len(configs),
                                                            out.ctypes.data_as(C.c_void_p)))
         return out[:, :nb]
+
+
+AOH_CONTAINER_MAGIC = b"w3bk\x02"   # tools/w3cli.cpp: the block container, version 2 (AC over Huffman)
+
+
+def aoh_container_ranges(ctx, blob, ranges):
+    """The bytes of `ranges` of a version-2 `w3bk` container (an AC-over-Huffman file as tools/w3cli.cpp writes it: magic, version 2,
+    u64 original length, u32 block size, u32 block count, ctx_bits, the 256 codes (u16) and lengths (u8), the u32 length table — all
+    big-endian — then the streams), through Context.aoh_decode_ranges.  W3Error(W3_E_FORMAT) for anything else."""
+    a = _u8(blob)
+    hdr = 21 + 1 + 768
+    if len(a) < 21 or a[:5].tobytes() != AOH_CONTAINER_MAGIC:
+        raise W3Error(L.W3_E_FORMAT, "not a version-2 w3bk container")
+    orig, bs, nb = int.from_bytes(a[5:13].tobytes(), "big"), int.from_bytes(a[13:17].tobytes(), "big"), int.from_bytes(a[17:21].tobytes(), "big")
+    if bs == 0 or nb != (orig + bs - 1) // bs or len(a) < hdr + 4 * nb:
+        raise W3Error(L.W3_E_FORMAT, "truncated or inconsistent w3bk header")
+    ctx_bits = int(a[21])
+    codes = a[22:22 + 512].view(">u2").astype(np.uint16).tolist()
+    lens = a[22 + 512:22 + 768].tolist()
+    block_lens = a[hdr:hdr + 4 * nb].view(">u4").astype(np.uint32)
+    comp = a[hdr + 4 * nb:]
+    if int(block_lens.sum(dtype=np.uint64)) > len(comp):
+        raise W3Error(L.W3_E_FORMAT, "the w3bk length table claims more than the file holds")
+    return ctx.aoh_decode_ranges(HuffCode.from_tables(codes, lens), ctx_bits, comp, block_lens, bs, orig, ranges)
 
 
 def encode_blocks_sharded_device(ctxs, model, d_ins, block_size, d_out, d_lens, root=0, transport="auto"):

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "w3_device.h"
+#include "w3_generic.h"
 #include "w3_sweep.h"
 #include "w3_predict_wave.h"
 #include "w3_aoh_plan.h"
@@ -59,6 +60,7 @@ struct AohArgs {
     uint8_t *stripes; uint32_t stripe_cap; uint32_t *out_len; uint32_t *overflow;
     // decode
     const uint8_t *cin; const uint64_t *coffs; const uint32_t *clens; uint8_t *dout;
+    const DecodeJob *jobs;                     // null: lane k decodes block first_block + k whole; else job first_block + k (w3_ranges.h)
 };
 
 enum { AOH_STATS = 0, AOH_ENCODE = 1, AOH_DECODE = 2 };
@@ -129,10 +131,13 @@ __global__ void __launch_bounds__(64) k_aoh(AohArgs a) {
     uint32_t hist = 0u;
 
     if (MODE == AOH_DECODE) {
+        uint32_t sb = b, dlen = len;                   // the stream, the bytes to decode and where they go: the block, or the lane's job
+        uint64_t doff = off;
+        if (a.jobs) { const DecodeJob jb = a.jobs[b]; sb = jb.blk; dlen = jb.len; doff = jb.dst; }
         Decoder dec;
-        dec.init(a.cin + a.coffs[b], a.clens[b]);
+        dec.init(a.cin + a.coffs[sb], a.clens[sb]);
         const uint32_t max_len = s_code.max_len;
-        for (uint32_t i = 0; i < len; i++) {           // ends on the block's BYTE count
+        for (uint32_t i = 0; i < dlen; i++) {          // ends on the BYTE count
             uint32_t code = 0u, l = 0u, sym = 0u;
             while (l < max_len) {                      // (a stream that is not one of ours ends every symbol at max_len: the step count,
                 uint32_t cv;                           //  and with it the exact map's fill, stays within what the host sized it for)
@@ -146,7 +151,7 @@ __global__ void __launch_bounds__(64) k_aoh(AohArgs a) {
                 const uint32_t d = code - (fc & 0xFFFFu);
                 if (d < (fc >> 16)) { sym = s_code.sym[s_code.offs[l] + d]; break; }
             }
-            a.dout[off + i] = (uint8_t)sym;
+            a.dout[doff + i] = (uint8_t)sym;
         }
         return;
     }

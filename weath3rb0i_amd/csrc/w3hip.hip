@@ -24,6 +24,7 @@
 #include "w3_selftest.h"
 #include "w3_sweep.h"
 #include "w3_aoh.h"
+#include "w3_aoh_spec.h"
 #include "w3_rccl.h"
 
 using namespace w3;
@@ -316,7 +317,7 @@ extern "C" int w3_ctx_set_option(w3_ctx *ctx, int opt, int64_t value) {
         ctx->tp.acc_limit = (uint32_t)value;
         return W3_OK;
     case W3_OPT_VARIANT:
-        if (value < 0 || value > 2047) return W3_E_INVALID;
+        if (value < 0 || value > 4095) return W3_E_INVALID;
         // the fault-injection hook exists for the test of the sampled verification: without the verification it would only corrupt output
         if ((value & W3_VAR_INJECT_LDS_FAULT) && !ctx->tp.verify) { ctx->err = "W3_OPT_VARIANT bit 32 (fault injection) needs W3_OPT_VERIFY on"; return W3_E_INVALID; }
         ctx->tp.variant = (uint32_t)value;
@@ -1659,32 +1660,37 @@ static std::vector<uint8_t> ranges_meta(const std::vector<RangeJob> &jobs, const
     return m;
 }
 
-// Decode the jobs (d_jobs[n_jobs], stream indices into d_lens[nb] / d_cin) into the staging buffer, then gather the pieces
-// (d_chunks[n_chunks], at most W3_GATHER_PIECE_MAX bytes each) into d_out.
-static int ranges_run(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, const uint8_t *d_cin, const uint32_t *d_lens, uint32_t nb, size_t block_size,
-                      uint64_t orig_len, const DecodeJob *d_jobs, uint32_t n_jobs, const RangePiece *d_chunks, uint32_t n_chunks, uint64_t staging,
-                      uint8_t *d_out) {
+// The decoder behind a ranges call: a model spec (w3_decode_ranges*), or AC over Huffman's table and ctx_bits (w3_aoh_decode_ranges*).
+struct RangeDec {
+    const ParsedSpec *ps = nullptr;
+    const w3_huff_code *aoh_code = nullptr; uint8_t aoh_ctx_bits = 0;
+};
+// (the AOH decoders live with their family, below)
+static int aoh_decode_run(w3_ctx *ctx, hipStream_t s, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *d_cin, const uint32_t *d_lens, uint32_t nb,
+                          size_t block_size, uint64_t orig_len, uint8_t *d_out, const DecodeJob *d_jobs, uint32_t n_jobs, uint32_t max_job_len, bool spec);
+static bool aoh_ranges_take_spec(const w3_ctx *ctx, uint8_t ctx_bits);
+
+// Decode the jobs (d_jobs[n_jobs], stream indices into d_lens[nb] / d_cin; the longest decodes max_job_len bytes) into the staging
+// buffer, then gather the pieces (d_chunks[n_chunks], at most W3_GATHER_PIECE_MAX bytes each) into d_out.
+static int ranges_run(w3_ctx *ctx, hipStream_t s, const RangeDec &rd, const uint8_t *d_cin, const uint32_t *d_lens, uint32_t nb, size_t block_size,
+                      uint64_t orig_len, const DecodeJob *d_jobs, uint32_t n_jobs, uint32_t max_job_len, const RangePiece *d_chunks, uint32_t n_chunks,
+                      uint64_t staging, uint8_t *d_out) {
     ENSURE(ctx, ctx->rg_stage, (size_t)staging + 16);   // (k_gather_pieces reads up to 3 bytes past a piece)
     uint8_t *d_stage = (uint8_t *)ctx->rg_stage.p;
-    const int rc = ps.is_cm() ? cm_decode(ctx, s, ps, d_cin, d_lens, nb, block_size, orig_len, d_stage, d_jobs, n_jobs)
-                              : generic_decode(ctx, s, ps, d_cin, d_lens, nb, block_size, orig_len, d_stage, d_jobs, n_jobs);
+    const int rc = !rd.ps ? aoh_decode_run(ctx, s, rd.aoh_code, rd.aoh_ctx_bits, d_cin, d_lens, nb, block_size, orig_len, d_stage, d_jobs, n_jobs, max_job_len,
+                                           aoh_ranges_take_spec(ctx, rd.aoh_ctx_bits))
+                 : rd.ps->is_cm() ? cm_decode(ctx, s, *rd.ps, d_cin, d_lens, nb, block_size, orig_len, d_stage, d_jobs, n_jobs)
+                                  : generic_decode(ctx, s, *rd.ps, d_cin, d_lens, nb, block_size, orig_len, d_stage, d_jobs, n_jobs);
     if (rc) return rc;
     hipLaunchKernelGGL(k_gather_pieces, dim3(std::min<uint32_t>(n_chunks, 4096u)), dim3(256), 0, s, (const uint8_t *)d_stage, d_chunks, n_chunks, d_out);
     HIPCHK(ctx, hipGetLastError());
     return W3_OK;
 }
 
-extern "C" int w3_decode_ranges_device(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *d_in, size_t in_len, const uint32_t *d_block_lens,
-                                       size_t nblocks, size_t block_size, uint64_t orig_len, const w3_range *ranges, size_t n_ranges,
-                                       uint8_t *d_out, size_t out_cap, size_t *out_len, void *stream) {
-    if (!ctx) return W3_E_INVALID;
-    if (out_len) *out_len = 0;
-    int rc = check_args(ctx, (size_t)orig_len, block_size);
-    if (rc) return rc;
-    if ((rc = jobs_idle(ctx))) return rc;   // (job 0's HuffHistory tables, length scan and model tables)
-    ParsedSpec ps;
-    if ((rc = parse_spec(spec, ps))) { ctx->err = "malformed model spec"; return rc; }
-    if (!out_len) return W3_E_INVALID;
+// w3_decode_ranges_device / w3_aoh_decode_ranges_device behind their argument checks (*out_len is 0 on entry)
+static int ranges_device(w3_ctx *ctx, const RangeDec &rd, const uint8_t *d_in, size_t in_len, const uint32_t *d_block_lens, size_t nblocks, size_t block_size,
+                         uint64_t orig_len, const w3_range *ranges, size_t n_ranges, uint8_t *d_out, size_t out_cap, size_t *out_len, void *stream) {
+    int rc;
     RangePlan p;
     if (plan_ranges(orig_len, block_size, nblocks, ranges, n_ranges, p)) return ranges_invalid(ctx, orig_len, block_size, nblocks);
     *out_len = (size_t)p.out_len;
@@ -1693,7 +1699,7 @@ extern "C" int w3_decode_ranges_device(w3_ctx *ctx, const w3_model_spec *spec, c
     if (!d_in || !d_block_lens || !d_out) return W3_E_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    if ((rc = stage_huff(ctx, s, ps))) return rc;
+    if (rd.ps && (rc = stage_huff(ctx, s, *rd.ps))) return rc;
     {   // the length table must not claim more than the caller's buffer holds (as w3_decode_blocks_device)
         ENSURE(ctx, ctx->coffs, nblocks * 8);
         ENSURE(ctx, ctx->total, 8);
@@ -1708,17 +1714,33 @@ extern "C" int w3_decode_ranges_device(w3_ctx *ctx, const w3_model_spec *spec, c
     const std::vector<uint8_t> meta = ranges_meta(p.jobs, chunks, coff);
     ENSURE(ctx, ctx->rg_meta, meta.size());
     HIPCHK(ctx, hipMemcpyAsync(ctx->rg_meta.p, meta.data(), meta.size(), hipMemcpyHostToDevice, s));
-    rc = ranges_run(ctx, s, ps, d_in, d_block_lens, (uint32_t)nblocks, block_size, orig_len, (const DecodeJob *)ctx->rg_meta.p, (uint32_t)p.jobs.size(),
-                    (const RangePiece *)((uint8_t *)ctx->rg_meta.p + coff), (uint32_t)chunks.size(), p.staging, d_out);
+    rc = ranges_run(ctx, s, rd, d_in, d_block_lens, (uint32_t)nblocks, block_size, orig_len, (const DecodeJob *)ctx->rg_meta.p, (uint32_t)p.jobs.size(),
+                    p.jobs[0].len, (const RangePiece *)((uint8_t *)ctx->rg_meta.p + coff), (uint32_t)chunks.size(), p.staging, d_out);
     if (rc) return rc;
     HIPCHK(ctx, hipStreamSynchronize(s));   // (meta: pageable memory of this frame)
     return W3_OK;
 }
 
+extern "C" int w3_decode_ranges_device(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *d_in, size_t in_len, const uint32_t *d_block_lens,
+                                       size_t nblocks, size_t block_size, uint64_t orig_len, const w3_range *ranges, size_t n_ranges,
+                                       uint8_t *d_out, size_t out_cap, size_t *out_len, void *stream) {
+    if (!ctx) return W3_E_INVALID;
+    if (out_len) *out_len = 0;
+    int rc = check_args(ctx, (size_t)orig_len, block_size);
+    if (rc) return rc;
+    if ((rc = jobs_idle(ctx))) return rc;   // (job 0's HuffHistory tables, length scan and model tables)
+    ParsedSpec ps;
+    if ((rc = parse_spec(spec, ps))) { ctx->err = "malformed model spec"; return rc; }
+    if (!out_len) return W3_E_INVALID;
+    RangeDec rd;
+    rd.ps = &ps;
+    return ranges_device(ctx, rd, d_in, in_len, d_block_lens, nblocks, block_size, orig_len, ranges, n_ranges, d_out, out_cap, out_len, stream);
+}
+
 // One device call of the host variant: only the selected blocks' streams go over PCIe, with the compact length table, the jobs (naming
 // streams by their index in that table) and the gather's pieces — all in one pinned buffer, one H2D copy — then one D2H copy of the
 // packed output.  The ranges were validated by the caller; the length table's total was checked against in_len.
-static int ranges_host_one(w3_ctx *ctx, const ParsedSpec &ps, const uint8_t *in, const uint32_t *block_lens, size_t nblocks, size_t block_size,
+static int ranges_host_one(w3_ctx *ctx, const RangeDec &rd, const uint8_t *in, const uint32_t *block_lens, size_t nblocks, size_t block_size,
                            uint64_t orig_len, const w3_range *ranges, size_t n_ranges, uint8_t *out) {
     RangePlan p;
     if (plan_ranges(orig_len, block_size, nblocks, ranges, n_ranges, p)) return ranges_invalid(ctx, orig_len, block_size, nblocks);
@@ -1760,27 +1782,20 @@ static int ranges_host_one(w3_ctx *ctx, const ParsedSpec &ps, const uint8_t *in,
     ENSURE(ctx, ctx->io_out, (size_t)p.out_len);
     uint8_t *d = (uint8_t *)ctx->rg_meta.p;
     HIPCHK(ctx, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
-    int rc = stage_huff(ctx, s, ps);
+    int rc = rd.ps ? stage_huff(ctx, s, *rd.ps) : W3_OK;
     if (rc) return rc;
-    rc = ranges_run(ctx, s, ps, d + str_off, (const uint32_t *)(d + lens_off), (uint32_t)nd, block_size, orig_len, (const DecodeJob *)d, (uint32_t)nd,
-                    (const RangePiece *)(d + coff), (uint32_t)chunks.size(), p.staging, (uint8_t *)ctx->io_out.p);
+    rc = ranges_run(ctx, s, rd, d + str_off, (const uint32_t *)(d + lens_off), (uint32_t)nd, block_size, orig_len, (const DecodeJob *)d, (uint32_t)nd,
+                    p.jobs[0].len, (const RangePiece *)(d + coff), (uint32_t)chunks.size(), p.staging, (uint8_t *)ctx->io_out.p);
     if (rc) return rc;
     HIPCHK(ctx, hipMemcpyAsync(out, ctx->io_out.p, (size_t)p.out_len, hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
     return W3_OK;
 }
 
-extern "C" int w3_decode_ranges(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t in_len, const uint32_t *block_lens,
-                                size_t nblocks, size_t block_size, uint64_t orig_len, const w3_range *ranges, size_t n_ranges,
-                                uint8_t *out, size_t out_cap, size_t *out_len) {
-    if (!ctx) return W3_E_INVALID;
-    if (out_len) *out_len = 0;
-    int rc = check_args(ctx, (size_t)orig_len, block_size, false);   // (any length: a large selection goes through in several device calls)
-    if (rc) return rc;
-    if ((rc = jobs_idle(ctx))) return rc;
-    ParsedSpec ps;
-    if ((rc = parse_spec(spec, ps))) { ctx->err = "malformed model spec"; return rc; }
-    if (!out_len) return W3_E_INVALID;
+// w3_decode_ranges / w3_aoh_decode_ranges behind their argument checks (*out_len is 0 on entry)
+static int ranges_host(w3_ctx *ctx, const RangeDec &rd, const uint8_t *in, size_t in_len, const uint32_t *block_lens, size_t nblocks, size_t block_size,
+                       uint64_t orig_len, const w3_range *ranges, size_t n_ranges, uint8_t *out, size_t out_cap, size_t *out_len) {
+    int rc;
     RangePlan p;
     if (plan_ranges(orig_len, block_size, nblocks, ranges, n_ranges, p)) return ranges_invalid(ctx, orig_len, block_size, nblocks);
     *out_len = (size_t)p.out_len;
@@ -1794,7 +1809,7 @@ extern "C" int w3_decode_ranges(w3_ctx *ctx, const w3_model_spec *spec, const ui
     // blocks per device call: 2 GiB worth (W3_OPT_HOST_CHUNK_BLOCKS: fewer, for tests), and at most as many bytes of packed output
     const uint64_t capb = ctx->host_chunk_blocks ? (uint64_t)ctx->host_chunk_blocks : (uint64_t)host_call_cap_blocks(block_size);
     if (p.blocks.size() <= capb && p.out_len <= capb * block_size)
-        return ranges_host_one(ctx, ps, in, block_lens, nblocks, block_size, orig_len, ranges, n_ranges, out);
+        return ranges_host_one(ctx, rd, in, block_lens, nblocks, block_size, orig_len, ranges, n_ranges, out);
     // A larger selection: the ranges are cut into parts of at most capb / 2 blocks' worth (each touches at most capb / 2 + 1 blocks), and
     // runs of consecutive parts go through one device call each while their blocks, counted part by part, and bytes stay within the cap.
     // Consecutive parts are consecutive stretches of the output, so each call writes its packed output straight to its place in `out`.
@@ -1803,7 +1818,7 @@ extern "C" int w3_decode_ranges(w3_ctx *ctx, const w3_model_spec *spec, const ui
     uint64_t bblocks = 0, bbytes = 0, dst = 0;
     auto flush = [&]() -> int {
         if (batch.empty()) return W3_OK;
-        const int r = ranges_host_one(ctx, ps, in, block_lens, nblocks, block_size, orig_len, batch.data(), batch.size(), out + dst);
+        const int r = ranges_host_one(ctx, rd, in, block_lens, nblocks, block_size, orig_len, batch.data(), batch.size(), out + dst);
         dst += bbytes;
         batch.clear(); bblocks = 0; bbytes = 0;
         return r;
@@ -1819,6 +1834,22 @@ extern "C" int w3_decode_ranges(w3_ctx *ctx, const w3_model_spec *spec, const ui
         }
     }
     return flush();
+}
+
+extern "C" int w3_decode_ranges(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t in_len, const uint32_t *block_lens,
+                                size_t nblocks, size_t block_size, uint64_t orig_len, const w3_range *ranges, size_t n_ranges,
+                                uint8_t *out, size_t out_cap, size_t *out_len) {
+    if (!ctx) return W3_E_INVALID;
+    if (out_len) *out_len = 0;
+    int rc = check_args(ctx, (size_t)orig_len, block_size, false);   // (any length: a large selection goes through in several device calls)
+    if (rc) return rc;
+    if ((rc = jobs_idle(ctx))) return rc;
+    ParsedSpec ps;
+    if ((rc = parse_spec(spec, ps))) { ctx->err = "malformed model spec"; return rc; }
+    if (!out_len) return W3_E_INVALID;
+    RangeDec rd;
+    rd.ps = &ps;
+    return ranges_host(ctx, rd, in, in_len, block_lens, nblocks, block_size, orig_len, ranges, n_ranges, out, out_cap, out_len);
 }
 
 // ---------------------------------------------------------------------------
@@ -2467,8 +2498,10 @@ static int aoh_prepare(w3_ctx *ctx, hipStream_t s, const w3_huff_code *codes, si
 // 4 << ctx_bits bytes or, when that is smaller, the exact map with next_pow2(2 x steps[c]) slots of 8 bytes (steps[c]: the most
 // steps one lane of configuration c can take).  As many whole configurations per launch as fit the memory budget (the batching of
 // w3_sweep_ordern_device); a configuration whose tables alone exceed it goes in batches of blocks.  Tables are zero-filled per batch.
+// max_lanes (the decoders' job calls under W3_OPT_AOH_BATCH_BLOCKS; 0 = no cap): most lanes per batch.
 template <int MODE>
-static int aoh_launch(w3_ctx *ctx, hipStream_t s, AohArgs a, AohPrep &P, std::vector<AohCfg> &cfg, const std::vector<uint64_t> &steps, uint32_t nb) {
+static int aoh_launch(w3_ctx *ctx, hipStream_t s, AohArgs a, AohPrep &P, std::vector<AohCfg> &cfg, const std::vector<uint64_t> &steps, uint32_t nb,
+                      uint32_t max_lanes = 0) {
     const size_t ncfg = cfg.size();
     for (size_t c = 0; c < ncfg; c++) {
         const uint64_t slots = std::max<uint64_t>(1024, next_pow2(2 * steps[c])), hash_bytes = slots * 8, direct = 4ull << cfg[c].ctx_bits;
@@ -2487,7 +2520,7 @@ static int aoh_launch(w3_ctx *ctx, hipStream_t s, AohArgs a, AohPrep &P, std::ve
         uint64_t need = 0;
         bool fits = true;
         for (size_t c0 = 0; c0 < ncfg && fits;) {
-            if (cfg[c0].stride * nb <= budget) {                       // whole configurations
+            if (cfg[c0].stride * nb <= budget && (!max_lanes || nb <= max_lanes)) {   // whole configurations
                 uint64_t used = 0;
                 size_t c1 = c0;
                 for (; c1 < ncfg && used + cfg[c1].stride * nb <= budget; c1++) { cfg[c1].base = used; used += cfg[c1].stride * nb; }
@@ -2496,6 +2529,7 @@ static int aoh_launch(w3_ctx *ctx, hipStream_t s, AohArgs a, AohPrep &P, std::ve
                 c0 = c1;
             } else {                                                   // one configuration, batches of blocks
                 uint64_t lanes = budget / cfg[c0].stride;
+                if (max_lanes) lanes = std::min<uint64_t>(lanes, max_lanes);
                 if (lanes >= 64) lanes = lanes / 64 * 64;
                 if (lanes == 0) { fits = false; break; }
                 cfg[c0].base = 0;
@@ -2750,6 +2784,80 @@ extern "C" int w3_aoh_encode_blocks(w3_ctx *ctx, const w3_huff_code *code, uint8
     return W3_OK;
 }
 
+// k_aoh_decode_spec (w3_aoh_spec.h) over jobs [0, nl): a direct table of 4 << ctx_bits bytes per job, as many jobs per batch (a
+// multiple of 4: a wavefront takes four) as the memory budget of aoh_launch holds, W3_OPT_AOH_BATCH_BLOCKS caps a batch (tests);
+// the tables are zero-filled per batch on the stream.
+static int aoh_spec_launch(w3_ctx *ctx, hipStream_t s, AohSpecArgs a, uint8_t ctx_bits, uint32_t nl) {
+    const uint64_t stride = std::max<uint64_t>(4ull << ctx_bits, 16);
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(ctx, hipMemGetInfo(&free_b, &total_b));
+    uint64_t budget = std::min<uint64_t>((uint64_t)(free_b + ctx->tables.cap) * 3 / 4, 200ull << 30);
+    uint32_t per = 0;
+    for (;;) {
+        uint64_t lanes = std::min<uint64_t>(budget / stride, nl);
+        if (ctx->aoh_batch_blocks) lanes = std::min<uint64_t>(lanes, ctx->aoh_batch_blocks);
+        if (lanes >= 4) lanes = lanes / 4 * 4;
+        if (lanes == 0) { ctx->err = "the Counter table of one job does not fit the device budget"; return W3_E_NOMEM; }
+        const int rc = ensure(ctx, ctx->tables, (size_t)(lanes * stride));
+        if (rc == W3_OK) { per = (uint32_t)lanes; break; }
+        if (rc != W3_E_NOMEM || budget < (1ull << 20)) return rc;
+        budget /= 2;   // (as aoh_launch)
+    }
+    a.tables = (uint8_t *)ctx->tables.p; a.stride = stride; a.ctx_mask = (uint32_t)((1ull << ctx_bits) - 1ull);
+    for (uint32_t first = 0; first < nl; first += per) {
+        const uint32_t cnt = std::min(per, nl - first);
+        HIPCHK(ctx, hipMemsetAsync(ctx->tables.p, 0, (size_t)(cnt * stride), s));
+        a.first = first; a.count = cnt;
+        hipLaunchKernelGGL(k_aoh_decode_spec, dim3((cnt + 3u) / 4u), dim3(64), 0, s, a);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    return W3_OK;
+}
+
+// which decoder a ranges call takes: the sixteen-lane kernel where it covers, unless W3_OPT_VARIANT bit 1024 asks for the lane kernel
+static bool aoh_ranges_take_spec(const w3_ctx *ctx, uint8_t ctx_bits) {
+    return aoh_spec_covers(ctx_bits) && !(ctx->tp.variant & W3_VAR_DECODE_LANE);
+}
+// ... and the full decode: the lane kernel, as before the sixteen-lane kernel existed, unless bit 2048 asks for that one (an untimed
+// form does not become a default: DESIGN.md 7)
+static bool aoh_full_take_spec(const w3_ctx *ctx, uint8_t ctx_bits) {
+    return (ctx->tp.variant & W3_VAR_AOH_DECODE_SPEC) && aoh_ranges_take_spec(ctx, ctx_bits);
+}
+
+// The decoders of the family on device-resident streams (d_lens[nb], validated by the caller): every block whole into d_out
+// (d_jobs == nullptr), or the n_jobs decode jobs of a ranges call (w3_ranges.h; the longest decodes max_job_len bytes) into d_out =
+// the staging buffer.  spec: k_aoh_decode_spec, else k_aoh<AOH_DECODE>.  Does not synchronise after the launches.
+static int aoh_decode_run(w3_ctx *ctx, hipStream_t s, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *d_cin, const uint32_t *d_lens, uint32_t nb,
+                          size_t block_size, uint64_t orig_len, uint8_t *d_out, const DecodeJob *d_jobs, uint32_t n_jobs, uint32_t max_job_len, bool spec) {
+    int rc;
+    const unsigned max_len = w3aoh::max_len(code);
+    if (d_jobs) {   // the streams' offsets (the full decode's caller has scanned the table to validate it)
+        ENSURE(ctx, ctx->coffs, (size_t)nb * 8);
+        ENSURE(ctx, ctx->total, 8);
+        hipLaunchKernelGGL(k_scan_lens, dim3(1), dim3(1024), 0, s, d_lens, (uint64_t *)ctx->coffs.p, (uint64_t *)ctx->total.p, nb);
+    }
+    AohPrep P;
+    if ((rc = aoh_prepare(ctx, s, code, 1, 1, nb, nullptr, (size_t)orig_len, block_size, P))) return rc;
+    const uint32_t nl = d_jobs ? n_jobs : nb;
+    if (spec) {
+        AohSpecArgs sa;
+        memset(&sa, 0, sizeof sa);
+        sa.code = P.d_codes; sa.jobs = d_jobs; sa.n = orig_len; sa.block_size = (uint32_t)block_size;
+        sa.cin = d_cin; sa.coffs = (const uint64_t *)ctx->coffs.p; sa.clens = d_lens; sa.dout = d_out;
+        return aoh_spec_launch(ctx, s, sa, ctx_bits, nl);
+    }
+    std::vector<AohCfg> cfg(1);
+    memset(&cfg[0], 0, sizeof cfg[0]);
+    cfg[0].ctx_bits = ctx_bits;
+    // the decoder does not know a stream's bit count before it has decoded it: the map is sized for the most steps a lane can take
+    std::vector<uint64_t> steps(1, (uint64_t)(d_jobs ? max_job_len : std::min<uint64_t>(block_size, orig_len)) * max_len);
+    AohArgs a;
+    memset(&a, 0, sizeof a);
+    a.n = orig_len; a.block_size = (uint32_t)block_size;
+    a.cin = d_cin; a.coffs = (const uint64_t *)ctx->coffs.p; a.clens = d_lens; a.dout = d_out; a.jobs = d_jobs;
+    return aoh_launch<AOH_DECODE>(ctx, s, a, P, cfg, steps, nl, d_jobs ? ctx->aoh_batch_blocks : 0u);
+}
+
 extern "C" int w3_aoh_decode_blocks_device(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *d_in, size_t in_len,
                                            const uint32_t *d_block_lens, size_t nblocks, size_t block_size, uint64_t orig_len, uint8_t *d_out, void *stream) {
     int rc = aoh_check(ctx, code, 1, &ctx_bits, 1, (size_t)orig_len, block_size, true);
@@ -2758,8 +2866,7 @@ extern "C" int w3_aoh_decode_blocks_device(w3_ctx *ctx, const w3_huff_code *code
     if (nb != nblocks) { ctx->err = "nblocks does not match orig_len/block_size"; return W3_E_INVALID; }
     if (nb == 0) return W3_OK;
     if (!d_in || !d_block_lens || !d_out) return W3_E_INVALID;
-    const unsigned max_len = w3aoh::max_len(code);
-    if (max_len == 0) { ctx->err = "a table without symbols decodes nothing"; return W3_E_INVALID; }
+    if (w3aoh::max_len(code) == 0) { ctx->err = "a table without symbols decodes nothing"; return W3_E_INVALID; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     {   // the length table must not claim more than the caller's buffer holds (w3_decode_blocks_device)
@@ -2771,21 +2878,50 @@ extern "C" int w3_aoh_decode_blocks_device(w3_ctx *ctx, const w3_huff_code *code
         HIPCHK(ctx, hipStreamSynchronize(s));
         if (total > in_len) { ctx->err = "block length table claims " + std::to_string(total) + " compressed bytes, the buffer holds " + std::to_string(in_len); return W3_E_FORMAT; }
     }
-    AohPrep P;
-    if ((rc = aoh_prepare(ctx, s, code, 1, 1, (uint32_t)nb, nullptr, (size_t)orig_len, block_size, P))) return rc;
-    std::vector<AohCfg> cfg(1);
-    memset(&cfg[0], 0, sizeof cfg[0]);
-    cfg[0].ctx_bits = ctx_bits;
-    // the decoder does not know a block's bit count before it has decoded it: the map is sized for the most steps a block can take
-    std::vector<uint64_t> steps(1, (uint64_t)std::min<uint64_t>(block_size, orig_len) * max_len);
-    AohArgs a;
-    memset(&a, 0, sizeof a);
-    a.n = orig_len; a.block_size = (uint32_t)block_size;
-    a.cin = d_in; a.coffs = (const uint64_t *)ctx->coffs.p; a.clens = d_block_lens; a.dout = d_out;
-    if ((rc = aoh_launch<AOH_DECODE>(ctx, s, a, P, cfg, steps, (uint32_t)nb))) return rc;
+    const bool spec = aoh_full_take_spec(ctx, ctx_bits);
+    if ((rc = aoh_decode_run(ctx, s, code, ctx_bits, d_in, d_block_lens, (uint32_t)nb, block_size, orig_len, d_out, nullptr, 0, 0, spec))) return rc;
     HIPCHK(ctx, hipStreamSynchronize(s));
+    ctx->timing.path = spec ? W3_PATH_SPEC : W3_PATH_GENERIC;
     return W3_OK;
 }
+
+// Random access on the family's streams (w3hip.h): the plan, the workspace and the gather are those of w3_decode_ranges[_device]
+// (ranges_host / ranges_device), the decoder is aoh_decode_run over the plan's jobs.
+static int aoh_ranges_check(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, size_t block_size, uint64_t orig_len, bool one_device, size_t *out_len) {
+    if (out_len) *out_len = 0;
+    int rc = aoh_check(ctx, code, 1, &ctx_bits, 1, (size_t)orig_len, block_size, one_device);
+    if (rc) return rc;
+    if (w3aoh::max_len(code) == 0) { ctx->err = "a table without symbols decodes nothing"; return W3_E_INVALID; }
+    return out_len ? W3_OK : W3_E_INVALID;
+}
+
+extern "C" int w3_aoh_decode_ranges_device(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *d_in, size_t in_len,
+                                           const uint32_t *d_block_lens, size_t nblocks, size_t block_size, uint64_t orig_len, const w3_range *ranges,
+                                           size_t n_ranges, uint8_t *d_out, size_t out_cap, size_t *out_len, void *stream) {
+    if (!ctx) return W3_E_INVALID;
+    int rc = aoh_ranges_check(ctx, code, ctx_bits, block_size, orig_len, true, out_len);
+    if (rc) return rc;
+    RangeDec rd;
+    rd.aoh_code = code; rd.aoh_ctx_bits = ctx_bits;
+    if ((rc = ranges_device(ctx, rd, d_in, in_len, d_block_lens, nblocks, block_size, orig_len, ranges, n_ranges, d_out, out_cap, out_len, stream))) return rc;
+    ctx->timing.path = aoh_ranges_take_spec(ctx, ctx_bits) ? W3_PATH_SPEC : W3_PATH_GENERIC;
+    return W3_OK;
+}
+
+extern "C" int w3_aoh_decode_ranges(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *in, size_t in_len, const uint32_t *block_lens,
+                                    size_t nblocks, size_t block_size, uint64_t orig_len, const w3_range *ranges, size_t n_ranges, uint8_t *out,
+                                    size_t out_cap, size_t *out_len) {
+    if (!ctx) return W3_E_INVALID;
+    int rc = aoh_ranges_check(ctx, code, ctx_bits, block_size, orig_len, false, out_len);   // (any length, as w3_decode_ranges)
+    if (rc) return rc;
+    RangeDec rd;
+    rd.aoh_code = code; rd.aoh_ctx_bits = ctx_bits;
+    if ((rc = ranges_host(ctx, rd, in, in_len, block_lens, nblocks, block_size, orig_len, ranges, n_ranges, out, out_cap, out_len))) return rc;
+    ctx->timing.path = aoh_ranges_take_spec(ctx, ctx_bits) ? W3_PATH_SPEC : W3_PATH_GENERIC;
+    return W3_OK;
+}
+
+extern "C" int w3_aoh_decode_spec_covers(uint8_t ctx_bits) { return aoh_spec_covers(ctx_bits) ? 1 : 0; }
 
 extern "C" int w3_aoh_decode_blocks(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *in, size_t in_len, const uint32_t *block_lens,
                                     size_t nblocks, size_t block_size, uint64_t orig_len, uint8_t *out) {
