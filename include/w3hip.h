@@ -170,7 +170,8 @@ enum {
                            where the instance specialised for all-raw-history models would run */
     W3_OPT_FAULT_BLOCK = 10, /* test hook, with W3_OPT_VARIANT bit 32: the one block the injected fault hits (-1 = every block, default) */
     W3_OPT_HOST_CHUNK_BLOCKS = 12, /* w3_encode_blocks: blocks per pipelined piece of a host-buffer call (0 = default: equal pieces of at most
-                           4,096 blocks; tests use small values to get ragged pieces) */
+                           4,096 blocks; tests use small values to get ragged pieces).  w3_decode_blocks, w3_decode_ranges and the w3_aoh_*
+                           host-buffer calls: blocks per device call (0 = default: 2 GiB worth) */
     W3_OPT_FAULT_KERNELS = 13, /* test hook, with W3_OPT_VARIANT bit 32: bit mask (1 .. 7) of the kernels whose returning LDS adds the injected
                            fault mis-orders — 1 = k_predict_small's rounds (default), 2 = k_rank_sorted's rounds, 4 = k_partition8's
                            cursor adds (two records of one bin swap their slots in the tile: a permutation, never another index) */

@@ -1,6 +1,7 @@
 """AC over Huffman on the device (w3_aoh_*; bin/ac-over-huffman/main.rs:69-89) against the CPU truth of tests/aoh_ref.py, byte for byte:
 streams, length tables, ACStats bit counts, decode, the sweep, refusals, the CLI's version-2 container.  Every case runs on each
-path that is built: the fused lane-per-block kernel (W3_PATH_GENERIC) and, when the library has one, the two-phase form."""
+path that is built: the fused lane-per-block kernel (W3_PATH_GENERIC) and, when the library has one, the two-phase form.  The
+host-buffer calls go through in runs of whole blocks, one device call each; W3_OPT_HOST_CHUNK_BLOCKS sets the run length."""
 import ctypes as C
 import os
 import subprocess
@@ -351,3 +352,25 @@ def test_cli_version_2_container(ctx, oracle, build_dir, tmp_path):
         r = run("t", str(g), W3_MODEL="aoh")
         assert r.returncode == 0, r.stderr
         assert (tmp_path / (name[:-4] + ".orig")).read_bytes() == content
+
+
+def test_host_calls_in_runs(ctx, oracle, build_dir, text):
+    """10 blocks of 1,024 bytes and a 77-byte tail under W3_OPT_HOST_CHUNK_BLOCKS = 3 (four runs, the last of two blocks, one ragged), 1 (a
+    run per block) and 64 (one run), and without the option: encode, the counting sink and decode equal the CPU truth whatever the runs."""
+    bs, cb = 1024, 12
+    data = text[:10 * bs + 77]
+    codes, lens = aoh_ref.code_table(oracle, text, 12)
+    code = _code(codes, lens)
+    want, wlens = aoh_ref.encode_blocks(oracle, build_dir, codes, lens, cb, data, bs)
+    wbits = aoh_ref.stats_bits(oracle, build_dir, codes, lens, cb, data, bs)
+    assert len(wlens) == 11
+    try:
+        for runs_of in (3, 1, 64, 0):
+            ctx.set_host_chunk_blocks(runs_of)
+            out, glens = ctx.aoh_encode_blocks(code, cb, data, bs)
+            assert ctx.timing()["n_parts"] == ((11 + runs_of - 1) // runs_of if runs_of else 1), runs_of
+            assert glens.tolist() == wlens.tolist() and out.tobytes() == want, runs_of
+            assert ctx.aoh_encode_stats(code, cb, data, bs).tolist() == wbits.tolist(), runs_of
+            assert ctx.aoh_decode_blocks(code, cb, np.frombuffer(want, dtype=np.uint8), wlens, bs, len(data)).tobytes() == bytes(data), runs_of
+    finally:
+        ctx.set_host_chunk_blocks(0)

@@ -1,6 +1,7 @@
 """GPU parity of the HOST-BUFFER path (compress() of main.rs:89-113 reads a file and writes a file): w3_encode_blocks cut into
 pipelined pieces, and w3_encode_host_submit / w3_encode_host_wait with calls in flight — against the CPU oracle, byte for byte,
-from pageable and from pinned memory."""
+from pageable and from pinned memory.  W3_OPT_HOST_CHUNK_BLOCKS is the piece size of w3_encode_blocks and the run length of w3_decode_blocks,
+of the ranges calls and of AC over Huffman's host-buffer calls (tests/test_gpu_aoh.py)."""
 import numpy as np
 import pytest
 

@@ -112,7 +112,8 @@ class Context:
         self._chk(self.lib.w3_ctx_set_option(self.h, L.W3_OPT_SLOT_BUDGET_MB, int(mb)))
 
     def set_host_chunk_blocks(self, blocks=0):
-        """W3_OPT_HOST_CHUNK_BLOCKS: blocks per pipelined piece of a host-buffer call (0 = default)."""
+        """W3_OPT_HOST_CHUNK_BLOCKS: blocks per pipelined piece of encode_blocks, and per device call of decode_blocks, decode_ranges
+        and the aoh_* host-buffer calls (0 = default)."""
         self._chk(self.lib.w3_ctx_set_option(self.h, L.W3_OPT_HOST_CHUNK_BLOCKS, int(blocks)))
 
     def set_aoh_batch_blocks(self, blocks):

@@ -21,6 +21,7 @@
 #include "w3_slot.h"
 #include "w3_slot2.h"
 #include "w3_spec.h"
+#include "w3_tables_plan.h"
 
 // Tuning / timing-experiment hooks read from the environment exist only in -DW3_TUNING builds: the shipped library never
 // calls getenv.  (Some of them make the kernels skip work, i.e. produce wrong results.)
@@ -161,8 +162,6 @@ struct TwoPhaseWs {
         P_cap = keys_cap = perm_cap = redo_cap = streams_cap = 0;
     }
 };
-
-static inline uint64_t tp_next_pow2(uint64_t v) { uint64_t p = 1; while (p < v) p <<= 1; return p; }
 
 static inline int tp_ensure(void *&p, size_t &cap, size_t bytes, std::string &err) {
     if (p && bytes <= cap) return W3_OK;
@@ -372,14 +371,14 @@ static inline int twophase_predict_a(TwoPhaseWs &ws, hipStream_t s, const Parsed
         }
         if (c == LEAF_WAVE) {
             // wave per block, time order, Counter table in HBM (w3_predict_wave.h)
-            const uint64_t hash_slots = std::max<uint64_t>(1024, tp_next_pow2(16ull * block_size));
-            const uint64_t hash_bytes = 8ull * hash_slots + 16ull, direct_bytes = std::max<uint64_t>(4ull << nd.bits, 16ull);
+            const w3::CounterTable ct = w3::counter_table(nd.bits, 8ull * block_size);
+            const uint64_t hash_bytes = ct.hash_bytes + 16ull, direct_bytes = std::max<uint64_t>(ct.direct_bytes, 16ull);   // (ctx 0's own slot behind the map)
             w3::WaveArgs wa;
             memset(&wa, 0, sizeof wa);
             wa.in = d_in; wa.n = n; wa.block_size = (uint32_t)block_size; wa.nblocks = nb; wa.P = (uint16_t *)pa.P;
             wa.align = nd.align; wa.hist_mask = (uint32_t)((1ull << (nd.bits - nd.align)) - 1ull);
-            wa.use_hash = (nd.bits >= 32 || direct_bytes > hash_bytes) ? 1u : 0u;
-            wa.hash_slots = (uint32_t)hash_slots;
+            wa.use_hash = (nd.bits >= 32 || ct.use_hash) ? 1u : 0u;
+            wa.hash_slots = (uint32_t)ct.slots;
             wa.table_stride = wa.use_hash ? hash_bytes : direct_bytes;
             size_t free_b = 0, total_b = 0;
             if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); err = "hipMemGetInfo failed"; return W3_E_HIP; }

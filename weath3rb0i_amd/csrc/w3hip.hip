@@ -20,6 +20,7 @@
 #include "w3_cm.h"
 #include "w3_decode_spec.h"
 #include "w3_pack.h"
+#include "w3_tables_plan.h"
 #include "w3_twophase.h"
 #include "w3_selftest.h"
 #include "w3_sweep.h"
@@ -438,17 +439,8 @@ extern "C" int w3_spec_validate(const w3_model_spec *spec) {
     return parse_spec(spec, ps);
 }
 
-static uint64_t next_pow2(uint64_t v) {
-    uint64_t p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
-
 // Lay out the per-lane model tables of the generic path.
 static uint64_t layout_generic(const ParsedSpec &ps, size_t block_size, GenericArgs &ga) {
-    const uint64_t steps = (uint64_t)block_size * 8;
-    const uint64_t hash_slots = std::max<uint64_t>(1024, next_pow2(2 * steps));
-    const uint64_t hash_bytes = hash_slots * 8;
     uint64_t off = 0;
     ga.n_leaves = ps.n_leaves;
     for (int l = 0; l < ps.n_leaves; l++) {
@@ -466,9 +458,9 @@ static uint64_t layout_generic(const ParsedSpec &ps, size_t block_size, GenericA
         }
         lp.hist_mask = (uint32_t)((1ull << (nd.bits - nd.align)) - 1ull);
         if (nd.frozen) continue;
-        const uint64_t direct_bytes = 4ull << nd.bits;
-        if (direct_bytes <= hash_bytes) { lp.use_hash = 0; off += direct_bytes; }
-        else { lp.use_hash = 1; lp.hash_mask = (uint32_t)(hash_slots - 1); off += hash_bytes; }
+        const CounterTable t = counter_table(nd.bits, (uint64_t)block_size * 8);
+        lp.use_hash = t.use_hash; lp.hash_mask = t.use_hash ? (uint32_t)(t.slots - 1) : 0u;
+        off += t.use_hash ? t.hash_bytes : t.direct_bytes;
     }
     return std::max<uint64_t>(off, 16);
 }
@@ -476,6 +468,23 @@ static uint64_t layout_generic(const ParsedSpec &ps, size_t block_size, GenericA
 // ACHistory leaves of the lane-per-block kernels: tabulate the coder states of every 16-bit history prefix once per call
 // (k_achash_lut, w3_predict.h) so that leaf_ctx looks the hash up instead of running the nested coder bit by bit.
 static int prepare_achash_luts(w3_ctx *ctx, hipStream_t s, GenericArgs &ga);
+
+// the decoders' length table: enqueue the exclusive scan of d_lens[nb] into ctx->coffs, its sum into ctx->total
+static int scan_lens(w3_ctx *ctx, hipStream_t s, const uint32_t *d_lens, uint32_t nb) {
+    ENSURE(ctx, ctx->coffs, (size_t)nb * 8);
+    ENSURE(ctx, ctx->total, 8);
+    hipLaunchKernelGGL(k_scan_lens, dim3(1), dim3(1024), 0, s, d_lens, (uint64_t *)ctx->coffs.p, (uint64_t *)ctx->total.p, nb);
+    return W3_OK;
+}
+// ... and the table must not claim more than the caller's buffer holds: the kernels read cin + offset for clens[b] bytes
+static int check_len_table(w3_ctx *ctx, hipStream_t s, const uint32_t *d_lens, uint32_t nb, size_t in_len) {
+    if (const int rc = scan_lens(ctx, s, d_lens, nb)) return rc;
+    uint64_t total = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&total, ctx->total.p, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    if (total > in_len) { ctx->err = "block length table claims " + std::to_string(total) + " compressed bytes, the buffer holds " + std::to_string(in_len); return W3_E_FORMAT; }
+    return W3_OK;
+}
 
 // ---------------------------------------------------------------------------
 // pack: scan block lengths, compact stripes into d_out
@@ -552,6 +561,19 @@ static int decode_group_bits(const w3_ctx *ctx, uint32_t blocks_in_batch) {
     return (ctx->tp.tune & 16384u) ? 2 : 4;
 }
 
+// k_generic over cnt lanes; 1-4 leaves: all Counter loads of a step in flight together
+template <bool DECODE>
+static void launch_generic(const GenericArgs &ga, uint32_t cnt, hipStream_t s) {
+    const dim3 grid((cnt + 63) / 64), blk(64);
+    switch (ga.n_leaves) {
+    case 1: hipLaunchKernelGGL((k_generic_nl<DECODE, 1>), grid, blk, 0, s, ga); break;
+    case 2: hipLaunchKernelGGL((k_generic_nl<DECODE, 2>), grid, blk, 0, s, ga); break;
+    case 3: hipLaunchKernelGGL((k_generic_nl<DECODE, 3>), grid, blk, 0, s, ga); break;
+    case 4: hipLaunchKernelGGL((k_generic_nl<DECODE, 4>), grid, blk, 0, s, ga); break;
+    default: hipLaunchKernelGGL(k_generic<DECODE>, grid, blk, 0, s, ga); break;
+    }
+}
+
 static int generic_encode(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, const uint8_t *d_in, size_t n, size_t block_size,
                           uint32_t nb, uint32_t stripe_cap, uint32_t *d_lens) {
     GenericArgs ga;
@@ -572,13 +594,7 @@ static int generic_encode(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, cons
         ga.first_block = first; ga.n_lanes = cnt;
         ga.stripes = (uint8_t *)ctx->stripes.p + (uint64_t)first * stripe_cap;
         HIPCHK(ctx, hipMemsetAsync(ctx->tables.p, 0, (size_t)cnt * lane_stride, s));
-        switch (ga.n_leaves) {   // 1-4 leaves: all Counter loads of a step in flight together
-        case 1: hipLaunchKernelGGL((k_generic_nl<false, 1>), dim3((cnt + 63) / 64), dim3(64), 0, s, ga); break;
-        case 2: hipLaunchKernelGGL((k_generic_nl<false, 2>), dim3((cnt + 63) / 64), dim3(64), 0, s, ga); break;
-        case 3: hipLaunchKernelGGL((k_generic_nl<false, 3>), dim3((cnt + 63) / 64), dim3(64), 0, s, ga); break;
-        case 4: hipLaunchKernelGGL((k_generic_nl<false, 4>), dim3((cnt + 63) / 64), dim3(64), 0, s, ga); break;
-        default: hipLaunchKernelGGL(k_generic<false>, dim3((cnt + 63) / 64), dim3(64), 0, s, ga); break;
-        }
+        launch_generic<false>(ga, cnt, s);
         HIPCHK(ctx, hipGetLastError());
     }
     return W3_OK;
@@ -587,6 +603,7 @@ static int generic_encode(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, cons
 // The decoders: every block of the length table d_lens[nb] whole (d_jobs == nullptr), or the n_jobs decode jobs of d_jobs (the
 // random-access decode: w3_ranges.h) — the lanes, and with them the table budget's batches, the table zero-fill, the APM tables'
 // initialisation and k_decode_spec's choices, then count jobs instead of blocks.
+// Precondition: ctx->coffs holds the exclusive scan of d_lens[nb], enqueued on s (scan_lens / check_len_table).
 static int generic_decode(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, const uint8_t *d_cin, const uint32_t *d_lens, uint32_t nb,
                           size_t block_size, uint64_t orig_len, uint8_t *d_out, const DecodeJob *d_jobs = nullptr, uint32_t n_jobs = 0) {
     GenericArgs ga;
@@ -598,9 +615,6 @@ static int generic_decode(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, cons
     if (rc) return rc;
     if ((rc = prepare_achash_luts(ctx, s, ga))) return rc;
     ENSURE(ctx, ctx->tables, (size_t)lanes * lane_stride);
-    ENSURE(ctx, ctx->coffs, (size_t)nb * 8);
-    ENSURE(ctx, ctx->total, 8);
-    hipLaunchKernelGGL(k_scan_lens, dim3(1), dim3(1024), 0, s, d_lens, (uint64_t *)ctx->coffs.p, (uint64_t *)ctx->total.p, nb);
     ga.n = orig_len; ga.block_size = (uint32_t)block_size;
     ga.huff = ctx->tp.huff; ga.n_huff = (int)ps.n_huff;
     ga.tables = (uint8_t *)ctx->tables.p; ga.lane_stride = lane_stride;
@@ -621,13 +635,7 @@ static int generic_decode(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, cons
                 continue;
             }
         }
-        switch (ga.n_leaves) {
-        case 1: hipLaunchKernelGGL((k_generic_nl<true, 1>), dim3((cnt + 63) / 64), dim3(64), 0, s, ga); break;
-        case 2: hipLaunchKernelGGL((k_generic_nl<true, 2>), dim3((cnt + 63) / 64), dim3(64), 0, s, ga); break;
-        case 3: hipLaunchKernelGGL((k_generic_nl<true, 3>), dim3((cnt + 63) / 64), dim3(64), 0, s, ga); break;
-        case 4: hipLaunchKernelGGL((k_generic_nl<true, 4>), dim3((cnt + 63) / 64), dim3(64), 0, s, ga); break;
-        default: hipLaunchKernelGGL(k_generic<true>, dim3((cnt + 63) / 64), dim3(64), 0, s, ga); break;
-        }
+        launch_generic<true>(ga, cnt, s);
         HIPCHK(ctx, hipGetLastError());
     }
     return W3_OK;
@@ -730,15 +738,13 @@ static int cm_encode(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, const uin
     return cm_run<false>(ctx, s, ca, lane_stride, nb, stripe_cap);
 }
 
+// (precondition as generic_decode: ctx->coffs holds the exclusive scan of d_lens[nb], enqueued on s)
 static int cm_decode(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, const uint8_t *d_cin, const uint32_t *d_lens, uint32_t nb,
                      size_t block_size, uint64_t orig_len, uint8_t *d_out, const DecodeJob *d_jobs = nullptr, uint32_t n_jobs = 0) {
     CmArgs ca;
     memset(&ca, 0, sizeof ca);
     const uint64_t lane_stride = layout_cm(ps, block_size, ca);
     { int rc_ = prepare_achash_luts(ctx, s, ca.g); if (rc_) return rc_; }
-    ENSURE(ctx, ctx->coffs, (size_t)nb * 8);
-    ENSURE(ctx, ctx->total, 8);
-    hipLaunchKernelGGL(k_scan_lens, dim3(1), dim3(1024), 0, s, d_lens, (uint64_t *)ctx->coffs.p, (uint64_t *)ctx->total.p, nb);
     ca.g.n = orig_len; ca.g.block_size = (uint32_t)block_size;
     ca.g.huff = ctx->tp.huff; ca.g.n_huff = (int)ps.n_huff;
     ca.g.cin = d_cin; ca.g.coffs = (const uint64_t *)ctx->coffs.p; ca.g.clens = d_lens; ca.g.dout = d_out;
@@ -1492,15 +1498,7 @@ extern "C" int w3_decode_blocks_device(w3_ctx *ctx, const w3_model_spec *spec, c
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     if ((rc = stage_huff(ctx, s, ps))) return rc;
-    {   // the length table must not claim more than the caller's buffer holds: the kernels read cin + offset for clens[b] bytes
-        ENSURE(ctx, ctx->coffs, (size_t)nb * 8);
-        ENSURE(ctx, ctx->total, 8);
-        hipLaunchKernelGGL(k_scan_lens, dim3(1), dim3(1024), 0, s, d_block_lens, (uint64_t *)ctx->coffs.p, (uint64_t *)ctx->total.p, (uint32_t)nb);
-        uint64_t total = 0;
-        HIPCHK(ctx, hipMemcpyAsync(&total, ctx->total.p, 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipStreamSynchronize(s));
-        if (total > in_len) { ctx->err = "block length table claims " + std::to_string(total) + " compressed bytes, the buffer holds " + std::to_string(in_len); return W3_E_FORMAT; }
-    }
+    if ((rc = check_len_table(ctx, s, d_block_lens, (uint32_t)nb, in_len))) return rc;
     rc = ps.is_cm() ? cm_decode(ctx, s, ps, d_in, d_block_lens, (uint32_t)nb, block_size, orig_len, d_out)
                     : generic_decode(ctx, s, ps, d_in, d_block_lens, (uint32_t)nb, block_size, orig_len, d_out);
     if (rc) return rc;
@@ -1522,6 +1520,8 @@ extern "C" int w3_decode_blocks_device(w3_ctx *ctx, const w3_model_spec *spec, c
 // W3_OPT_HOST_CHUNK_BLOCKS overrides the piece size (tests: ragged pieces; measurements).
 // blocks per device call of a host-buffer entry point whose input exceeds what one device call handles (check_args): 2 GiB worth
 static size_t host_call_cap_blocks(size_t block_size) { return std::max<size_t>(1, ((size_t)1 << 31) / block_size); }
+// ... and of w3_decode_blocks, the ranges calls and AC over Huffman's host-buffer calls, which go through in runs of whole blocks, one device call each
+static size_t host_run_blocks(const w3_ctx *ctx, size_t block_size) { return ctx->host_chunk_blocks ? (size_t)ctx->host_chunk_blocks : host_call_cap_blocks(block_size); }
 
 static size_t host_chunk_blocks(const w3_ctx *ctx, const ParsedSpec &ps, size_t nb, size_t block_size, size_t n) {
     const size_t cap = host_call_cap_blocks(block_size);   // (a host buffer of any length goes through in pieces, as the reference streams any length: main.rs:97-109)
@@ -1530,6 +1530,16 @@ static size_t host_chunk_blocks(const w3_ctx *ctx, const ParsedSpec &ps, size_t 
     if (nb <= W3_FREE_RUN4_BLOCKS) return nb;
     const size_t pieces = (nb + W3_FREE_RUN4_BLOCKS - 1) / W3_FREE_RUN4_BLOCKS;
     return std::min((nb + pieces - 1) / pieces, cap);
+}
+
+// one more piece's timing into a call's sums (n_parts counts the pieces; path and n_wide are the last piece's)
+static void timing_add(w3_timing &sum, const w3_timing &t) {
+    sum.predict_ms += t.predict_ms; sum.coder_ms += t.coder_ms; sum.pack_ms += t.pack_ms; sum.generic_ms += t.generic_ms; sum.total_ms += t.total_ms;
+    sum.apm_ms += t.apm_ms; sum.slot_ms += t.slot_ms; sum.achash_ms += t.achash_ms; sum.small_ms += t.small_ms;
+    for (int w = 0; w < 4; w++) { sum.part_ms[w] += t.part_ms[w]; sum.rank_ms[w] += t.rank_ms[w]; }
+    sum.path = t.path; sum.n_wide = t.n_wide; sum.n_parts += 1;
+    sum.n_coder_launches += t.n_coder_launches; sum.coder_bytes += t.coder_bytes; sum.predict_bytes += t.predict_bytes;
+    sum.n_recoded_blocks += t.n_recoded_blocks; sum.n_slot_launches += t.n_slot_launches; sum.n_lds_faults += t.n_lds_faults;
 }
 
 extern "C" int w3_encode_blocks(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t n, size_t block_size, uint8_t *out,
@@ -1565,13 +1575,7 @@ extern "C" int w3_encode_blocks(w3_ctx *ctx, const w3_model_spec *spec, const ui
         const int r = host_wait_core(ctx, hjob, room ? out + off : nullptr, room ? out_cap - off : 0, &len);
         off += len;
         if (r != W3_OK && first_err == W3_OK) first_err = r;
-        const w3_timing &t = ctx->timing;
-        sum.predict_ms += t.predict_ms; sum.coder_ms += t.coder_ms; sum.pack_ms += t.pack_ms; sum.generic_ms += t.generic_ms; sum.total_ms += t.total_ms;
-        sum.apm_ms += t.apm_ms; sum.slot_ms += t.slot_ms; sum.achash_ms += t.achash_ms; sum.small_ms += t.small_ms;
-        for (int w = 0; w < 4; w++) { sum.part_ms[w] += t.part_ms[w]; sum.rank_ms[w] += t.rank_ms[w]; }
-        sum.path = t.path; sum.n_wide = t.n_wide; sum.n_parts += 1;
-        sum.n_coder_launches += t.n_coder_launches; sum.coder_bytes += t.coder_bytes; sum.predict_bytes += t.predict_bytes;
-        sum.n_recoded_blocks += t.n_recoded_blocks; sum.n_slot_launches += t.n_slot_launches; sum.n_lds_faults += t.n_lds_faults;
+        timing_add(sum, ctx->timing);
     };
     // Equal pieces.  (A half-size first and last piece — the call's first H2D + predict phase and its last predict + APM overlap nothing —
     // was measured: 97.6 against 96.9 ms at 1e9 B, 91.8 against 53.4 ms at 4e8 B; profiles/r4_host_path/.)
@@ -1594,6 +1598,31 @@ extern "C" int w3_encode_blocks(w3_ctx *ctx, const w3_model_spec *spec, const ui
     return W3_OK;
 }
 
+// The host-buffer decoders behind their argument checks (nblocks == ceil(orig_len / block_size) >= 1): any length, in runs of whole blocks.  Per run the
+// streams and their lengths go to the device, dev(d_in, in_len, d_lens, nblocks, orig_len, d_out) — the family's device entry point — decodes, the bytes come back.
+template <class Dev>
+static int host_decode_runs(w3_ctx *ctx, const uint8_t *in, size_t in_len, const uint32_t *block_lens, size_t nblocks, size_t block_size, uint64_t orig_len,
+                            uint8_t *out, Dev &&dev) {
+    const size_t run = host_run_blocks(ctx, block_size);
+    uint64_t coff = 0;
+    for (size_t b0 = 0; b0 < nblocks; b0 += run) {
+        const size_t b1 = std::min(nblocks, b0 + run);
+        uint64_t clen = 0;
+        for (size_t b = b0; b < b1; b++) clen += block_lens[b];
+        if (coff + clen > in_len) { ctx->err = "block length table claims " + std::to_string(coff + clen) + " compressed bytes, the buffer holds " + std::to_string(in_len); return W3_E_FORMAT; }
+        const uint64_t o0 = (uint64_t)b0 * block_size, o1 = std::min<uint64_t>(orig_len, (uint64_t)b1 * block_size);
+        ENSURE(ctx, ctx->io_in, std::max<size_t>((size_t)clen, 16));
+        ENSURE(ctx, ctx->io_out, (size_t)(o1 - o0));
+        ENSURE(ctx, ctx->lens, (b1 - b0) * 4);
+        HIPCHK(ctx, hipMemcpy(ctx->io_in.p, in + coff, (size_t)clen, hipMemcpyHostToDevice));
+        HIPCHK(ctx, hipMemcpy(ctx->lens.p, block_lens + b0, (b1 - b0) * 4, hipMemcpyHostToDevice));
+        if (const int rc = dev((const uint8_t *)ctx->io_in.p, (size_t)clen, (const uint32_t *)ctx->lens.p, b1 - b0, o1 - o0, (uint8_t *)ctx->io_out.p)) return rc;
+        HIPCHK(ctx, hipMemcpy(out + o0, ctx->io_out.p, (size_t)(o1 - o0), hipMemcpyDeviceToHost));
+        coff += clen;
+    }
+    return W3_OK;
+}
+
 extern "C" int w3_decode_blocks(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t in_len, const uint32_t *block_lens, size_t nblocks,
                                 size_t block_size, uint64_t orig_len, uint8_t *out) {
     int rc = check_args(ctx, (size_t)orig_len, block_size, false);
@@ -1601,41 +1630,11 @@ extern "C" int w3_decode_blocks(w3_ctx *ctx, const w3_model_spec *spec, const ui
     if ((rc = jobs_idle(ctx))) return rc;
     if (nblocks == 0 && orig_len == 0) return w3_spec_validate(spec);
     if (!in || !block_lens || !out) return W3_E_INVALID;
-    {   // any length: runs of blocks under the per-call limit, one after the other (W3_OPT_HOST_CHUNK_BLOCKS: the run length, for tests)
-        const size_t run = ctx->host_chunk_blocks ? (size_t)ctx->host_chunk_blocks : host_call_cap_blocks(block_size);
-        if (nblocks > run) {
-            if ((uint64_t)(nblocks - 1) * block_size >= orig_len) { ctx->err = "more blocks than orig_len / block_size"; return W3_E_INVALID; }
-            uint64_t coff = 0;
-            for (size_t b0 = 0; b0 < nblocks; b0 += run) {
-                const size_t b1 = std::min(nblocks, b0 + run);
-                uint64_t clen = 0;
-                for (size_t b = b0; b < b1; b++) clen += block_lens[b];
-                if (coff + clen > in_len) { ctx->err = "block length table claims more compressed bytes than the buffer holds"; return W3_E_FORMAT; }
-                const uint64_t o0 = (uint64_t)b0 * block_size, o1 = std::min<uint64_t>(orig_len, (uint64_t)b1 * block_size);
-                const uint32_t keep = ctx->host_chunk_blocks;
-                ctx->host_chunk_blocks = 0;   // (the pieces themselves are single calls)
-                rc = w3_decode_blocks(ctx, spec, in + coff, (size_t)clen, block_lens + b0, b1 - b0, block_size, o1 - o0, out + o0);
-                ctx->host_chunk_blocks = keep;
-                if (rc) return rc;
-                coff += clen;
-            }
-            return W3_OK;
-        }
-    }
+    if ((uint64_t)nblocks != (orig_len + block_size - 1) / block_size) { ctx->err = "nblocks does not match orig_len/block_size"; return W3_E_INVALID; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    uint64_t total = 0;
-    for (size_t b = 0; b < nblocks; b++) total += block_lens[b];
-    if (total > in_len) { ctx->err = "block length table claims " + std::to_string(total) + " compressed bytes, the buffer holds " + std::to_string(in_len); return W3_E_FORMAT; }
-    ENSURE(ctx, ctx->io_in, std::max<size_t>(total, 16));
-    ENSURE(ctx, ctx->io_out, (size_t)orig_len);
-    ENSURE(ctx, ctx->lens, nblocks * 4);
-    HIPCHK(ctx, hipMemcpy(ctx->io_in.p, in, total, hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemcpy(ctx->lens.p, block_lens, nblocks * 4, hipMemcpyHostToDevice));
-    rc = w3_decode_blocks_device(ctx, spec, (const uint8_t *)ctx->io_in.p, (size_t)total, (const uint32_t *)ctx->lens.p, nblocks, block_size, orig_len,
-                                 (uint8_t *)ctx->io_out.p, ctx->stream);
-    if (rc) return rc;
-    HIPCHK(ctx, hipMemcpy(out, ctx->io_out.p, (size_t)orig_len, hipMemcpyDeviceToHost));
-    return W3_OK;
+    return host_decode_runs(ctx, in, in_len, block_lens, nblocks, block_size, orig_len, out, [&](const uint8_t *d_in, size_t len, const uint32_t *d_lens, size_t nb, uint64_t olen, uint8_t *d_out) {
+        return w3_decode_blocks_device(ctx, spec, d_in, len, d_lens, nb, block_size, olen, d_out, ctx->stream);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -1700,15 +1699,7 @@ static int ranges_device(w3_ctx *ctx, const RangeDec &rd, const uint8_t *d_in, s
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     if (rd.ps && (rc = stage_huff(ctx, s, *rd.ps))) return rc;
-    {   // the length table must not claim more than the caller's buffer holds (as w3_decode_blocks_device)
-        ENSURE(ctx, ctx->coffs, nblocks * 8);
-        ENSURE(ctx, ctx->total, 8);
-        hipLaunchKernelGGL(k_scan_lens, dim3(1), dim3(1024), 0, s, d_block_lens, (uint64_t *)ctx->coffs.p, (uint64_t *)ctx->total.p, (uint32_t)nblocks);
-        uint64_t total = 0;
-        HIPCHK(ctx, hipMemcpyAsync(&total, ctx->total.p, 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipStreamSynchronize(s));
-        if (total > in_len) { ctx->err = "block length table claims " + std::to_string(total) + " compressed bytes, the buffer holds " + std::to_string(in_len); return W3_E_FORMAT; }
-    }
+    if ((rc = check_len_table(ctx, s, d_block_lens, (uint32_t)nblocks, in_len))) return rc;
     const std::vector<RangePiece> chunks = gather_chunks(p, W3_GATHER_PIECE_MAX);
     size_t coff = 0;
     const std::vector<uint8_t> meta = ranges_meta(p.jobs, chunks, coff);
@@ -1784,6 +1775,7 @@ static int ranges_host_one(w3_ctx *ctx, const RangeDec &rd, const uint8_t *in, c
     HIPCHK(ctx, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
     int rc = rd.ps ? stage_huff(ctx, s, *rd.ps) : W3_OK;
     if (rc) return rc;
+    if ((rc = scan_lens(ctx, s, (const uint32_t *)(d + lens_off), (uint32_t)nd))) return rc;   // (the compact table's total was checked on the host)
     rc = ranges_run(ctx, s, rd, d + str_off, (const uint32_t *)(d + lens_off), (uint32_t)nd, block_size, orig_len, (const DecodeJob *)d, (uint32_t)nd,
                     p.jobs[0].len, (const RangePiece *)(d + coff), (uint32_t)chunks.size(), p.staging, (uint8_t *)ctx->io_out.p);
     if (rc) return rc;
@@ -1807,7 +1799,7 @@ static int ranges_host(w3_ctx *ctx, const RangeDec &rd, const uint8_t *in, size_
     if (total > in_len) { ctx->err = "block length table claims " + std::to_string(total) + " compressed bytes, the buffer holds " + std::to_string(in_len); return W3_E_FORMAT; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     // blocks per device call: 2 GiB worth (W3_OPT_HOST_CHUNK_BLOCKS: fewer, for tests), and at most as many bytes of packed output
-    const uint64_t capb = ctx->host_chunk_blocks ? (uint64_t)ctx->host_chunk_blocks : (uint64_t)host_call_cap_blocks(block_size);
+    const uint64_t capb = host_run_blocks(ctx, block_size);
     if (p.blocks.size() <= capb && p.out_len <= capb * block_size)
         return ranges_host_one(ctx, rd, in, block_lens, nblocks, block_size, orig_len, ranges, n_ranges, out);
     // A larger selection: the ranges are cut into parts of at most capb / 2 blocks' worth (each touches at most capb / 2 + 1 blocks), and
@@ -2363,12 +2355,10 @@ extern "C" int w3_sweep_ordern_device(w3_ctx *ctx, const uint8_t *d_in, size_t n
         if (bits[c] < 1 || bits[c] > 32 || aligns[c] > 7 || aligns[c] > bits[c] || (int)bits[c] - (int)aligns[c] > 31) return W3_E_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    const uint64_t steps = (uint64_t)block_size * 8;
-    const uint64_t hash_slots = std::max<uint64_t>(1024, next_pow2(2 * steps)), hash_bytes = hash_slots * 8;
     std::vector<SweepCfg> cfg(ncfg);
     size_t free_b = 0, total_b = 0;
     HIPCHK(ctx, hipMemGetInfo(&free_b, &total_b));
-    const uint64_t budget = std::min<uint64_t>((uint64_t)(free_b + ctx->tables.cap) * 3 / 4, 200ull << 30);
+    const uint64_t budget = sweep_budget(free_b, ctx->tables.cap);
     ENSURE(ctx, ctx->sweep, ncfg * sizeof(SweepCfg) + (size_t)ncfg * nb * 4);
     SweepCfg *d_cfg = (SweepCfg *)ctx->sweep.p;
     uint32_t *d_bits = (uint32_t *)((uint8_t *)ctx->sweep.p + ncfg * sizeof(SweepCfg));
@@ -2381,13 +2371,12 @@ extern "C" int w3_sweep_ordern_device(w3_ctx *ctx, const uint8_t *d_in, size_t n
         uint64_t used = 0;
         size_t c1 = c0;
         for (; c1 < ncfg; c1++) {
-            const uint64_t direct = 4ull << bits[c1];
-            const bool hashed = direct > hash_bytes;
-            const uint64_t stride = hashed ? hash_bytes : std::max<uint64_t>(direct, 16);
+            const CounterTable t = counter_table(bits[c1], (uint64_t)block_size * 8);
+            const uint64_t stride = t.use_hash ? t.hash_bytes : std::max<uint64_t>(t.direct_bytes, 16);
             if (c1 > c0 && used + stride * nb > budget) break;
             SweepCfg &cf = cfg[c1];
-            cf.bits = bits[c1]; cf.align = aligns[c1]; cf.use_hash = hashed; cf.pad = 0;
-            cf.hash_mask = (uint32_t)(hash_slots - 1); cf.hist_mask = (uint32_t)((1ull << (bits[c1] - aligns[c1])) - 1ull);
+            cf.bits = bits[c1]; cf.align = aligns[c1]; cf.use_hash = t.use_hash; cf.pad = 0;
+            cf.hash_mask = (uint32_t)(t.slots - 1); cf.hist_mask = (uint32_t)((1ull << (bits[c1] - aligns[c1])) - 1ull);
             cf.base = used; cf.stride = stride;
             used += stride * nb;
         }
@@ -2494,62 +2483,48 @@ static int aoh_prepare(w3_ctx *ctx, hipStream_t s, const w3_huff_code *codes, si
     return W3_OK;
 }
 
-// Launch k_aoh<MODE> for configurations cfg[] (ctx_bits and code_idx set) x blocks [0, nb): per lane a direct Counter table of
-// 4 << ctx_bits bytes or, when that is smaller, the exact map with next_pow2(2 x steps[c]) slots of 8 bytes (steps[c]: the most
-// steps one lane of configuration c can take).  As many whole configurations per launch as fit the memory budget (the batching of
-// w3_sweep_ordern_device); a configuration whose tables alone exceed it goes in batches of blocks.  Tables are zero-filled per batch.
+// The sweep family's workspace in ctx->tables: plan(budget) lays a call out within `budget` bytes and returns the bytes it needs (0:
+// it does not fit; plan has set ctx->err).  One hipMalloc of that size can fail although hipMemGetInfo calls the memory free
+// (table_budget): the plan is then made again with half the budget.
+template <class Plan>
+static int ensure_sweep_tables(w3_ctx *ctx, Plan &&plan) {
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(ctx, hipMemGetInfo(&free_b, &total_b));
+    for (uint64_t budget = sweep_budget(free_b, ctx->tables.cap);; budget /= 2) {
+        const uint64_t need = plan(budget);
+        if (!need) return W3_E_NOMEM;
+        const int rc = ensure(ctx, ctx->tables, (size_t)need);
+        if (rc != W3_E_NOMEM || budget < (1ull << 20)) return rc;
+    }
+}
+
+// Launch k_aoh<MODE> for configurations cfg[] (ctx_bits and code_idx set) x blocks [0, nb): per lane a Counter table in the form of
+// counter_table(ctx_bits, steps[c]) (steps[c]: the most steps one lane of configuration c can take), in the launches of
+// plan_cfg_batches (w3_tables_plan.h) under the budget of ensure_sweep_tables.  Tables are zero-filled per batch.
 // max_lanes (the decoders' job calls under W3_OPT_AOH_BATCH_BLOCKS; 0 = no cap): most lanes per batch.
 template <int MODE>
 static int aoh_launch(w3_ctx *ctx, hipStream_t s, AohArgs a, AohPrep &P, std::vector<AohCfg> &cfg, const std::vector<uint64_t> &steps, uint32_t nb,
                       uint32_t max_lanes = 0) {
     const size_t ncfg = cfg.size();
+    std::vector<uint64_t> strides(ncfg), base(ncfg);
     for (size_t c = 0; c < ncfg; c++) {
-        const uint64_t slots = std::max<uint64_t>(1024, next_pow2(2 * steps[c])), hash_bytes = slots * 8, direct = 4ull << cfg[c].ctx_bits;
+        const CounterTable t = counter_table(cfg[c].ctx_bits, steps[c]);
         AohCfg &cf = cfg[c];
-        cf.use_hash = direct > hash_bytes; cf.pad = 0;
-        cf.hash_mask = (uint32_t)(slots - 1); cf.ctx_mask = (uint32_t)((1ull << cf.ctx_bits) - 1ull);
-        cf.stride = cf.use_hash ? hash_bytes : std::max<uint64_t>(direct, 16);
+        cf.use_hash = t.use_hash; cf.pad = 0;
+        cf.hash_mask = (uint32_t)(t.slots - 1); cf.ctx_mask = (uint32_t)((1ull << cf.ctx_bits) - 1ull);
+        cf.stride = strides[c] = t.use_hash ? t.hash_bytes : std::max<uint64_t>(t.direct_bytes, 16);
     }
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(ctx, hipMemGetInfo(&free_b, &total_b));
-    uint64_t budget = std::min<uint64_t>((uint64_t)(free_b + ctx->tables.cap) * 3 / 4, 200ull << 30);
-    struct Batch { size_t c0, c1; uint32_t first_block, n_lanes; uint64_t used; };
-    std::vector<Batch> plan;
-    for (;;) {
-        plan.clear();
+    std::vector<CfgBatch> plan;
+    const int rc = ensure_sweep_tables(ctx, [&](uint64_t budget) {
         uint64_t need = 0;
-        bool fits = true;
-        for (size_t c0 = 0; c0 < ncfg && fits;) {
-            if (cfg[c0].stride * nb <= budget && (!max_lanes || nb <= max_lanes)) {   // whole configurations
-                uint64_t used = 0;
-                size_t c1 = c0;
-                for (; c1 < ncfg && used + cfg[c1].stride * nb <= budget; c1++) { cfg[c1].base = used; used += cfg[c1].stride * nb; }
-                plan.push_back({c0, c1, 0u, nb, used});
-                need = std::max(need, used);
-                c0 = c1;
-            } else {                                                   // one configuration, batches of blocks
-                uint64_t lanes = budget / cfg[c0].stride;
-                if (max_lanes) lanes = std::min<uint64_t>(lanes, max_lanes);
-                if (lanes >= 64) lanes = lanes / 64 * 64;
-                if (lanes == 0) { fits = false; break; }
-                cfg[c0].base = 0;
-                for (uint32_t b0 = 0; b0 < nb; b0 += (uint32_t)lanes) {
-                    const uint32_t cnt = (uint32_t)std::min<uint64_t>(lanes, nb - b0);
-                    plan.push_back({c0, c0 + 1, b0, cnt, cfg[c0].stride * cnt});
-                    need = std::max(need, cfg[c0].stride * cnt);
-                }
-                c0++;
-            }
-        }
-        if (!fits) { ctx->err = "the Counter table of one lane does not fit the device budget"; return W3_E_NOMEM; }
-        const int rc = ensure(ctx, ctx->tables, (size_t)need);
-        if (rc == W3_OK) break;
-        if (rc != W3_E_NOMEM || budget < (1ull << 20)) return rc;
-        budget /= 2;   // (one hipMalloc of that size can fail although hipMemGetInfo calls the memory free: table_budget)
-    }
+        if (!plan_cfg_batches(strides.data(), ncfg, nb, budget, max_lanes, plan, base.data(), need)) { ctx->err = "the Counter table of one lane does not fit the device budget"; return (uint64_t)0; }
+        return need;
+    });
+    if (rc) return rc;
+    for (size_t c = 0; c < ncfg; c++) cfg[c].base = base[c];
     HIPCHK(ctx, hipMemcpy(P.d_cfg, cfg.data(), ncfg * sizeof(AohCfg), hipMemcpyHostToDevice));
     a.cfg = P.d_cfg; a.codes = P.d_codes; a.tables = (uint8_t *)ctx->tables.p; a.nblocks = nb;
-    for (const Batch &bt : plan) {
+    for (const CfgBatch &bt : plan) {
         HIPCHK(ctx, hipMemsetAsync(ctx->tables.p, 0, (size_t)bt.used, s));
         a.first_cfg = (uint32_t)bt.c0; a.first_block = bt.first_block; a.n_lanes = bt.n_lanes; a.waves_per_cfg = (bt.n_lanes + 63) / 64;
         hipLaunchKernelGGL(k_aoh<MODE>, dim3((unsigned)((bt.c1 - bt.c0) * a.waves_per_cfg)), dim3(64), 0, s, a);
@@ -2562,10 +2537,8 @@ static int aoh_launch(w3_ctx *ctx, hipStream_t s, AohArgs a, AohPrep &P, std::ve
 // k_predict_wave's form (twice as many slots as the call's longest block has steps, and ctx 0's own slot behind them).
 struct AohWaveTable { bool use_hash; uint64_t slots, stride; };
 static AohWaveTable aoh_wave_table(uint8_t ctx_bits, uint64_t max_l) {
-    const uint64_t slots = std::max<uint64_t>(1024, next_pow2(2 * max_l)), hash_bytes = 8 * slots + 16, direct = std::max<uint64_t>(4ull << ctx_bits, 16);
-    AohWaveTable t;
-    t.use_hash = direct > hash_bytes; t.slots = slots; t.stride = t.use_hash ? hash_bytes : direct;
-    return t;
+    const CounterTable c = counter_table(ctx_bits, max_l);
+    return AohWaveTable{c.use_hash, c.slots, c.use_hash ? c.hash_bytes + 16 : std::max<uint64_t>(c.direct_bytes, 16)};
 }
 
 // which form a call takes (W3_OPT_PATH; W3_PATH_AUTO by the measured rule of w3_aoh.h)
@@ -2576,7 +2549,7 @@ static bool aoh_takes_twophase(const w3_ctx *ctx, uint32_t nb, uint8_t ctx_bits,
 
 // The two-phase form (w3_aoh.h) of encode (STATS = false: into the stripes, as aoh_launch<AOH_ENCODE>) and of the counting sink, one
 // configuration: per batch of whole blocks (w3_aoh_plan.h) k_aoh_pack, k_aoh_predict, k_aoh_coder.  ONE allocation (ctx->tables) holds
-// the plan's offsets, the Counter tables of the resident wavefronts, P and the strings; the budget rule is aoh_launch's, a call whose
+// the plan's offsets, the Counter tables of the resident wavefronts, P and the strings; the budget is ensure_sweep_tables', a call whose
 // workspace exceeds it goes in batches (W3_OPT_AOH_BATCH_BLOCKS: the tests' cap on a batch).  With W3_OPT_TIMING the phases' times
 // are added to ctx->timing batch by batch.
 template <bool STATS>
@@ -2586,9 +2559,6 @@ static int aoh_twophase_run(w3_ctx *ctx, hipStream_t s, AohTwoArgs a, AohPrep &P
     HIPCHK(ctx, hipStreamSynchronize(s));
     const AohWaveTable tk = aoh_wave_table(ctx_bits, P.max_l[0]);
     auto up256 = [](uint64_t v) { return (v + 255) / 256 * 256; };
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(ctx, hipMemGetInfo(&free_b, &total_b));
-    uint64_t budget = std::min<uint64_t>((uint64_t)(free_b + ctx->tables.cap) * 3 / 4, 200ull << 30);
     const uint64_t meta = up256((uint64_t)nb * 16);
     uint64_t resident = 256 * 32;
     {
@@ -2600,22 +2570,20 @@ static int aoh_twophase_run(w3_ctx *ctx, hipStream_t s, AohTwoArgs a, AohPrep &P
     }
     AohPlan plan;
     uint64_t waves = 0, o_P = 0, o_str = 0;
-    for (;;) {
+    const int rc = ensure_sweep_tables(ctx, [&](uint64_t budget) -> uint64_t {
         // latency-bound: as many wavefronts as the chip holds of this kernel (more would queue behind them with tables of their own), their
         // tables within half the budget
         waves = std::min<uint64_t>(std::min<uint64_t>(nb, resident), budget / 2 / tk.stride);
-        if (waves == 0) { ctx->err = "the Counter table of one block (" + std::to_string(tk.stride) + " B) does not fit the device budget"; return W3_E_NOMEM; }
+        if (waves == 0) { ctx->err = "the Counter table of one block (" + std::to_string(tk.stride) + " B) does not fit the device budget"; return 0; }
         o_P = meta + up256(waves * tk.stride);
         if (o_P + 256 >= budget || !aoh_plan(L.data(), nb, budget - o_P - 256, ctx->aoh_batch_blocks, plan)) {
             ctx->err = "the bit string and probabilities of one block do not fit the device budget";
-            return W3_E_NOMEM;
+            return 0;
         }
         o_str = o_P + up256(2 * plan.max_p_steps);
-        const int rc = ensure(ctx, ctx->tables, (size_t)(o_str + plan.max_str_bytes));
-        if (rc == W3_OK) break;
-        if (rc != W3_E_NOMEM || budget < (1ull << 20)) return rc;
-        budget /= 2;   // (one hipMalloc of that size can fail although hipMemGetInfo calls the memory free: table_budget)
-    }
+        return o_str + plan.max_str_bytes;
+    });
+    if (rc) return rc;
     uint8_t *base = (uint8_t *)ctx->tables.p;
     HIPCHK(ctx, hipMemcpy(base, plan.str_off.data(), (size_t)nb * 8, hipMemcpyHostToDevice));
     HIPCHK(ctx, hipMemcpy(base + (size_t)nb * 8, plan.p_off.data(), (size_t)nb * 8, hipMemcpyHostToDevice));
@@ -2749,7 +2717,7 @@ extern "C" int w3_aoh_encode_blocks(w3_ctx *ctx, const w3_huff_code *code, uint8
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     memset(&ctx->timing, 0, sizeof ctx->timing);
-    const size_t run = host_call_cap_blocks(block_size);   // any length: device calls of at most 2 GiB of input, one after the other
+    const size_t run = host_run_blocks(ctx, block_size);   // any length: device calls of at most 2 GiB of input, one after the other
     JobRef J = jobref(ctx, 0);
     size_t off = 0;
     uint32_t parts = 0;
@@ -2785,24 +2753,16 @@ extern "C" int w3_aoh_encode_blocks(w3_ctx *ctx, const w3_huff_code *code, uint8
 }
 
 // k_aoh_decode_spec (w3_aoh_spec.h) over jobs [0, nl): a direct table of 4 << ctx_bits bytes per job, as many jobs per batch (a
-// multiple of 4: a wavefront takes four) as the memory budget of aoh_launch holds, W3_OPT_AOH_BATCH_BLOCKS caps a batch (tests);
+// multiple of 4: a wavefront takes four) as the budget of ensure_sweep_tables holds, W3_OPT_AOH_BATCH_BLOCKS caps a batch (tests);
 // the tables are zero-filled per batch on the stream.
 static int aoh_spec_launch(w3_ctx *ctx, hipStream_t s, AohSpecArgs a, uint8_t ctx_bits, uint32_t nl) {
     const uint64_t stride = std::max<uint64_t>(4ull << ctx_bits, 16);
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(ctx, hipMemGetInfo(&free_b, &total_b));
-    uint64_t budget = std::min<uint64_t>((uint64_t)(free_b + ctx->tables.cap) * 3 / 4, 200ull << 30);
     uint32_t per = 0;
-    for (;;) {
-        uint64_t lanes = std::min<uint64_t>(budget / stride, nl);
-        if (ctx->aoh_batch_blocks) lanes = std::min<uint64_t>(lanes, ctx->aoh_batch_blocks);
-        if (lanes >= 4) lanes = lanes / 4 * 4;
-        if (lanes == 0) { ctx->err = "the Counter table of one job does not fit the device budget"; return W3_E_NOMEM; }
-        const int rc = ensure(ctx, ctx->tables, (size_t)(lanes * stride));
-        if (rc == W3_OK) { per = (uint32_t)lanes; break; }
-        if (rc != W3_E_NOMEM || budget < (1ull << 20)) return rc;
-        budget /= 2;   // (as aoh_launch)
-    }
+    const int rc = ensure_sweep_tables(ctx, [&](uint64_t budget) {
+        if (!(per = (uint32_t)lanes_per_batch(budget, stride, nl, ctx->aoh_batch_blocks, 4))) ctx->err = "the Counter table of one job does not fit the device budget";
+        return per * stride;
+    });
+    if (rc) return rc;
     a.tables = (uint8_t *)ctx->tables.p; a.stride = stride; a.ctx_mask = (uint32_t)((1ull << ctx_bits) - 1ull);
     for (uint32_t first = 0; first < nl; first += per) {
         const uint32_t cnt = std::min(per, nl - first);
@@ -2827,15 +2787,11 @@ static bool aoh_full_take_spec(const w3_ctx *ctx, uint8_t ctx_bits) {
 // The decoders of the family on device-resident streams (d_lens[nb], validated by the caller): every block whole into d_out
 // (d_jobs == nullptr), or the n_jobs decode jobs of a ranges call (w3_ranges.h; the longest decodes max_job_len bytes) into d_out =
 // the staging buffer.  spec: k_aoh_decode_spec, else k_aoh<AOH_DECODE>.  Does not synchronise after the launches.
+// Precondition: ctx->coffs holds the exclusive scan of d_lens[nb], enqueued on s (scan_lens / check_len_table).
 static int aoh_decode_run(w3_ctx *ctx, hipStream_t s, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *d_cin, const uint32_t *d_lens, uint32_t nb,
                           size_t block_size, uint64_t orig_len, uint8_t *d_out, const DecodeJob *d_jobs, uint32_t n_jobs, uint32_t max_job_len, bool spec) {
     int rc;
     const unsigned max_len = w3aoh::max_len(code);
-    if (d_jobs) {   // the streams' offsets (the full decode's caller has scanned the table to validate it)
-        ENSURE(ctx, ctx->coffs, (size_t)nb * 8);
-        ENSURE(ctx, ctx->total, 8);
-        hipLaunchKernelGGL(k_scan_lens, dim3(1), dim3(1024), 0, s, d_lens, (uint64_t *)ctx->coffs.p, (uint64_t *)ctx->total.p, nb);
-    }
     AohPrep P;
     if ((rc = aoh_prepare(ctx, s, code, 1, 1, nb, nullptr, (size_t)orig_len, block_size, P))) return rc;
     const uint32_t nl = d_jobs ? n_jobs : nb;
@@ -2869,15 +2825,7 @@ extern "C" int w3_aoh_decode_blocks_device(w3_ctx *ctx, const w3_huff_code *code
     if (w3aoh::max_len(code) == 0) { ctx->err = "a table without symbols decodes nothing"; return W3_E_INVALID; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    {   // the length table must not claim more than the caller's buffer holds (w3_decode_blocks_device)
-        ENSURE(ctx, ctx->coffs, (size_t)nb * 8);
-        ENSURE(ctx, ctx->total, 8);
-        hipLaunchKernelGGL(k_scan_lens, dim3(1), dim3(1024), 0, s, d_block_lens, (uint64_t *)ctx->coffs.p, (uint64_t *)ctx->total.p, (uint32_t)nb);
-        uint64_t total = 0;
-        HIPCHK(ctx, hipMemcpyAsync(&total, ctx->total.p, 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipStreamSynchronize(s));
-        if (total > in_len) { ctx->err = "block length table claims " + std::to_string(total) + " compressed bytes, the buffer holds " + std::to_string(in_len); return W3_E_FORMAT; }
-    }
+    if ((rc = check_len_table(ctx, s, d_block_lens, (uint32_t)nb, in_len))) return rc;
     const bool spec = aoh_full_take_spec(ctx, ctx_bits);
     if ((rc = aoh_decode_run(ctx, s, code, ctx_bits, d_in, d_block_lens, (uint32_t)nb, block_size, orig_len, d_out, nullptr, 0, 0, spec))) return rc;
     HIPCHK(ctx, hipStreamSynchronize(s));
@@ -2931,26 +2879,9 @@ extern "C" int w3_aoh_decode_blocks(w3_ctx *ctx, const w3_huff_code *code, uint8
     if (nblocks == 0) return W3_OK;
     if (!in || !block_lens || !out) return W3_E_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t run = host_call_cap_blocks(block_size);
-    uint64_t coff = 0;
-    for (size_t b0 = 0; b0 < nblocks; b0 += run) {
-        const size_t b1 = std::min(nblocks, b0 + run);
-        uint64_t clen = 0;
-        for (size_t b = b0; b < b1; b++) clen += block_lens[b];
-        if (coff + clen > in_len) { ctx->err = "block length table claims more compressed bytes than the buffer holds"; return W3_E_FORMAT; }
-        const uint64_t o0 = (uint64_t)b0 * block_size, o1 = std::min<uint64_t>(orig_len, (uint64_t)b1 * block_size);
-        ENSURE(ctx, ctx->io_in, std::max<size_t>((size_t)clen, 16));
-        ENSURE(ctx, ctx->io_out, (size_t)(o1 - o0));
-        ENSURE(ctx, ctx->lens, (b1 - b0) * 4);
-        HIPCHK(ctx, hipMemcpy(ctx->io_in.p, in + coff, (size_t)clen, hipMemcpyHostToDevice));
-        HIPCHK(ctx, hipMemcpy(ctx->lens.p, block_lens + b0, (b1 - b0) * 4, hipMemcpyHostToDevice));
-        rc = w3_aoh_decode_blocks_device(ctx, code, ctx_bits, (const uint8_t *)ctx->io_in.p, (size_t)clen, (const uint32_t *)ctx->lens.p, b1 - b0, block_size,
-                                         o1 - o0, (uint8_t *)ctx->io_out.p, ctx->stream);
-        if (rc) return rc;
-        HIPCHK(ctx, hipMemcpy(out + o0, ctx->io_out.p, (size_t)(o1 - o0), hipMemcpyDeviceToHost));
-        coff += clen;
-    }
-    return W3_OK;
+    return host_decode_runs(ctx, in, in_len, block_lens, nblocks, block_size, orig_len, out, [&](const uint8_t *d_in, size_t len, const uint32_t *d_lens, size_t nb, uint64_t olen, uint8_t *d_out) {
+        return w3_aoh_decode_blocks_device(ctx, code, ctx_bits, d_in, len, d_lens, nb, block_size, olen, d_out, ctx->stream);
+    });
 }
 
 // the counting sink for configurations (codes[code_idx[c]], ctx_bits[c]) on a device-resident input: d_bits[ncfg][nb] (device).
@@ -3007,7 +2938,7 @@ extern "C" int w3_aoh_encode_stats(w3_ctx *ctx, const w3_huff_code *code, uint8_
     if (nb == 0) return W3_OK;
     if (!in || !block_bits) return W3_E_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t run = host_call_cap_blocks(block_size);
+    const size_t run = host_run_blocks(ctx, block_size);
     for (size_t b0 = 0; b0 < nb; b0 += run) {
         const size_t b1 = std::min(nb, b0 + run), lo = b0 * block_size, hi = std::min(n, b1 * block_size);
         ENSURE(ctx, ctx->io_in, hi - lo);
@@ -3092,7 +3023,7 @@ extern "C" int w3_export_counters(w3_ctx *ctx, const w3_model_spec *spec, const 
     ga.tables = (uint8_t *)ctx->tables.p; ga.lane_stride = entries * 4;
     ga.in = (const uint8_t *)ctx->io_in.p; ga.stripes = (uint8_t *)ctx->stripes.p; ga.stripe_cap = cap;
     ga.out_len = (uint32_t *)ctx->lens.p; ga.overflow = (uint32_t *)ctx->flag.p; ga.out_bits = nullptr;
-    hipLaunchKernelGGL((k_generic_nl<false, 1>), dim3(1), dim3(64), 0, s, ga);
+    launch_generic<false>(ga, 1, s);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(counters, ctx->tables.p, entries * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
