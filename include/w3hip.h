@@ -34,8 +34,10 @@ enum {
     W3_E_HIP         = -3,  /* HIP runtime error (w3_last_error has the text)         */
     W3_E_UNSUPPORTED = -4,  /* valid spec the device path does not implement          */
     W3_E_NOMEM       = -5,  /* device workspace does not fit                          */
-    W3_E_FORMAT      = -6   /* bad container magic (main.rs:123-124 assert_eq!) or a block length table that
+    W3_E_FORMAT      = -6,  /* bad container magic (main.rs:123-124 assert_eq!) or a block length table that
                                claims more compressed bytes than the input buffer holds */
+    W3_E_CORRUPT     = -7   /* a decoded block does not match its CRC-32 (the *_checked calls and w3_crc32_verify_device);
+                               w3_last_error names the first bad block and the count */
 };
 
 /* ---- model spec ----------------------------------------------------------
@@ -162,7 +164,8 @@ enum {
                            count of a forgotten shape starts again at the context's count of calls).  A fault that hits each block independently with
                            probability q is missed with probability (1 - q)^S, S = the sample size.  A full in-round check needs a second returning LDS atomic per add (measured
                            +4.1 % of the step for the atomics alone, and no LDS left for its shadow tables) and was not built.  Full coverage = decode the output (w3_decode_blocks_device shares no kernel with the
-                           predict phase; bench.py does that for every block of its last step).  0 = off */
+                           predict phase; bench.py does that for every block of its last step).  A stored CRC table (w3_crc32_blocks_device on the input, beside the
+                           encode) makes that check possible without the input: w3_crc32_verify_device on the decoded output.  0 = off */
     W3_OPT_TUNE = 11,   /* scheduling / layout experiments (bit mask; output is identical whatever is set).  Bits 0 – 14: the submit / wait
                            pipeline's arrangements and the slot replay's shapes (HISTORY.md 2.8); 15: rank kernels with eight wavefronts per half
                            CU; 16: host-buffer copies on two streams of their own instead of the context's stream; 17 / 18: k_decode_spec with
@@ -170,8 +173,8 @@ enum {
                            where the instance specialised for all-raw-history models would run */
     W3_OPT_FAULT_BLOCK = 10, /* test hook, with W3_OPT_VARIANT bit 32: the one block the injected fault hits (-1 = every block, default) */
     W3_OPT_HOST_CHUNK_BLOCKS = 12, /* w3_encode_blocks: blocks per pipelined piece of a host-buffer call (0 = default: equal pieces of at most
-                           4,096 blocks; tests use small values to get ragged pieces).  w3_decode_blocks, w3_decode_ranges and the w3_aoh_*
-                           host-buffer calls: blocks per device call (0 = default: 2 GiB worth) */
+                           4,096 blocks; tests use small values to get ragged pieces).  w3_decode_blocks, w3_decode_ranges, w3_crc32_blocks, their
+                           *_checked forms and the w3_aoh_* host-buffer calls: blocks per device call (0 = default: 2 GiB worth) */
     W3_OPT_FAULT_KERNELS = 13, /* test hook, with W3_OPT_VARIANT bit 32: bit mask (1 .. 7) of the kernels whose returning LDS adds the injected
                            fault mis-orders — 1 = k_predict_small's rounds (default), 2 = k_rank_sorted's rounds, 4 = k_partition8's
                            cursor adds (two records of one bin swap their slots in the tile: a permutation, never another index) */
@@ -254,6 +257,51 @@ int w3_decode_ranges(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, 
 int w3_decode_ranges_device(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *d_in, size_t in_len, const uint32_t *d_block_lens,
                             size_t nblocks, size_t block_size, uint64_t orig_len, const w3_range *ranges /* host */, size_t n_ranges,
                             uint8_t *d_out, size_t out_cap, size_t *out_len, void *stream);
+
+/* ---- integrity: CRC-32 per block, and decodes that verify it -----------------------------------------------------------------
+ * The reference has no counterpart (one stream per file, no checksum: main.rs:89-144); build-defined on the block container.  An
+ * arithmetic decoder cannot notice a damaged stream: it is told how many bytes to produce and produces them.  A table of one CRC-32
+ * per ORIGINAL block, made beside the encode and stored with the container (tools/w3cli.cpp: versions 3 and 4), lets a decode tell.
+ * The checksum is CRC-32/ISO-HDLC, the one zlib.crc32 computes: reflected polynomial 0xEDB88320, init and xor-out 0xFFFFFFFF,
+ * crc("123456789") = 0xCBF43926, crc("") = 0.  Computed on the device (csrc/w3_crc.h: a wavefront per 64 KiB slice of a block, 1 KiB
+ * per load instruction, the slices of a larger block folded; blocks may start at any byte address).
+ *   w3_crc32_blocks          host buffers, any n: crc[ceil(n / block_size)]; the input goes up in runs of whole blocks
+ *                            (W3_OPT_HOST_CHUNK_BLOCKS: blocks per run, as for w3_decode_blocks).
+ *   w3_crc32_blocks_device   device buffers; the per-call limit on n of the device calls applies.  A device caller runs it on d_in on
+ *                            the stream of its encode: encode needs no entry point of its own.
+ *   w3_crc32_verify_device   compares the blocks of d_data with d_crc[ceil(n / block_size)] (device memory): W3_OK, or W3_E_CORRUPT with
+ *                            *bad_block = the lowest block that differs and *n_bad = how many do (UINT64_MAX and 0 when none; either
+ *                            pointer may be NULL).  The full device decode with a check is w3_decode_blocks_device (or the w3_aoh_ one),
+ *                            then this call on its output.
+ *   *_checked                the host full decodes and the four ranges calls with a w3_check behind their arguments.  chk->crc is HOST
+ *                            memory, one entry per block of the CONTAINER (nblocks), also for the ranges calls.  chk == NULL or
+ *                            chk->crc == NULL: W3_E_INVALID.  Every other argument error, W3_E_NOSPACE, W3_E_FORMAT and W3_E_INVALID for a
+ *                            job in flight come first and are the unchecked call's, word for word.  On W3_E_CORRUPT the outputs are written as
+ *                            the unchecked call writes them and *out_len is set; the caller discards them.  The full decodes verify every
+ *                            block of every run before its bytes leave the device.  The ranges calls decode every block a range touches
+ *                            WHOLE (a CRC cannot vouch for a prefix) and verify it in the staging buffer before the gather: W3_OK means
+ *                            every touched block is intact to its end, not only the requested bytes; a damaged block that no range touches
+ *                            is not seen.  A selection that w3_decode_ranges cuts into several device calls may count a bad block twice.
+ *                            The verify adds kernels on the call's stream and 16 bytes to a readback the call waits for anyway.
+ * Folding the CRC into the pinned w3_encode_host_submit pipeline (host input would cross PCIe once) is not built: DESIGN.md 7. */
+typedef struct w3_check {
+    const uint32_t *crc;   /* HOST memory, one entry per block of the container (nblocks) */
+    uint64_t bad_block;    /* out: lowest block whose decoded bytes do not match, UINT64_MAX if none */
+    uint64_t n_bad;        /* out: how many of the verified blocks do not match */
+} w3_check;
+int w3_crc32_blocks(w3_ctx *ctx, const uint8_t *in, size_t n, size_t block_size, uint32_t *crc);
+int w3_crc32_blocks_device(w3_ctx *ctx, const uint8_t *d_in, size_t n, size_t block_size, uint32_t *d_crc, void *stream);
+int w3_crc32_verify_device(w3_ctx *ctx, const uint8_t *d_data, size_t n, size_t block_size, const uint32_t *d_crc,
+                           uint64_t *bad_block, uint64_t *n_bad, void *stream);
+int w3_decode_blocks_checked(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t in_len, const uint32_t *block_lens,
+                             size_t nblocks, size_t block_size, uint64_t orig_len, uint8_t *out, w3_check *chk);
+int w3_decode_ranges_checked(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t in_len, const uint32_t *block_lens,
+                             size_t nblocks, size_t block_size, uint64_t orig_len, const w3_range *ranges, size_t n_ranges,
+                             uint8_t *out, size_t out_cap, size_t *out_len, w3_check *chk);
+int w3_decode_ranges_device_checked(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *d_in, size_t in_len, const uint32_t *d_block_lens,
+                                    size_t nblocks, size_t block_size, uint64_t orig_len, const w3_range *ranges /* host */, size_t n_ranges,
+                                    uint8_t *d_out, size_t out_cap, size_t *out_len, void *stream, w3_check *chk);
+/* (the w3_aoh_*_checked twins are declared with their family, below) */
 
 /* ---- the same encode, asynchronous: two to four calls in flight per context --------------------------
  * The reference codes one bit at a time on one thread (main.rs:103-109); here a call is three phases with different
@@ -451,6 +499,16 @@ int w3_aoh_decode_ranges_device(w3_ctx *ctx, const w3_huff_code *code, uint8_t c
                                 const w3_range *ranges /* host */, size_t n_ranges, uint8_t *d_out, size_t out_cap, size_t *out_len,
                                 void *stream);
 int w3_aoh_decode_spec_covers(uint8_t ctx_bits);   /* host only: 1 where the sixteen-lane decoder takes the call */
+/* The checked forms (w3_check, above: "integrity"): the same calls with the CRC table of the original blocks behind their arguments. */
+int w3_aoh_decode_blocks_checked(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *in, size_t in_len,
+                                 const uint32_t *block_lens, size_t nblocks, size_t block_size, uint64_t orig_len, uint8_t *out, w3_check *chk);
+int w3_aoh_decode_ranges_checked(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *in, size_t in_len,
+                                 const uint32_t *block_lens, size_t nblocks, size_t block_size, uint64_t orig_len,
+                                 const w3_range *ranges, size_t n_ranges, uint8_t *out, size_t out_cap, size_t *out_len, w3_check *chk);
+int w3_aoh_decode_ranges_device_checked(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *d_in, size_t in_len,
+                                        const uint32_t *d_block_lens, size_t nblocks, size_t block_size, uint64_t orig_len,
+                                        const w3_range *ranges /* host */, size_t n_ranges, uint8_t *d_out, size_t out_cap, size_t *out_len,
+                                        void *stream, w3_check *chk);
 int w3_aoh_encode_stats(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *in, size_t n, size_t block_size,
                         uint32_t *block_bits);
 int w3_aoh_encode_stats_device(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *d_in, size_t n, size_t block_size,

@@ -10,6 +10,10 @@
 // W3_MODEL=aoh or aoh:<hsize>,<ctx> codes with the reference's best-ratio research driver, AC over Huffman
 // (bin/ac-over-huffman/main.rs:69-89), into version 2 of the block container (below).
 //
+// W3_CHECK=1 (compress): the container also holds one CRC-32 per original block (w3_crc32_blocks) and a CRC-32 of its own header —
+// version 3 (version 1 + checks) or 4 (version 2 + checks); `w3 d` and `w3 r` on such a file verify every block they decode
+// (the *_checked calls) and write nothing when one is damaged.  Without it the files are versions 1 and 2, byte for byte as before.
+//
 // `w3 r <file.bin> <offset> <length>` (build-defined: random access, which the block container makes possible and the reference's one
 // stream per file does not) writes bytes [offset, offset + length) of the original to <stem>.part, decoding only the blocks they touch.
 #include <sys/stat.h>
@@ -26,6 +30,8 @@
 #include <vector>
 
 #include "../include/w3hip.h"
+#define W3_HD static inline
+#include "../weath3rb0i_amd/csrc/w3_crc.h"   // crc32_ref: the header's CRC is the host's business
 
 static const uint32_t kBlock = 65536;
 
@@ -113,7 +119,8 @@ static int die(w3_ctx *ctx, int rc, const char *what) {
 }
 
 static bool write_block_container(const std::string &out, size_t orig, const std::vector<uint32_t> &lens, size_t nb, const uint8_t *body, size_t blen,
-                                  const w3_huff_code *code = nullptr, uint8_t ctx_bits = 0);
+                                  const w3_huff_code *code = nullptr, uint8_t ctx_bits = 0, const uint32_t *crc = nullptr);
+static bool want_check() { const char *e = getenv("W3_CHECK"); return e && atoi(e) > 0; }
 // bytes per w3_encode_blocks / w3_decode_blocks call: a multiple of the block size below the library's 4 GiB limit
 static size_t call_max() {
     size_t m = (size_t)1 << 31;
@@ -138,6 +145,14 @@ static int compress(w3_ctx *ctx, const std::string &in, const std::string &out) 
     std::vector<uint32_t> lens(nb ? nb : 1);
     size_t blen = 0;
     int rc;
+    // W3_CHECK=1: one CRC-32 per original block, from the device (versions 3 / 4 of the container)
+    std::vector<uint32_t> crc;
+    if (want_check()) {
+        crc.resize(nb ? nb : 1);
+        rc = w3_crc32_blocks(ctx, data.data(), data.size(), kBlock, crc.data());
+        if (rc) return die(ctx, rc, "w3_crc32_blocks");
+    }
+    const uint32_t *crcp = crc.empty() ? nullptr : crc.data();
     const AohModel am = aoh_model();
     if (am.on) {   // version 2 of the container: the table is the file's (histogram of the whole file, main.rs:74), the library takes any length
         w3_huff_code code;
@@ -154,7 +169,7 @@ static int compress(w3_ctx *ctx, const std::string &in, const std::string &out) 
         rc = w3_aoh_encode_blocks(ctx, &code, (uint8_t)am.ctx, data.data(), data.size(), kBlock, body.data(), body.size(), &blen, lens.data());
         if (rc == W3_E_NOSPACE) { body.resize(blen); rc = w3_aoh_encode_blocks(ctx, &code, (uint8_t)am.ctx, data.data(), data.size(), kBlock, body.data(), body.size(), &blen, lens.data()); }
         if (rc) return die(ctx, rc, "w3_aoh_encode_blocks");
-        return write_block_container(out, data.size(), lens, nb, body.data(), blen, &code, (uint8_t)am.ctx) ? 0 : 1;
+        return write_block_container(out, data.size(), lens, nb, body.data(), blen, &code, (uint8_t)am.ctx, crcp) ? 0 : 1;
     }
     // W3_SHARDS=k: the blocks as k contiguous ranges on k contexts, one per GPU (round robin over the devices present) —
     // w3_encode_blocks_sharded, the single-process form of BASELINE configs[3]; same container bytes as one context
@@ -186,15 +201,17 @@ static int compress(w3_ctx *ctx, const std::string &in, const std::string &out) 
             if (data.empty()) break;
         }
     }
-    return write_block_container(out, data.size(), lens, nb, body.data(), blen) ? 0 : 1;
+    return write_block_container(out, data.size(), lens, nb, body.data(), blen, nullptr, 0, crcp) ? 0 : 1;
 }
 
 // "w3bk" + version + u64 length + u32 block size + u32 block count (version 1); version 2 (AC over Huffman) then holds ctx_bits (1 byte)
-// and the code table (256 codes of 2 bytes, then 256 lengths); then, in both, the length table and the streams.
+// and the code table (256 codes of 2 bytes, then 256 lengths); then, in both, the length table and the streams.  Versions 3 and 4 are 1
+// and 2 with checks: behind the length table the CRC-32 of every original block (u32 each), then the CRC-32 of every file byte before
+// that point (magic through CRC table), then the streams.
 static const size_t kHeader = 21, kAohExtra = 1 + 512 + 256;
 static bool write_block_container(const std::string &out, size_t orig, const std::vector<uint32_t> &lens, size_t nb, const uint8_t *body, size_t blen,
-                                  const w3_huff_code *code, uint8_t ctx_bits) {
-    std::vector<uint8_t> file = {'w', '3', 'b', 'k', (uint8_t)(code ? 2 : 1)};
+                                  const w3_huff_code *code, uint8_t ctx_bits, const uint32_t *crc) {
+    std::vector<uint8_t> file = {'w', '3', 'b', 'k', (uint8_t)((code ? 2 : 1) + (crc ? 2 : 0))};
     put_be(file, orig, 8); put_be(file, kBlock, 4); put_be(file, nb, 4);
     if (code) {
         file.push_back(ctx_bits);
@@ -202,6 +219,10 @@ static bool write_block_container(const std::string &out, size_t orig, const std
         for (int s = 0; s < 256; s++) file.push_back(code->len[s]);
     }
     for (size_t b = 0; b < nb; b++) put_be(file, lens[b], 4);
+    if (crc) {
+        for (size_t b = 0; b < nb; b++) put_be(file, crc[b], 4);
+        put_be(file, w3::crc32_ref(file.data(), file.size()), 4);
+    }
     file.insert(file.end(), body, body + blen);
     return write_file(out, file.data(), file.size());
 }
@@ -266,27 +287,46 @@ static int decompress(w3_ctx *ctx, const std::string &in, const std::string &out
         if (rc) return die(ctx, rc, "w3_decompress_stream");
         return write_file(out, o.data(), len) ? 0 : 1;
     }
-    if (data.size() < kHeader || memcmp(data.data(), "w3bk", 4) || (data[4] != 1 && data[4] != 2)) {  // main.rs:123-124 asserts the magic
+    if (data.size() < kHeader || memcmp(data.data(), "w3bk", 4) || data[4] < 1 || data[4] > 4) {  // main.rs:123-124 asserts the magic
         fprintf(stderr, "Magic numbers don't match up - file wasn't compressed with (this version of) w3cli!\n");
         return 1;
     }
-    const bool v2 = data[4] == 2;
+    const bool v2 = data[4] == 2 || data[4] == 4, checked = data[4] >= 3;
     const size_t hdr = kHeader + (v2 ? kAohExtra : 0);
     uint64_t orig = get_be(data.data() + 5, 8);
     uint32_t bs = (uint32_t)get_be(data.data() + 13, 4), nb = (uint32_t)get_be(data.data() + 17, 4);
-    if (data.size() < hdr + 4ull * nb) return die(ctx, W3_E_FORMAT, "length table");
+    const size_t tables = hdr + (checked ? 8ull * nb + 4 : 4ull * nb);   // where the streams begin
+    if (data.size() < tables) return die(ctx, W3_E_FORMAT, "length table");
+    std::vector<uint32_t> crc;
+    if (checked) {   // the header's own CRC first, on the host: nothing of a damaged header reaches the device
+        if ((uint32_t)get_be(data.data() + tables - 4, 4) != w3::crc32_ref(data.data(), tables - 4)) {
+            fprintf(stderr, "%s: the header (sizes, length table, CRC table) does not match its CRC-32: the file is damaged\n", in.c_str());
+            return 1;
+        }
+        crc.resize(nb ? nb : 1);
+        for (uint32_t b = 0; b < nb; b++) crc[b] = (uint32_t)get_be(data.data() + hdr + 4ull * nb + 4ull * b, 4);
+    }
     std::vector<uint32_t> lens(nb ? nb : 1);
     uint64_t total = 0;
     for (uint32_t b = 0; b < nb; b++) { lens[b] = (uint32_t)get_be(data.data() + hdr + 4ull * b, 4); total += lens[b]; }
-    if (data.size() < hdr + 4ull * nb + total) return die(ctx, W3_E_FORMAT, "streams");
+    if (data.size() < tables + total) return die(ctx, W3_E_FORMAT, "streams");
     std::vector<uint8_t> o((size_t)orig + 1);
-    const uint8_t *body = data.data() + hdr + 4ull * nb;
+    const uint8_t *body = data.data() + tables;
+    uint64_t first_bad = ~0ull, n_bad = 0;   // (checked files: over all the calls)
+    auto corrupt = [&]() {
+        fprintf(stderr, "%s: block %llu does not match its CRC-32 (%llu damaged block%s): nothing written\n", in.c_str(), (unsigned long long)first_bad,
+                (unsigned long long)n_bad, n_bad == 1 ? "" : "s");
+        return 1;
+    };
     if (v2) {   // AC over Huffman: the model is in the file (ctx_bits and the table), whatever W3_MODEL says
         w3_huff_code code;
         const uint8_t ctx_bits = data[kHeader];
         for (int s = 0; s < 256; s++) code.code[s] = (uint16_t)get_be(data.data() + kHeader + 1 + 2 * s, 2);
         memcpy(code.len, data.data() + kHeader + 1 + 512, 256);
-        int rc = w3_aoh_decode_blocks(ctx, &code, ctx_bits, body, (size_t)total, lens.data(), nb, bs, orig, o.data());
+        w3_check chk{crc.data(), 0, 0};
+        int rc = checked ? w3_aoh_decode_blocks_checked(ctx, &code, ctx_bits, body, (size_t)total, lens.data(), nb, bs, orig, o.data(), &chk)
+                         : w3_aoh_decode_blocks(ctx, &code, ctx_bits, body, (size_t)total, lens.data(), nb, bs, orig, o.data());
+        if (rc == W3_E_CORRUPT) { first_bad = chk.bad_block; n_bad = chk.n_bad; return corrupt(); }
         if (rc) return die(ctx, rc, "w3_aoh_decode_blocks");
         return write_file(out, o.data(), (size_t)orig) ? 0 : 1;
     }
@@ -297,11 +337,15 @@ static int decompress(w3_ctx *ctx, const std::string &in, const std::string &out
         uint64_t clen = 0;
         for (size_t b = b0; b < b1; b++) clen += lens[b];
         const uint64_t o0 = (uint64_t)b0 * bs, o1 = std::min<uint64_t>(orig, (uint64_t)b1 * bs);
-        int rc = w3_decode_blocks(ctx, &spec, body + coff, (size_t)clen, lens.data() + b0, b1 - b0, bs, (size_t)(o1 > o0 ? o1 - o0 : 0), o.data() + o0);
+        w3_check chk{checked ? crc.data() + b0 : nullptr, 0, 0};
+        int rc = checked ? w3_decode_blocks_checked(ctx, &spec, body + coff, (size_t)clen, lens.data() + b0, b1 - b0, bs, (size_t)(o1 > o0 ? o1 - o0 : 0), o.data() + o0, &chk)
+                         : w3_decode_blocks(ctx, &spec, body + coff, (size_t)clen, lens.data() + b0, b1 - b0, bs, (size_t)(o1 > o0 ? o1 - o0 : 0), o.data() + o0);
+        if (rc == W3_E_CORRUPT) { first_bad = std::min<uint64_t>(first_bad, b0 + chk.bad_block); n_bad += chk.n_bad; rc = W3_OK; }   // (every piece is verified)
         if (rc) return die(ctx, rc, "w3_decode_blocks");
         coff += clen;
         if (nb == 0) break;
     }
+    if (n_bad) return corrupt();
     return write_file(out, o.data(), (size_t)orig) ? 0 : 1;
 }
 
@@ -313,25 +357,46 @@ static int extract(w3_ctx *ctx, const std::string &in, uint64_t offset, uint64_t
         fprintf(stderr, "%s is a w30i single-stream file: random access needs the block container (w3bk) — decompress it whole with `w3 d`\n", in.c_str());
         return 1;
     }
+    if (data.size() >= kHeader && !memcmp(data.data(), "w3bk", 4) && data[4] == 4) {
+        fprintf(stderr, "%s is a version-4 block container (AC over Huffman, with checks): random access is not implemented for these streams — decompress it whole with `w3 d`\n", in.c_str());
+        return 1;
+    }
     if (data.size() >= kHeader && !memcmp(data.data(), "w3bk", 4) && data[4] == 2) {
         fprintf(stderr, "%s is a version-2 block container (AC over Huffman): random access is not implemented for these streams — decompress it whole with `w3 d`\n", in.c_str());
         return 1;
     }
-    if (data.size() < 21 || memcmp(data.data(), "w3bk", 4) || data[4] != 1) {
+    if (data.size() < 21 || memcmp(data.data(), "w3bk", 4) || (data[4] != 1 && data[4] != 3)) {
         fprintf(stderr, "Magic numbers don't match up - file wasn't compressed with (this version of) w3cli!\n");
         return 1;
     }
+    const bool checked = data[4] == 3;
     const uint64_t orig = get_be(data.data() + 5, 8);
     const uint32_t bs = (uint32_t)get_be(data.data() + 13, 4), nb = (uint32_t)get_be(data.data() + 17, 4);
-    if (data.size() < 21 + 4ull * nb) return die(ctx, W3_E_FORMAT, "length table");
-    std::vector<uint32_t> lens(nb ? nb : 1);
+    const size_t tables = 21 + (checked ? 8ull * nb + 4 : 4ull * nb);
+    if (data.size() < tables) return die(ctx, W3_E_FORMAT, "length table");
+    std::vector<uint32_t> lens(nb ? nb : 1), crc(nb ? nb : 1);
     for (uint32_t b = 0; b < nb; b++) lens[b] = (uint32_t)get_be(data.data() + 21 + 4ull * b, 4);
+    if (checked) {
+        if ((uint32_t)get_be(data.data() + tables - 4, 4) != w3::crc32_ref(data.data(), tables - 4)) {
+            fprintf(stderr, "%s: the header (sizes, length table, CRC table) does not match its CRC-32: the file is damaged\n", in.c_str());
+            return 1;
+        }
+        for (uint32_t b = 0; b < nb; b++) crc[b] = (uint32_t)get_be(data.data() + 21 + 4ull * nb + 4ull * b, 4);
+    }
     const w3_model_spec spec = init_model();
     const w3_range r{offset, length};
     std::vector<uint8_t> o((size_t)length + 1);
     size_t len = 0;
-    const int rc = w3_decode_ranges(ctx, &spec, data.data() + 21 + 4ull * nb, data.size() - 21 - 4ull * nb, lens.data(), nb, bs, orig, &r, 1,
-                                    o.data(), (size_t)length, &len);
+    w3_check chk{crc.data(), 0, 0};
+    const int rc = checked ? w3_decode_ranges_checked(ctx, &spec, data.data() + tables, data.size() - tables, lens.data(), nb, bs, orig, &r, 1,
+                                                      o.data(), (size_t)length, &len, &chk)
+                           : w3_decode_ranges(ctx, &spec, data.data() + tables, data.size() - tables, lens.data(), nb, bs, orig, &r, 1,
+                                              o.data(), (size_t)length, &len);
+    if (rc == W3_E_CORRUPT) {
+        fprintf(stderr, "%s: block %llu does not match its CRC-32 (%llu damaged block%s among those the range touches): nothing written\n", in.c_str(),
+                (unsigned long long)chk.bad_block, (unsigned long long)chk.n_bad, chk.n_bad == 1 ? "" : "s");
+        return 1;
+    }
     if (rc) return die(ctx, rc, "w3_decode_ranges");
     return write_file(out, o.data(), len) ? 0 : 1;
 }
@@ -400,7 +465,7 @@ int main(int argc, char **argv) {
         if (d) closedir(d);
         const char *cont = getenv("W3_CONTAINER"), *sh = getenv("W3_SHARDS"), *serial = getenv("W3_SERIAL");
         const bool block_container = !(cont && !strcmp(cont, "w30i")) && !(sh && atoi(sh) > 1);
-        if (action == 'c' && block_container && !serial && !aoh_model().on) ret = compress_dir_in_flight(ctx, files);   // files in flight (W3_SERIAL=1: one after the other)
+        if (action == 'c' && block_container && !serial && !want_check() && !aoh_model().on) ret = compress_dir_in_flight(ctx, files);   // files in flight (W3_SERIAL=1 or W3_CHECK=1: one after the other)
         else for (const std::string &p : files) ret |= run(ctx, p, action);
     } else {
         ret = run(ctx, argv[2], action);

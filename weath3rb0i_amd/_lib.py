@@ -14,6 +14,7 @@ W3_MAX_APM = 4
 W3_HIST_NONE, W3_HIST_RAW, W3_HIST_AC, W3_HIST_HUFF = 0, 1, 2, 3
 W3_MAX_HUFF = 4
 W3_OK, W3_E_INVALID, W3_E_NOSPACE, W3_E_HIP, W3_E_UNSUPPORTED, W3_E_NOMEM, W3_E_FORMAT = 0, -1, -2, -3, -4, -5, -6
+W3_E_CORRUPT = -7
 W3_OPT_PATH, W3_OPT_TIMING, W3_OPT_CODER, W3_OPT_ACC_LIMIT, W3_OPT_DEBUG_STAMPS, W3_OPT_VARIANT, W3_OPT_SLOT_BUDGET_MB, W3_OPT_VERIFY, W3_OPT_FAULT_BLOCK, W3_OPT_TUNE, W3_OPT_HOST_CHUNK_BLOCKS, W3_OPT_FAULT_KERNELS, W3_OPT_AOH_BATCH_BLOCKS = 1, 2, 3, 4, 5, 7, 8, 9, 10, 11, 12, 13, 14
 W3_VAR_NO_LDS_ATOMICS, W3_VAR_PARTITION4, W3_VAR_NO_CHAINED_PARTITION, W3_VAR_CM_UNSTAGED, W3_VAR_NO_SIDE_STREAM, W3_VAR_INJECT_LDS_FAULT = 1, 2, 4, 8, 16, 32
 W3_VAR_HALF_CU, W3_VAR_FULL_CU = 64, 128
@@ -44,6 +45,11 @@ class Range(C.Structure):
     _fields_ = [("offset", C.c_uint64), ("len", C.c_uint64)]
 
 
+class Check(C.Structure):
+    """w3_check: the CRC-32 table of the original blocks (host memory) and what a checked decode found"""
+    _fields_ = [("crc", C.c_void_p), ("bad_block", C.c_uint64), ("n_bad", C.c_uint64)]
+
+
 class Timing(C.Structure):
     _fields_ = [("predict_ms", C.c_float), ("coder_ms", C.c_float), ("pack_ms", C.c_float), ("generic_ms", C.c_float),
                 ("total_ms", C.c_float), ("path", C.c_uint32), ("n_coder_launches", C.c_uint32),
@@ -65,6 +71,8 @@ EXPORTS = [
     "w3_huff_code_table", "w3_aoh_max_compressed_size", "w3_aoh_encode_blocks", "w3_aoh_encode_blocks_device", "w3_aoh_decode_blocks",
     "w3_aoh_decode_blocks_device", "w3_aoh_encode_stats", "w3_aoh_encode_stats_device", "w3_sweep_ac_over_huffman",
     "w3_sweep_ac_over_huffman_device", "w3_aoh_decode_ranges", "w3_aoh_decode_ranges_device", "w3_aoh_decode_spec_covers",
+    "w3_crc32_blocks", "w3_crc32_blocks_device", "w3_crc32_verify_device", "w3_decode_blocks_checked", "w3_decode_ranges_checked",
+    "w3_decode_ranges_device_checked", "w3_aoh_decode_blocks_checked", "w3_aoh_decode_ranges_checked", "w3_aoh_decode_ranges_device_checked",
 ]
 
 _lib = None
@@ -152,6 +160,16 @@ def load():
     lib.w3_aoh_encode_stats_device.argtypes = [vp, hc, u8, vp, sz, sz, vp, vp]
     lib.w3_sweep_ac_over_huffman.argtypes = [vp, vp, sz, sz, vp, sz, vp, vp, sz, vp]
     lib.w3_sweep_ac_over_huffman_device.argtypes = [vp, vp, sz, sz, vp, sz, vp, vp, sz, vp]
+    ck = C.POINTER(Check)
+    lib.w3_crc32_blocks.argtypes = [vp, vp, sz, sz, vp]
+    lib.w3_crc32_blocks_device.argtypes = [vp, vp, sz, sz, vp, vp]
+    lib.w3_crc32_verify_device.argtypes = [vp, vp, sz, sz, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]
+    lib.w3_decode_blocks_checked.argtypes = lib.w3_decode_blocks.argtypes + [ck]
+    lib.w3_decode_ranges_checked.argtypes = lib.w3_decode_ranges.argtypes + [ck]
+    lib.w3_decode_ranges_device_checked.argtypes = lib.w3_decode_ranges_device.argtypes + [ck]
+    lib.w3_aoh_decode_blocks_checked.argtypes = lib.w3_aoh_decode_blocks.argtypes + [ck]
+    lib.w3_aoh_decode_ranges_checked.argtypes = lib.w3_aoh_decode_ranges.argtypes + [ck]
+    lib.w3_aoh_decode_ranges_device_checked.argtypes = lib.w3_aoh_decode_ranges_device.argtypes + [ck]
     lib.w3_rccl_library.argtypes = [C.c_char_p]
     lib.w3_rccl_status.argtypes = [C.c_char_p, sz]
     _lib = lib

@@ -59,9 +59,19 @@ class Context:
 
     __del__ = close
 
-    def _chk(self, rc):
+    def _chk(self, rc, check=None):
         if rc:
+            if rc == L.W3_E_CORRUPT and check is not None:
+                raise W3Error(rc, self.lib.w3_last_error(self.h).decode(), bad_block=int(check.bad_block), n_bad=int(check.n_bad))
             raise W3Error(rc, self.lib.w3_last_error(self.h).decode())
+
+    @staticmethod
+    def _check(crc):
+        """(w3_check over the table, the array that owns it) for a *_checked call"""
+        t = np.ascontiguousarray(crc, dtype=np.uint32)
+        if t.size == 0:
+            t = np.zeros(1, dtype=np.uint32)
+        return L.Check(t.ctypes.data, 2**64 - 1, 0), t
 
     def set_path(self, path):
         self._chk(self.lib.w3_ctx_set_option(self.h, L.W3_OPT_PATH, {"auto": 0, "generic": 1, "twophase": 2}[path]))
@@ -172,28 +182,65 @@ class Context:
         spec = None if model is None else (model.spec() if isinstance(model, Model) else model)
         return int(self.lib.w3_encode_host_max_in_flight(C.byref(spec) if spec is not None else None, int(n), int(block_size)))
 
-    def decode_blocks(self, model, comp, block_lens, block_size, orig_len):
+    def decode_blocks(self, model, comp, block_lens, block_size, orig_len, crc=None):
+        """crc: the CRC-32 table of the original blocks (crc32_blocks) — w3_decode_blocks_checked: every decoded block is verified on the
+        device, W3Error(W3_E_CORRUPT) with .bad_block and .n_bad when one differs.  None: w3_decode_blocks."""
         spec = model.spec() if isinstance(model, Model) else model
         a = _u8(comp)
         lens = np.ascontiguousarray(block_lens, dtype=np.uint32)
         out = np.empty(max(orig_len, 1), dtype=np.uint8)
-        rc = self.lib.w3_decode_blocks(self.h, C.byref(spec), a.ctypes.data_as(C.c_void_p), len(a), lens.ctypes.data_as(C.c_void_p),
-                                       len(lens), block_size, orig_len, out.ctypes.data_as(C.c_void_p))
-        self._chk(rc)
+        args = (self.h, C.byref(spec), a.ctypes.data_as(C.c_void_p), len(a), lens.ctypes.data_as(C.c_void_p),
+                len(lens), block_size, orig_len, out.ctypes.data_as(C.c_void_p))
+        if crc is None:
+            self._chk(self.lib.w3_decode_blocks(*args))
+        else:
+            ck, _keep = self._check(crc)
+            self._chk(self.lib.w3_decode_blocks_checked(*args, C.byref(ck)), ck)
         return out[:orig_len]
 
-    def decode_ranges(self, model, comp, block_lens, block_size, orig_len, ranges):
+    # ---- CRC-32 per block (include/w3hip.h "integrity") ----
+    def crc32_blocks(self, data, block_size):
+        """w3_crc32_blocks: zlib's CRC-32 of every block of `data`, computed on the device.  -> np.uint32[nblocks]"""
+        a = _u8(data)
+        nb = (len(a) + block_size - 1) // block_size if block_size else 0
+        crc = np.zeros(max(nb, 1), dtype=np.uint32)
+        self._chk(self.lib.w3_crc32_blocks(self.h, a.ctypes.data_as(C.c_void_p), len(a), block_size, crc.ctypes.data_as(C.c_void_p)))
+        return crc[:nb]
+
+    def crc32_blocks_device(self, d_in, block_size, d_crc, stream=None):
+        """w3_crc32_blocks_device: d_in torch.uint8 CUDA tensor, d_crc int32/uint32[nblocks] CUDA tensor receiving the table."""
+        st = C.c_void_p(stream) if stream else None
+        self._chk(self.lib.w3_crc32_blocks_device(self.h, C.c_void_p(d_in.data_ptr()), d_in.numel(), block_size, C.c_void_p(d_crc.data_ptr()), st))
+
+    def crc32_verify_device(self, d_data, block_size, d_crc, stream=None):
+        """w3_crc32_verify_device: the blocks of d_data against the table d_crc (both CUDA tensors).  -> (bad_block, n_bad) = (2**64 - 1, 0)
+        when every block matches; W3Error(W3_E_CORRUPT) with .bad_block (the lowest block that differs) and .n_bad otherwise."""
+        st = C.c_void_p(stream) if stream else None
+        bad, nbad = C.c_uint64(2**64 - 1), C.c_uint64(0)
+        rc = self.lib.w3_crc32_verify_device(self.h, C.c_void_p(d_data.data_ptr()), d_data.numel(), block_size, C.c_void_p(d_crc.data_ptr()),
+                                             C.byref(bad), C.byref(nbad), st)
+        if rc == L.W3_E_CORRUPT:
+            raise W3Error(rc, self.lib.w3_last_error(self.h).decode(), bad_block=bad.value, n_bad=nbad.value)
+        self._chk(rc)
+        return bad.value, nbad.value
+
+    def decode_ranges(self, model, comp, block_lens, block_size, orig_len, ranges, crc=None):
         """Random access (w3_decode_ranges): the bytes of `ranges` — (offset, len) pairs or an (n, 2) integer array — of the original data,
-        concatenated in request order, decoding only the blocks they touch.  -> np.uint8[sum of the lengths]"""
+        concatenated in request order, decoding only the blocks they touch.  -> np.uint8[sum of the lengths]
+        crc: the CRC-32 table of ALL the container's blocks — w3_decode_ranges_checked: every touched block is decoded whole and verified."""
         spec = model.spec() if isinstance(model, Model) else model
         a = _u8(comp)
         lens = np.ascontiguousarray(block_lens, dtype=np.uint32)
         rs, n, total = _ranges(ranges)
         out = np.empty(max(total, 1), dtype=np.uint8)
         olen = C.c_size_t()
-        rc = self.lib.w3_decode_ranges(self.h, C.byref(spec), a.ctypes.data_as(C.c_void_p), len(a), lens.ctypes.data_as(C.c_void_p), len(lens),
-                                       block_size, orig_len, rs, n, out.ctypes.data_as(C.c_void_p), total, C.byref(olen))
-        self._chk(rc)
+        args = (self.h, C.byref(spec), a.ctypes.data_as(C.c_void_p), len(a), lens.ctypes.data_as(C.c_void_p), len(lens),
+                block_size, orig_len, rs, n, out.ctypes.data_as(C.c_void_p), total, C.byref(olen))
+        if crc is None:
+            self._chk(self.lib.w3_decode_ranges(*args))
+        else:
+            ck, _keep = self._check(crc)
+            self._chk(self.lib.w3_decode_ranges_checked(*args, C.byref(ck)), ck)
         return out[: olen.value]
 
     def encode_stats(self, model, data, block_size):
@@ -256,26 +303,36 @@ class Context:
             self._chk(rc)
             return out[: olen.value], lens[:nb]
 
-    def aoh_decode_blocks(self, code, ctx_bits, comp, block_lens, block_size, orig_len):
+    def aoh_decode_blocks(self, code, ctx_bits, comp, block_lens, block_size, orig_len, crc=None):
+        """crc: as decode_blocks (w3_aoh_decode_blocks_checked)"""
         a = _u8(comp)
         lens = np.ascontiguousarray(block_lens, dtype=np.uint32)
         out = np.empty(max(orig_len, 1), dtype=np.uint8)
-        rc = self.lib.w3_aoh_decode_blocks(self.h, C.byref(code.table), ctx_bits, a.ctypes.data_as(C.c_void_p), len(a), lens.ctypes.data_as(C.c_void_p),
-                                           len(lens), block_size, orig_len, out.ctypes.data_as(C.c_void_p))
-        self._chk(rc)
+        args = (self.h, C.byref(code.table), ctx_bits, a.ctypes.data_as(C.c_void_p), len(a), lens.ctypes.data_as(C.c_void_p),
+                len(lens), block_size, orig_len, out.ctypes.data_as(C.c_void_p))
+        if crc is None:
+            self._chk(self.lib.w3_aoh_decode_blocks(*args))
+        else:
+            ck, _keep = self._check(crc)
+            self._chk(self.lib.w3_aoh_decode_blocks_checked(*args, C.byref(ck)), ck)
         return out[:orig_len]
 
-    def aoh_decode_ranges(self, code, ctx_bits, comp, block_lens, block_size, orig_len, ranges):
+    def aoh_decode_ranges(self, code, ctx_bits, comp, block_lens, block_size, orig_len, ranges, crc=None):
         """Random access on AC-over-Huffman streams (w3_aoh_decode_ranges): the bytes of `ranges` — (offset, len) pairs or an (n, 2) integer
-        array — of the original data, concatenated in request order, decoding only the blocks they touch.  -> np.uint8[sum of the lengths]"""
+        array — of the original data, concatenated in request order, decoding only the blocks they touch.  -> np.uint8[sum of the lengths]
+        crc: as decode_ranges (w3_aoh_decode_ranges_checked)"""
         a = _u8(comp)
         lens = np.ascontiguousarray(block_lens, dtype=np.uint32)
         rs, n, total = _ranges(ranges)
         out = np.empty(max(total, 1), dtype=np.uint8)
         olen = C.c_size_t()
-        rc = self.lib.w3_aoh_decode_ranges(self.h, C.byref(code.table), ctx_bits, a.ctypes.data_as(C.c_void_p), len(a), lens.ctypes.data_as(C.c_void_p),
-                                           len(lens), block_size, orig_len, rs, n, out.ctypes.data_as(C.c_void_p), total, C.byref(olen))
-        self._chk(rc)
+        args = (self.h, C.byref(code.table), ctx_bits, a.ctypes.data_as(C.c_void_p), len(a), lens.ctypes.data_as(C.c_void_p),
+                len(lens), block_size, orig_len, rs, n, out.ctypes.data_as(C.c_void_p), total, C.byref(olen))
+        if crc is None:
+            self._chk(self.lib.w3_aoh_decode_ranges(*args))
+        else:
+            ck, _keep = self._check(crc)
+            self._chk(self.lib.w3_aoh_decode_ranges_checked(*args, C.byref(ck)), ck)
         return out[: olen.value]
 
     def aoh_decode_spec_covers(self, ctx_bits):
@@ -396,17 +453,21 @@ class Context:
                                               d_lens.numel(), block_size, orig_len, C.c_void_p(d_out.data_ptr()), st)
         self._chk(rc)
 
-    def decode_ranges_device(self, model, d_comp, d_lens, block_size, orig_len, ranges, d_out, stream=None):
+    def decode_ranges_device(self, model, d_comp, d_lens, block_size, orig_len, ranges, d_out, stream=None, crc=None):
         """w3_decode_ranges_device: the bytes of `ranges` ((offset, len) pairs or an (n, 2) integer array, host side) of the original data,
-        concatenated in request order into the torch.uint8 CUDA tensor d_out.  -> bytes written"""
+        concatenated in request order into the torch.uint8 CUDA tensor d_out.  -> bytes written
+        crc: the CRC-32 table of all the container's blocks, HOST side (w3_decode_ranges_device_checked)"""
         spec = model.spec() if isinstance(model, Model) else model
         st = C.c_void_p(stream) if stream else None
         rs, n, _ = _ranges(ranges)
         olen = C.c_size_t()
-        rc = self.lib.w3_decode_ranges_device(self.h, C.byref(spec), C.c_void_p(d_comp.data_ptr()), d_comp.numel(), C.c_void_p(d_lens.data_ptr()),
-                                              d_lens.numel(), block_size, orig_len, rs, n, C.c_void_p(d_out.data_ptr()), d_out.numel(),
-                                              C.byref(olen), st)
-        self._chk(rc)
+        args = (self.h, C.byref(spec), C.c_void_p(d_comp.data_ptr()), d_comp.numel(), C.c_void_p(d_lens.data_ptr()),
+                d_lens.numel(), block_size, orig_len, rs, n, C.c_void_p(d_out.data_ptr()), d_out.numel(), C.byref(olen), st)
+        if crc is None:
+            self._chk(self.lib.w3_decode_ranges_device(*args))
+        else:
+            ck, _keep = self._check(crc)
+            self._chk(self.lib.w3_decode_ranges_device_checked(*args, C.byref(ck)), ck)
         return olen.value
 
 
@@ -423,16 +484,20 @@ class Context:
                                                        C.c_void_p(d_lens.data_ptr()), d_lens.numel(), block_size, orig_len,
                                                        C.c_void_p(d_out.data_ptr()), st))
 
-    def aoh_decode_ranges_device(self, code, ctx_bits, d_comp, d_lens, block_size, orig_len, ranges, d_out, stream=None):
+    def aoh_decode_ranges_device(self, code, ctx_bits, d_comp, d_lens, block_size, orig_len, ranges, d_out, stream=None, crc=None):
         """w3_aoh_decode_ranges_device: the bytes of `ranges` (host side, as aoh_decode_ranges) concatenated in request order into the
-        torch.uint8 CUDA tensor d_out.  -> bytes written"""
+        torch.uint8 CUDA tensor d_out.  -> bytes written.  crc: as decode_ranges_device (w3_aoh_decode_ranges_device_checked)"""
         st = C.c_void_p(stream) if stream else None
         rs, n, _ = _ranges(ranges)
         olen = C.c_size_t()
-        rc = self.lib.w3_aoh_decode_ranges_device(self.h, C.byref(code.table), ctx_bits, C.c_void_p(d_comp.data_ptr()), d_comp.numel(),
-                                                  C.c_void_p(d_lens.data_ptr()), d_lens.numel(), block_size, orig_len, rs, n,
-                                                  C.c_void_p(d_out.data_ptr()), d_out.numel(), C.byref(olen), st)
-        self._chk(rc)
+        args = (self.h, C.byref(code.table), ctx_bits, C.c_void_p(d_comp.data_ptr()), d_comp.numel(),
+                C.c_void_p(d_lens.data_ptr()), d_lens.numel(), block_size, orig_len, rs, n,
+                C.c_void_p(d_out.data_ptr()), d_out.numel(), C.byref(olen), st)
+        if crc is None:
+            self._chk(self.lib.w3_aoh_decode_ranges_device(*args))
+        else:
+            ck, _keep = self._check(crc)
+            self._chk(self.lib.w3_aoh_decode_ranges_device_checked(*args, C.byref(ck)), ck)
         return olen.value
 
     def aoh_encode_stats_device(self, code, ctx_bits, d_in, block_size, d_bits, stream=None):

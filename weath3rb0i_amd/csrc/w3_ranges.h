@@ -102,6 +102,29 @@ inline int plan_ranges(uint64_t orig_len, uint64_t block_size, uint64_t nblocks,
     return W3_OK;
 }
 
+// The plan of a CHECKED ranges call (the *_checked entry points): a CRC vouches for a whole block, never for a prefix, so every touched
+// block is decoded to its end (the short last block: to orig_len).  blen, bdst, staging and jobs are recomputed, and every piece keeps its
+// offset inside its first block; blocks, out_len and the pieces' dst and len stay as plan_ranges left them.  A range that runs through
+// several blocks is still one contiguous stretch of the staging buffer: every block before the input's last one is block_size long.
+inline void widen_to_whole_blocks(RangePlan &p, uint64_t orig_len, uint64_t block_size) {
+    const size_t nd = p.blocks.size();
+    const std::vector<uint64_t> old_dst(p.bdst);
+    p.staging = 0;
+    for (size_t k = 0; k < nd; k++) {
+        const uint64_t start = (uint64_t)p.blocks[k] * block_size;
+        p.blen[k] = (uint32_t)std::min(block_size, orig_len - start);
+        p.bdst[k] = p.staging;
+        p.staging += p.blen[k];
+    }
+    for (size_t k = 0; k < nd; k++) p.jobs[k] = RangeJob{p.blocks[k], p.blen[k], p.bdst[k]};
+    std::stable_sort(p.jobs.begin(), p.jobs.end(), [](const RangeJob &a, const RangeJob &b) { return a.len > b.len; });   // (ties keep block order)
+    for (auto &pc : p.pieces) {
+        if (!pc.len) continue;
+        const size_t k = (size_t)(std::upper_bound(old_dst.begin(), old_dst.end(), pc.src) - old_dst.begin()) - 1;   // (the block the piece starts in)
+        pc.src = p.bdst[k] + (pc.src - old_dst[k]);
+    }
+}
+
 // the host-buffer variant's jobs: blk = the stream's index in the compact length table (the order of p.blocks)
 inline std::vector<RangeJob> compact_jobs(const RangePlan &p) {
     std::vector<RangeJob> out(p.jobs);

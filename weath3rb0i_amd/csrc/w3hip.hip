@@ -27,6 +27,7 @@
 #include "w3_aoh.h"
 #include "w3_aoh_spec.h"
 #include "w3_rccl.h"
+#include "w3_crc.h"
 
 using namespace w3;
 
@@ -106,6 +107,10 @@ struct w3_ctx {
     // host variant the compact length table and the selected streams behind them), and the host variant's pinned host copy of those
     DevBuf rg_stage, rg_meta;
     void *h_rg = nullptr; size_t h_rg_cap = 0;
+    // CRC-32 per block (w3_crc.h): [0, 16) the verify's result {lowest mismatching segment, mismatches}, from byte 256 on the slices' CRCs;
+    // crc_tab: a table on its way to or from a host caller; crc_res: where the result lands on the host
+    DevBuf crc_ws, crc_tab;
+    uint64_t crc_res[2] = {~0ull, 0};
     TwoPhaseWs tp;
     // the second job of the submit / wait pipeline
     struct JobWs { TwoPhaseWs tp; DevBuf stripes, flag, bits, offs, huff; hipEvent_t ev[W3_NEV]{}; } jx[W3_MAX_JOBS - 1];
@@ -198,6 +203,7 @@ extern "C" const char *w3_strerror(int code) {
     case W3_E_UNSUPPORTED: return "model spec not implemented on the device";
     case W3_E_NOMEM: return "device workspace does not fit";
     case W3_E_FORMAT: return "bad container magic";
+    case W3_E_CORRUPT: return "decoded block does not match its CRC-32";
     default: return "unknown error";
     }
 }
@@ -249,7 +255,7 @@ extern "C" void w3_ctx_destroy(w3_ctx *ctx) {
     (void)hipDeviceSynchronize();
     DevBuf *bufs[] = {&ctx->tables, &ctx->stripes, &ctx->lens, &ctx->offs, &ctx->total, &ctx->flag,
                       &ctx->io_in, &ctx->io_out, &ctx->coffs, &ctx->misc, &ctx->cm_luts, &ctx->achash_luts, &ctx->huff, &ctx->bits, &ctx->sweep, &ctx->aoh,
-                      &ctx->rg_stage, &ctx->rg_meta};
+                      &ctx->rg_stage, &ctx->rg_meta, &ctx->crc_ws, &ctx->crc_tab};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (ctx->h_rg) (void)hipHostFree(ctx->h_rg);
@@ -1506,6 +1512,102 @@ extern "C" int w3_decode_blocks_device(w3_ctx *ctx, const w3_model_spec *spec, c
     return W3_OK;
 }
 
+
+// ---------------------------------------------------------------------------
+// CRC-32 per block (w3_crc.h)
+// ---------------------------------------------------------------------------
+static_assert(sizeof(CrcSeg) == 16, "w3_crc.h segment layout");
+#define W3_CRC_WS_SLICES 256u   // byte offset of the slices' CRCs in ctx->crc_ws (the result words sit in front of them)
+
+// Enqueue the CRCs of nseg segments of d_base on s: uniform blocks of block_size over n bytes (d_segs == nullptr), or the explicit list
+// d_segs (none longer than max_len).  d_out != nullptr: d_out[k] = segment k's CRC.  check: every CRC is compared with d_want[k]
+// (implicit form) or d_segs[k].want, and the result words ctx->crc_ws[0 .. 16) = {lowest mismatching segment or ~0, mismatches} are
+// written (crc_fetch brings them to ctx->crc_res).  Does not synchronise.
+static int crc_enqueue(w3_ctx *ctx, hipStream_t s, const uint8_t *d_base, uint64_t n, uint32_t block_size, const CrcSeg *d_segs, uint64_t nseg,
+                       uint32_t max_len, uint32_t *d_out, const uint32_t *d_want, bool check) {
+    if (nseg == 0 && !check) return W3_OK;
+    const uint32_t spb = std::max(1u, crc_slices_of(max_len));
+    const uint64_t nsl = nseg * spb;
+    const bool direct = spb == 1 && !check && d_out;   // one slice per segment and nothing to compare: the slices' CRCs are the answer
+    ENSURE(ctx, ctx->crc_ws, W3_CRC_WS_SLICES + (direct ? 0 : (size_t)nsl * 4));
+    uint8_t *ws = (uint8_t *)ctx->crc_ws.p;
+    if (check) {
+        HIPCHK(ctx, hipMemsetAsync(ws, 0xFF, 8, s));
+        HIPCHK(ctx, hipMemsetAsync(ws + 8, 0, 8, s));
+    }
+    if (nseg == 0) return W3_OK;
+    uint32_t *d_slices = direct ? d_out : (uint32_t *)(ws + W3_CRC_WS_SLICES);
+    hipLaunchKernelGGL(k_crc32_slices, dim3((uint32_t)std::min<uint64_t>((nsl + 3) / 4, 2048)), dim3(256), 0, s, d_base, n, block_size, d_segs, nseg, spb,
+                       d_slices);
+    HIPCHK(ctx, hipGetLastError());
+    if (direct) return W3_OK;
+    hipLaunchKernelGGL(k_crc32_fold, dim3((uint32_t)std::min<uint64_t>((nseg + 255) / 256, 1024)), dim3(256), 0, s, n, block_size, d_segs, nseg, spb,
+                       (const uint32_t *)d_slices, d_out, d_want, check ? 1 : 0, (unsigned long long *)ws);
+    HIPCHK(ctx, hipGetLastError());
+    return W3_OK;
+}
+// the verify's 16 result bytes, on their way to ctx->crc_res behind the kernels (valid once s has been synchronised)
+static int crc_fetch(w3_ctx *ctx, hipStream_t s) {
+    HIPCHK(ctx, hipMemcpyAsync(ctx->crc_res, ctx->crc_ws.p, 16, hipMemcpyDeviceToHost, s));
+    return W3_OK;
+}
+
+// What a checked call reports (include/w3hip.h): the lowest bad block and the count, accumulated over the device calls it is made of.
+struct CrcReport {
+    uint64_t bad = ~0ull, n_bad = 0;
+    void add(uint64_t block, uint64_t count) { if (count) { bad = std::min(bad, block); n_bad += count; } }
+    int finish(w3_ctx *ctx, w3_check *chk) const {
+        chk->bad_block = bad; chk->n_bad = n_bad;
+        if (!n_bad) return W3_OK;
+        ctx->err = "block " + std::to_string(bad) + " does not match its CRC-32 (" + std::to_string(n_bad) + " of the verified blocks do not)";
+        return W3_E_CORRUPT;
+    }
+};
+// a checked call's w3_check argument: W3_E_INVALID without a table; the outputs start as "nothing found"
+static int check_arg(w3_ctx *ctx, w3_check *chk) {
+    if (!chk || !chk->crc) { if (ctx) ctx->err = "a checked call needs a w3_check with its CRC table"; return W3_E_INVALID; }
+    chk->bad_block = ~0ull; chk->n_bad = 0;
+    return W3_OK;
+}
+
+extern "C" int w3_crc32_blocks_device(w3_ctx *ctx, const uint8_t *d_in, size_t n, size_t block_size, uint32_t *d_crc, void *stream) {
+    int rc = check_args(ctx, n, block_size);
+    if (rc) return rc;
+    if ((rc = jobs_idle(ctx))) return rc;   // (the slices' workspace is the context's)
+    if (n == 0) return W3_OK;
+    if (!d_in || !d_crc) return W3_E_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    const uint64_t nb = (n + block_size - 1) / block_size;
+    if ((rc = crc_enqueue(ctx, s, d_in, n, (uint32_t)block_size, nullptr, nb, (uint32_t)std::min<uint64_t>(block_size, n), d_crc, nullptr, false))) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return W3_OK;
+}
+
+extern "C" int w3_crc32_verify_device(w3_ctx *ctx, const uint8_t *d_data, size_t n, size_t block_size, const uint32_t *d_crc, uint64_t *bad_block,
+                                      uint64_t *n_bad, void *stream) {
+    int rc = check_args(ctx, n, block_size);
+    if (rc) return rc;
+    if ((rc = jobs_idle(ctx))) return rc;
+    if (bad_block) *bad_block = ~0ull;
+    if (n_bad) *n_bad = 0;
+    if (n == 0) return W3_OK;
+    if (!d_data || !d_crc) return W3_E_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    const uint64_t nb = (n + block_size - 1) / block_size;
+    if ((rc = crc_enqueue(ctx, s, d_data, n, (uint32_t)block_size, nullptr, nb, (uint32_t)std::min<uint64_t>(block_size, n), nullptr, d_crc, true))) return rc;
+    if ((rc = crc_fetch(ctx, s))) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    CrcReport rep;
+    rep.add(ctx->crc_res[0], ctx->crc_res[1]);
+    w3_check out{d_crc, 0, 0};
+    rc = rep.finish(ctx, &out);
+    if (bad_block) *bad_block = out.bad_block;
+    if (n_bad) *n_bad = out.n_bad;
+    return rc;
+}
+
 // ---------------------------------------------------------------------------
 // host-buffer entry points
 // ---------------------------------------------------------------------------
@@ -1600,11 +1702,14 @@ extern "C" int w3_encode_blocks(w3_ctx *ctx, const w3_model_spec *spec, const ui
 
 // The host-buffer decoders behind their argument checks (nblocks == ceil(orig_len / block_size) >= 1): any length, in runs of whole blocks.  Per run the
 // streams and their lengths go to the device, dev(d_in, in_len, d_lens, nblocks, orig_len, d_out) — the family's device entry point — decodes, the bytes come back.
+// chk != nullptr (the *_checked calls): after each run's decode the run's part of chk->crc goes up and the decoded bytes are verified on the
+// device before they travel; every run is decoded and verified, and the report covers all of them.
 template <class Dev>
 static int host_decode_runs(w3_ctx *ctx, const uint8_t *in, size_t in_len, const uint32_t *block_lens, size_t nblocks, size_t block_size, uint64_t orig_len,
-                            uint8_t *out, Dev &&dev) {
+                            uint8_t *out, Dev &&dev, w3_check *chk = nullptr) {
     const size_t run = host_run_blocks(ctx, block_size);
     uint64_t coff = 0;
+    CrcReport rep;
     for (size_t b0 = 0; b0 < nblocks; b0 += run) {
         const size_t b1 = std::min(nblocks, b0 + run);
         uint64_t clen = 0;
@@ -1617,14 +1722,45 @@ static int host_decode_runs(w3_ctx *ctx, const uint8_t *in, size_t in_len, const
         HIPCHK(ctx, hipMemcpy(ctx->io_in.p, in + coff, (size_t)clen, hipMemcpyHostToDevice));
         HIPCHK(ctx, hipMemcpy(ctx->lens.p, block_lens + b0, (b1 - b0) * 4, hipMemcpyHostToDevice));
         if (const int rc = dev((const uint8_t *)ctx->io_in.p, (size_t)clen, (const uint32_t *)ctx->lens.p, b1 - b0, o1 - o0, (uint8_t *)ctx->io_out.p)) return rc;
-        HIPCHK(ctx, hipMemcpy(out + o0, ctx->io_out.p, (size_t)(o1 - o0), hipMemcpyDeviceToHost));
+        if (chk) {
+            ENSURE(ctx, ctx->crc_tab, (b1 - b0) * 4);
+            HIPCHK(ctx, hipMemcpyAsync(ctx->crc_tab.p, chk->crc + b0, (b1 - b0) * 4, hipMemcpyHostToDevice, ctx->stream));
+            if (const int rc = crc_enqueue(ctx, ctx->stream, (const uint8_t *)ctx->io_out.p, o1 - o0, (uint32_t)block_size, nullptr, b1 - b0,
+                                           (uint32_t)std::min<uint64_t>(block_size, o1 - o0), nullptr, (const uint32_t *)ctx->crc_tab.p, true)) return rc;
+            if (const int rc = crc_fetch(ctx, ctx->stream)) return rc;
+        }
+        HIPCHK(ctx, hipMemcpy(out + o0, ctx->io_out.p, (size_t)(o1 - o0), hipMemcpyDeviceToHost));   // (waits for the context's blocking stream too)
+        if (chk) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); rep.add(b0 + ctx->crc_res[0], ctx->crc_res[1]); }
         coff += clen;
+    }
+    return chk ? rep.finish(ctx, chk) : W3_OK;
+}
+
+// CRC-32 of every block of a host buffer of any length: up in runs of whole blocks (as host_decode_runs), the table back run by run.
+extern "C" int w3_crc32_blocks(w3_ctx *ctx, const uint8_t *in, size_t n, size_t block_size, uint32_t *crc) {
+    int rc = check_args(ctx, n, block_size, false);
+    if (rc) return rc;
+    if ((rc = jobs_idle(ctx))) return rc;
+    if (n == 0) return W3_OK;
+    if (!in || !crc) return W3_E_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t nb = (n + block_size - 1) / block_size, run = host_run_blocks(ctx, block_size);
+    for (size_t b0 = 0; b0 < nb; b0 += run) {
+        const size_t b1 = std::min(nb, b0 + run);
+        const uint64_t o0 = (uint64_t)b0 * block_size, o1 = std::min<uint64_t>(n, (uint64_t)b1 * block_size);
+        ENSURE(ctx, ctx->io_in, (size_t)(o1 - o0));
+        ENSURE(ctx, ctx->crc_tab, (b1 - b0) * 4);
+        HIPCHK(ctx, hipMemcpyAsync(ctx->io_in.p, in + o0, (size_t)(o1 - o0), hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = crc_enqueue(ctx, ctx->stream, (const uint8_t *)ctx->io_in.p, o1 - o0, (uint32_t)block_size, nullptr, b1 - b0,
+                              (uint32_t)std::min<uint64_t>(block_size, o1 - o0), (uint32_t *)ctx->crc_tab.p, nullptr, false))) return rc;
+        HIPCHK(ctx, hipMemcpyAsync(crc + b0, ctx->crc_tab.p, (b1 - b0) * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     }
     return W3_OK;
 }
 
-extern "C" int w3_decode_blocks(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t in_len, const uint32_t *block_lens, size_t nblocks,
-                                size_t block_size, uint64_t orig_len, uint8_t *out) {
+static int decode_blocks_host(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t in_len, const uint32_t *block_lens, size_t nblocks,
+                             size_t block_size, uint64_t orig_len, uint8_t *out, w3_check *chk) {
     int rc = check_args(ctx, (size_t)orig_len, block_size, false);
     if (rc) return rc;
     if ((rc = jobs_idle(ctx))) return rc;
@@ -1634,7 +1770,17 @@ extern "C" int w3_decode_blocks(w3_ctx *ctx, const w3_model_spec *spec, const ui
     HIPCHK(ctx, hipSetDevice(ctx->device));
     return host_decode_runs(ctx, in, in_len, block_lens, nblocks, block_size, orig_len, out, [&](const uint8_t *d_in, size_t len, const uint32_t *d_lens, size_t nb, uint64_t olen, uint8_t *d_out) {
         return w3_decode_blocks_device(ctx, spec, d_in, len, d_lens, nb, block_size, olen, d_out, ctx->stream);
-    });
+    }, chk);
+}
+extern "C" int w3_decode_blocks(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t in_len, const uint32_t *block_lens, size_t nblocks,
+                                size_t block_size, uint64_t orig_len, uint8_t *out) {
+    return decode_blocks_host(ctx, spec, in, in_len, block_lens, nblocks, block_size, orig_len, out, nullptr);
+}
+extern "C" int w3_decode_blocks_checked(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t in_len, const uint32_t *block_lens,
+                                        size_t nblocks, size_t block_size, uint64_t orig_len, uint8_t *out, w3_check *chk) {
+    if (!ctx) return W3_E_INVALID;
+    if (const int rc = check_arg(ctx, chk)) return rc;
+    return decode_blocks_host(ctx, spec, in, in_len, block_lens, nblocks, block_size, orig_len, out, chk);
 }
 
 // ---------------------------------------------------------------------------
@@ -1663,17 +1809,28 @@ static std::vector<uint8_t> ranges_meta(const std::vector<RangeJob> &jobs, const
 struct RangeDec {
     const ParsedSpec *ps = nullptr;
     const w3_huff_code *aoh_code = nullptr; uint8_t aoh_ctx_bits = 0;
+    // the *_checked calls: every touched block is decoded whole (widen_to_whole_blocks) and verified in the staging buffer before the gather
+    w3_check *chk = nullptr;
+    CrcReport *rep = nullptr;
 };
+// the verify's segment list of a widened plan, appended to a call's metadata (16-byte aligned; *segs_off = where)
+static void ranges_crc_segs(std::vector<uint8_t> &meta, const RangePlan &p, const uint32_t *crc, size_t &segs_off) {
+    segs_off = (meta.size() + 15) / 16 * 16;
+    meta.resize(segs_off + p.blocks.size() * sizeof(CrcSeg));
+    CrcSeg *sg = (CrcSeg *)(meta.data() + segs_off);
+    for (size_t k = 0; k < p.blocks.size(); k++) sg[k] = CrcSeg{p.bdst[k], p.blen[k], crc[p.blocks[k]]};
+}
 // (the AOH decoders live with their family, below)
 static int aoh_decode_run(w3_ctx *ctx, hipStream_t s, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *d_cin, const uint32_t *d_lens, uint32_t nb,
                           size_t block_size, uint64_t orig_len, uint8_t *d_out, const DecodeJob *d_jobs, uint32_t n_jobs, uint32_t max_job_len, bool spec);
 static bool aoh_ranges_take_spec(const w3_ctx *ctx, uint8_t ctx_bits);
 
 // Decode the jobs (d_jobs[n_jobs], stream indices into d_lens[nb] / d_cin; the longest decodes max_job_len bytes) into the staging
-// buffer, then gather the pieces (d_chunks[n_chunks], at most W3_GATHER_PIECE_MAX bytes each) into d_out.
+// buffer, then gather the pieces (d_chunks[n_chunks], at most W3_GATHER_PIECE_MAX bytes each) into d_out.  d_segs != nullptr (a checked
+// call): between the two, the n_jobs segments of the staging buffer are verified and the result is on its way to ctx->crc_res.
 static int ranges_run(w3_ctx *ctx, hipStream_t s, const RangeDec &rd, const uint8_t *d_cin, const uint32_t *d_lens, uint32_t nb, size_t block_size,
                       uint64_t orig_len, const DecodeJob *d_jobs, uint32_t n_jobs, uint32_t max_job_len, const RangePiece *d_chunks, uint32_t n_chunks,
-                      uint64_t staging, uint8_t *d_out) {
+                      uint64_t staging, uint8_t *d_out, const CrcSeg *d_segs = nullptr) {
     ENSURE(ctx, ctx->rg_stage, (size_t)staging + 16);   // (k_gather_pieces reads up to 3 bytes past a piece)
     uint8_t *d_stage = (uint8_t *)ctx->rg_stage.p;
     const int rc = !rd.ps ? aoh_decode_run(ctx, s, rd.aoh_code, rd.aoh_ctx_bits, d_cin, d_lens, nb, block_size, orig_len, d_stage, d_jobs, n_jobs, max_job_len,
@@ -1681,6 +1838,10 @@ static int ranges_run(w3_ctx *ctx, hipStream_t s, const RangeDec &rd, const uint
                  : rd.ps->is_cm() ? cm_decode(ctx, s, *rd.ps, d_cin, d_lens, nb, block_size, orig_len, d_stage, d_jobs, n_jobs)
                                   : generic_decode(ctx, s, *rd.ps, d_cin, d_lens, nb, block_size, orig_len, d_stage, d_jobs, n_jobs);
     if (rc) return rc;
+    if (d_segs) {
+        if (const int r = crc_enqueue(ctx, s, d_stage, staging, (uint32_t)block_size, d_segs, n_jobs, max_job_len, nullptr, nullptr, true)) return r;
+        if (const int r = crc_fetch(ctx, s)) return r;
+    }
     hipLaunchKernelGGL(k_gather_pieces, dim3(std::min<uint32_t>(n_chunks, 4096u)), dim3(256), 0, s, (const uint8_t *)d_stage, d_chunks, n_chunks, d_out);
     HIPCHK(ctx, hipGetLastError());
     return W3_OK;
@@ -1700,21 +1861,25 @@ static int ranges_device(w3_ctx *ctx, const RangeDec &rd, const uint8_t *d_in, s
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     if (rd.ps && (rc = stage_huff(ctx, s, *rd.ps))) return rc;
     if ((rc = check_len_table(ctx, s, d_block_lens, (uint32_t)nblocks, in_len))) return rc;
+    if (rd.chk) widen_to_whole_blocks(p, orig_len, block_size);
     const std::vector<RangePiece> chunks = gather_chunks(p, W3_GATHER_PIECE_MAX);
-    size_t coff = 0;
-    const std::vector<uint8_t> meta = ranges_meta(p.jobs, chunks, coff);
+    size_t coff = 0, segs_off = 0;
+    std::vector<uint8_t> meta = ranges_meta(p.jobs, chunks, coff);
+    if (rd.chk) ranges_crc_segs(meta, p, rd.chk->crc, segs_off);
     ENSURE(ctx, ctx->rg_meta, meta.size());
     HIPCHK(ctx, hipMemcpyAsync(ctx->rg_meta.p, meta.data(), meta.size(), hipMemcpyHostToDevice, s));
     rc = ranges_run(ctx, s, rd, d_in, d_block_lens, (uint32_t)nblocks, block_size, orig_len, (const DecodeJob *)ctx->rg_meta.p, (uint32_t)p.jobs.size(),
-                    p.jobs[0].len, (const RangePiece *)((uint8_t *)ctx->rg_meta.p + coff), (uint32_t)chunks.size(), p.staging, d_out);
+                    p.jobs[0].len, (const RangePiece *)((uint8_t *)ctx->rg_meta.p + coff), (uint32_t)chunks.size(), p.staging, d_out,
+                    rd.chk ? (const CrcSeg *)((uint8_t *)ctx->rg_meta.p + segs_off) : nullptr);
     if (rc) return rc;
     HIPCHK(ctx, hipStreamSynchronize(s));   // (meta: pageable memory of this frame)
+    if (rd.chk && ctx->crc_res[1]) rd.rep->add(p.blocks[(size_t)ctx->crc_res[0]], ctx->crc_res[1]);
     return W3_OK;
 }
 
-extern "C" int w3_decode_ranges_device(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *d_in, size_t in_len, const uint32_t *d_block_lens,
-                                       size_t nblocks, size_t block_size, uint64_t orig_len, const w3_range *ranges, size_t n_ranges,
-                                       uint8_t *d_out, size_t out_cap, size_t *out_len, void *stream) {
+static int decode_ranges_device_any(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *d_in, size_t in_len, const uint32_t *d_block_lens,
+                                    size_t nblocks, size_t block_size, uint64_t orig_len, const w3_range *ranges, size_t n_ranges,
+                                    uint8_t *d_out, size_t out_cap, size_t *out_len, void *stream, w3_check *chk) {
     if (!ctx) return W3_E_INVALID;
     if (out_len) *out_len = 0;
     int rc = check_args(ctx, (size_t)orig_len, block_size);
@@ -1724,8 +1889,23 @@ extern "C" int w3_decode_ranges_device(w3_ctx *ctx, const w3_model_spec *spec, c
     if ((rc = parse_spec(spec, ps))) { ctx->err = "malformed model spec"; return rc; }
     if (!out_len) return W3_E_INVALID;
     RangeDec rd;
-    rd.ps = &ps;
-    return ranges_device(ctx, rd, d_in, in_len, d_block_lens, nblocks, block_size, orig_len, ranges, n_ranges, d_out, out_cap, out_len, stream);
+    CrcReport rep;
+    rd.ps = &ps; rd.chk = chk; rd.rep = &rep;
+    rc = ranges_device(ctx, rd, d_in, in_len, d_block_lens, nblocks, block_size, orig_len, ranges, n_ranges, d_out, out_cap, out_len, stream);
+    return rc || !chk ? rc : rep.finish(ctx, chk);
+}
+extern "C" int w3_decode_ranges_device(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *d_in, size_t in_len, const uint32_t *d_block_lens,
+                                       size_t nblocks, size_t block_size, uint64_t orig_len, const w3_range *ranges, size_t n_ranges,
+                                       uint8_t *d_out, size_t out_cap, size_t *out_len, void *stream) {
+    return decode_ranges_device_any(ctx, spec, d_in, in_len, d_block_lens, nblocks, block_size, orig_len, ranges, n_ranges, d_out, out_cap, out_len, stream, nullptr);
+}
+extern "C" int w3_decode_ranges_device_checked(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *d_in, size_t in_len, const uint32_t *d_block_lens,
+                                               size_t nblocks, size_t block_size, uint64_t orig_len, const w3_range *ranges, size_t n_ranges,
+                                               uint8_t *d_out, size_t out_cap, size_t *out_len, void *stream, w3_check *chk) {
+    if (!ctx) return W3_E_INVALID;
+    if (out_len) *out_len = 0;
+    if (const int rc = check_arg(ctx, chk)) return rc;
+    return decode_ranges_device_any(ctx, spec, d_in, in_len, d_block_lens, nblocks, block_size, orig_len, ranges, n_ranges, d_out, out_cap, out_len, stream, chk);
 }
 
 // One device call of the host variant: only the selected blocks' streams go over PCIe, with the compact length table, the jobs (naming
@@ -1748,9 +1928,11 @@ static int ranges_host_one(w3_ctx *ctx, const RangeDec &rd, const uint8_t *in, c
     }
     uint64_t sbytes = 0;
     for (size_t k = 0; k < nd; k++) sbytes += block_lens[p.blocks[k]];
+    if (rd.chk) widen_to_whole_blocks(p, orig_len, block_size);
     const std::vector<RangePiece> chunks = gather_chunks(p, W3_GATHER_PIECE_MAX);
-    size_t coff = 0;
-    const std::vector<uint8_t> meta = ranges_meta(compact_jobs(p), chunks, coff);
+    size_t coff = 0, segs_off = 0;
+    std::vector<uint8_t> meta = ranges_meta(compact_jobs(p), chunks, coff);
+    if (rd.chk) ranges_crc_segs(meta, p, rd.chk->crc, segs_off);
     const size_t lens_off = (meta.size() + 15) / 16 * 16, str_off = (lens_off + nd * 4 + 15) / 16 * 16;
     const size_t bytes = str_off + (size_t)sbytes;
     if (bytes > ctx->h_rg_cap) {
@@ -1777,10 +1959,12 @@ static int ranges_host_one(w3_ctx *ctx, const RangeDec &rd, const uint8_t *in, c
     if (rc) return rc;
     if ((rc = scan_lens(ctx, s, (const uint32_t *)(d + lens_off), (uint32_t)nd))) return rc;   // (the compact table's total was checked on the host)
     rc = ranges_run(ctx, s, rd, d + str_off, (const uint32_t *)(d + lens_off), (uint32_t)nd, block_size, orig_len, (const DecodeJob *)d, (uint32_t)nd,
-                    p.jobs[0].len, (const RangePiece *)(d + coff), (uint32_t)chunks.size(), p.staging, (uint8_t *)ctx->io_out.p);
+                    p.jobs[0].len, (const RangePiece *)(d + coff), (uint32_t)chunks.size(), p.staging, (uint8_t *)ctx->io_out.p,
+                    rd.chk ? (const CrcSeg *)(d + segs_off) : nullptr);
     if (rc) return rc;
     HIPCHK(ctx, hipMemcpyAsync(out, ctx->io_out.p, (size_t)p.out_len, hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
+    if (rd.chk && ctx->crc_res[1]) rd.rep->add(p.blocks[(size_t)ctx->crc_res[0]], ctx->crc_res[1]);
     return W3_OK;
 }
 
@@ -1828,9 +2012,9 @@ static int ranges_host(w3_ctx *ctx, const RangeDec &rd, const uint8_t *in, size_
     return flush();
 }
 
-extern "C" int w3_decode_ranges(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t in_len, const uint32_t *block_lens,
-                                size_t nblocks, size_t block_size, uint64_t orig_len, const w3_range *ranges, size_t n_ranges,
-                                uint8_t *out, size_t out_cap, size_t *out_len) {
+static int decode_ranges_any(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t in_len, const uint32_t *block_lens,
+                             size_t nblocks, size_t block_size, uint64_t orig_len, const w3_range *ranges, size_t n_ranges,
+                             uint8_t *out, size_t out_cap, size_t *out_len, w3_check *chk) {
     if (!ctx) return W3_E_INVALID;
     if (out_len) *out_len = 0;
     int rc = check_args(ctx, (size_t)orig_len, block_size, false);   // (any length: a large selection goes through in several device calls)
@@ -1840,8 +2024,23 @@ extern "C" int w3_decode_ranges(w3_ctx *ctx, const w3_model_spec *spec, const ui
     if ((rc = parse_spec(spec, ps))) { ctx->err = "malformed model spec"; return rc; }
     if (!out_len) return W3_E_INVALID;
     RangeDec rd;
-    rd.ps = &ps;
-    return ranges_host(ctx, rd, in, in_len, block_lens, nblocks, block_size, orig_len, ranges, n_ranges, out, out_cap, out_len);
+    CrcReport rep;
+    rd.ps = &ps; rd.chk = chk; rd.rep = &rep;
+    rc = ranges_host(ctx, rd, in, in_len, block_lens, nblocks, block_size, orig_len, ranges, n_ranges, out, out_cap, out_len);
+    return rc || !chk ? rc : rep.finish(ctx, chk);
+}
+extern "C" int w3_decode_ranges(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t in_len, const uint32_t *block_lens,
+                                size_t nblocks, size_t block_size, uint64_t orig_len, const w3_range *ranges, size_t n_ranges,
+                                uint8_t *out, size_t out_cap, size_t *out_len) {
+    return decode_ranges_any(ctx, spec, in, in_len, block_lens, nblocks, block_size, orig_len, ranges, n_ranges, out, out_cap, out_len, nullptr);
+}
+extern "C" int w3_decode_ranges_checked(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t in_len, const uint32_t *block_lens,
+                                        size_t nblocks, size_t block_size, uint64_t orig_len, const w3_range *ranges, size_t n_ranges,
+                                        uint8_t *out, size_t out_cap, size_t *out_len, w3_check *chk) {
+    if (!ctx) return W3_E_INVALID;
+    if (out_len) *out_len = 0;
+    if (const int rc = check_arg(ctx, chk)) return rc;
+    return decode_ranges_any(ctx, spec, in, in_len, block_lens, nblocks, block_size, orig_len, ranges, n_ranges, out, out_cap, out_len, chk);
 }
 
 // ---------------------------------------------------------------------------
@@ -2843,36 +3042,65 @@ static int aoh_ranges_check(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_b
     return out_len ? W3_OK : W3_E_INVALID;
 }
 
-extern "C" int w3_aoh_decode_ranges_device(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *d_in, size_t in_len,
-                                           const uint32_t *d_block_lens, size_t nblocks, size_t block_size, uint64_t orig_len, const w3_range *ranges,
-                                           size_t n_ranges, uint8_t *d_out, size_t out_cap, size_t *out_len, void *stream) {
+static int aoh_decode_ranges_device_any(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *d_in, size_t in_len,
+                                        const uint32_t *d_block_lens, size_t nblocks, size_t block_size, uint64_t orig_len, const w3_range *ranges,
+                                        size_t n_ranges, uint8_t *d_out, size_t out_cap, size_t *out_len, void *stream, w3_check *chk) {
     if (!ctx) return W3_E_INVALID;
     int rc = aoh_ranges_check(ctx, code, ctx_bits, block_size, orig_len, true, out_len);
     if (rc) return rc;
     RangeDec rd;
-    rd.aoh_code = code; rd.aoh_ctx_bits = ctx_bits;
+    CrcReport rep;
+    rd.aoh_code = code; rd.aoh_ctx_bits = ctx_bits; rd.chk = chk; rd.rep = &rep;
     if ((rc = ranges_device(ctx, rd, d_in, in_len, d_block_lens, nblocks, block_size, orig_len, ranges, n_ranges, d_out, out_cap, out_len, stream))) return rc;
     ctx->timing.path = aoh_ranges_take_spec(ctx, ctx_bits) ? W3_PATH_SPEC : W3_PATH_GENERIC;
-    return W3_OK;
+    return chk ? rep.finish(ctx, chk) : W3_OK;
+}
+extern "C" int w3_aoh_decode_ranges_device(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *d_in, size_t in_len,
+                                           const uint32_t *d_block_lens, size_t nblocks, size_t block_size, uint64_t orig_len, const w3_range *ranges,
+                                           size_t n_ranges, uint8_t *d_out, size_t out_cap, size_t *out_len, void *stream) {
+    return aoh_decode_ranges_device_any(ctx, code, ctx_bits, d_in, in_len, d_block_lens, nblocks, block_size, orig_len, ranges, n_ranges, d_out, out_cap, out_len, stream, nullptr);
+}
+extern "C" int w3_aoh_decode_ranges_device_checked(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *d_in, size_t in_len,
+                                                   const uint32_t *d_block_lens, size_t nblocks, size_t block_size, uint64_t orig_len,
+                                                   const w3_range *ranges, size_t n_ranges, uint8_t *d_out, size_t out_cap, size_t *out_len, void *stream,
+                                                   w3_check *chk) {
+    if (!ctx) return W3_E_INVALID;
+    if (out_len) *out_len = 0;
+    if (const int rc = check_arg(ctx, chk)) return rc;
+    return aoh_decode_ranges_device_any(ctx, code, ctx_bits, d_in, in_len, d_block_lens, nblocks, block_size, orig_len, ranges, n_ranges, d_out, out_cap, out_len, stream, chk);
 }
 
-extern "C" int w3_aoh_decode_ranges(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *in, size_t in_len, const uint32_t *block_lens,
-                                    size_t nblocks, size_t block_size, uint64_t orig_len, const w3_range *ranges, size_t n_ranges, uint8_t *out,
-                                    size_t out_cap, size_t *out_len) {
+static int aoh_decode_ranges_any(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *in, size_t in_len, const uint32_t *block_lens,
+                                 size_t nblocks, size_t block_size, uint64_t orig_len, const w3_range *ranges, size_t n_ranges, uint8_t *out,
+                                 size_t out_cap, size_t *out_len, w3_check *chk) {
     if (!ctx) return W3_E_INVALID;
     int rc = aoh_ranges_check(ctx, code, ctx_bits, block_size, orig_len, false, out_len);   // (any length, as w3_decode_ranges)
     if (rc) return rc;
     RangeDec rd;
-    rd.aoh_code = code; rd.aoh_ctx_bits = ctx_bits;
+    CrcReport rep;
+    rd.aoh_code = code; rd.aoh_ctx_bits = ctx_bits; rd.chk = chk; rd.rep = &rep;
     if ((rc = ranges_host(ctx, rd, in, in_len, block_lens, nblocks, block_size, orig_len, ranges, n_ranges, out, out_cap, out_len))) return rc;
     ctx->timing.path = aoh_ranges_take_spec(ctx, ctx_bits) ? W3_PATH_SPEC : W3_PATH_GENERIC;
-    return W3_OK;
+    return chk ? rep.finish(ctx, chk) : W3_OK;
+}
+extern "C" int w3_aoh_decode_ranges(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *in, size_t in_len, const uint32_t *block_lens,
+                                    size_t nblocks, size_t block_size, uint64_t orig_len, const w3_range *ranges, size_t n_ranges, uint8_t *out,
+                                    size_t out_cap, size_t *out_len) {
+    return aoh_decode_ranges_any(ctx, code, ctx_bits, in, in_len, block_lens, nblocks, block_size, orig_len, ranges, n_ranges, out, out_cap, out_len, nullptr);
+}
+extern "C" int w3_aoh_decode_ranges_checked(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *in, size_t in_len,
+                                            const uint32_t *block_lens, size_t nblocks, size_t block_size, uint64_t orig_len, const w3_range *ranges,
+                                            size_t n_ranges, uint8_t *out, size_t out_cap, size_t *out_len, w3_check *chk) {
+    if (!ctx) return W3_E_INVALID;
+    if (out_len) *out_len = 0;
+    if (const int rc = check_arg(ctx, chk)) return rc;
+    return aoh_decode_ranges_any(ctx, code, ctx_bits, in, in_len, block_lens, nblocks, block_size, orig_len, ranges, n_ranges, out, out_cap, out_len, chk);
 }
 
 extern "C" int w3_aoh_decode_spec_covers(uint8_t ctx_bits) { return aoh_spec_covers(ctx_bits) ? 1 : 0; }
 
-extern "C" int w3_aoh_decode_blocks(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *in, size_t in_len, const uint32_t *block_lens,
-                                    size_t nblocks, size_t block_size, uint64_t orig_len, uint8_t *out) {
+static int aoh_decode_blocks_host(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *in, size_t in_len, const uint32_t *block_lens,
+                                 size_t nblocks, size_t block_size, uint64_t orig_len, uint8_t *out, w3_check *chk) {
     int rc = aoh_check(ctx, code, 1, &ctx_bits, 1, (size_t)orig_len, block_size, false);
     if (rc) return rc;
     if ((uint64_t)nblocks != (orig_len + block_size - 1) / block_size) { ctx->err = "nblocks does not match orig_len/block_size"; return W3_E_INVALID; }
@@ -2881,7 +3109,17 @@ extern "C" int w3_aoh_decode_blocks(w3_ctx *ctx, const w3_huff_code *code, uint8
     HIPCHK(ctx, hipSetDevice(ctx->device));
     return host_decode_runs(ctx, in, in_len, block_lens, nblocks, block_size, orig_len, out, [&](const uint8_t *d_in, size_t len, const uint32_t *d_lens, size_t nb, uint64_t olen, uint8_t *d_out) {
         return w3_aoh_decode_blocks_device(ctx, code, ctx_bits, d_in, len, d_lens, nb, block_size, olen, d_out, ctx->stream);
-    });
+    }, chk);
+}
+extern "C" int w3_aoh_decode_blocks(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *in, size_t in_len, const uint32_t *block_lens,
+                                    size_t nblocks, size_t block_size, uint64_t orig_len, uint8_t *out) {
+    return aoh_decode_blocks_host(ctx, code, ctx_bits, in, in_len, block_lens, nblocks, block_size, orig_len, out, nullptr);
+}
+extern "C" int w3_aoh_decode_blocks_checked(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *in, size_t in_len,
+                                            const uint32_t *block_lens, size_t nblocks, size_t block_size, uint64_t orig_len, uint8_t *out, w3_check *chk) {
+    if (!ctx) return W3_E_INVALID;
+    if (const int rc = check_arg(ctx, chk)) return rc;
+    return aoh_decode_blocks_host(ctx, code, ctx_bits, in, in_len, block_lens, nblocks, block_size, orig_len, out, chk);
 }
 
 // the counting sink for configurations (codes[code_idx[c]], ctx_bits[c]) on a device-resident input: d_bits[ncfg][nb] (device).

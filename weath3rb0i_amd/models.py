@@ -11,8 +11,9 @@ from . import _lib as L
 
 
 class W3Error(RuntimeError):
-    def __init__(self, code, msg=""):
+    def __init__(self, code, msg="", bad_block=None, n_bad=None):
         self.code = code
+        self.bad_block, self.n_bad = bad_block, n_bad   # W3_E_CORRUPT: the lowest block that fails its CRC-32, and how many do
         super().__init__("w3hip error %d (%s) %s" % (code, L.load().w3_strerror(code).decode(), msg))
 
 
