@@ -591,7 +591,8 @@ def test_twophase_counter_saturation(ctx, oracle):
 
 def test_coder_variants_and_fallback(ctx, oracle):
     """Every coder kernel (k_coder_x4 / x5 asm pipelines, x3, x2, k_coder_fast with its slot/carry accumulator, the robust k_coder) and
-    the hand-back path; x5 also with one, three and four streams mixed on the fly and ragged / tiny blocks (its C paths)."""
+    the hand-back path; x5, x4 and x3 also with one, three and four streams mixed on the fly (the mix and lane setup they share, at
+    every L) and ragged / tiny blocks (the C paths x4 and x5 share: blocks below one chunk, below one ring, no multiple of either)."""
     data = markov_text(60000, seed=31) + bytes(5000) + np.random.default_rng(2).integers(0, 256, 20000, dtype=np.uint8).tobytes()
     want, wlens = oracle.encode_blocks(oracle.BestOfTwoModel(oracle.Order0(), oracle.Order1()), data, 8192, nthreads=8)
     model = w3.BestOfTwoModel(w3.Order0(), w3.Order1())
@@ -611,11 +612,16 @@ def test_coder_variants_and_fallback(ctx, oracle):
                 if limit == 19:
                     assert ctx.timing()["n_recoded_blocks"] > 0
             ctx.set_acc_limit(46)
-        ctx.set_coder("x5")
         tail = markov_text(3 * 8192 + 5, seed=77) + b"ab"
         for name in ("order0", "best012", "best_ac_wide"):
+            dev, orc = pair(oracle, name)
             for d_, bs_ in ((data, 8192), (tail, 8192), (tail[:8195], 4099), (tail[:700], 7), (tail[:64 * 13 + 3], 13)):
-                check_blocks(ctx, oracle, name, d_, bs_, "twophase")
+                want_, wlens_ = oracle.encode_blocks(orc(), d_, bs_, nthreads=8)   # one reference for the three coders
+                for mode in ("x5", "x4", "x3"):
+                    ctx.set_coder(mode)
+                    out, lens = ctx.encode_blocks(dev(), d_, bs_)
+                    assert lens.tolist() == wlens_.tolist(), (mode, name, len(d_), bs_)
+                    assert out.tobytes() == want_.tobytes(), (mode, name, len(d_), bs_)
     finally:
         ctx.set_acc_limit(46)
         ctx.set_coder("x4")

@@ -19,6 +19,12 @@
 //  * a lane whose pending run outgrows the 64-bit accumulator (probability
 //    ~2^-39 per E3 episode; adversarial inputs can force it) gives up and its
 //    block is re-coded by k_coder (counted pending bits, any length).
+//
+// This file owns k_coder, k_coder_fast, k_coder_x2 and k_coder_x3<L>, and the three parts the coder kernels (those of
+// w3_coder4.h and w3_coder5.h included) take from here: SlotAcc (the slot/carry output accumulator: guard, absorb,
+// move-32, final flush), opinion_mix2<L> / opinion_mix2_at (OpinionMixer2 over a dword's two steps) and coder_lanes (lane -> block setup
+// of the wave pipelines).  k_coder_fast and the output wave of k_coder_x4 keep their own copy of the accumulator code:
+// with SlotAcc inlined both measured slower than the margin allows (profiles/coder_shared/README.md).
 #pragma once
 #include "w3_device.h"
 
@@ -39,6 +45,11 @@ struct CoderArgs {
     uint32_t *out_bits;    // [nblocks] ACStats bit count of each block (helpers.rs:60-90: written bits before the flush), or null
 };
 
+// bytes of the block at byte offset off: block_size, or what is left of the input
+__device__ __forceinline__ uint32_t coder_block_len(uint64_t n, uint64_t off, uint32_t block_size) {
+    return (uint32_t)((n - off) < block_size ? (n - off) : block_size);
+}
+
 // Robust coder: counted pending bits (Encoder in w3_device.h).  Codes the
 // blocks listed in redo[0..n_redo) or, when redo == nullptr, every block.
 __global__ void __launch_bounds__(64) k_coder(CoderArgs a) {
@@ -47,7 +58,7 @@ __global__ void __launch_bounds__(64) k_coder(CoderArgs a) {
     if (a.redo) { if (idx >= a.n_redo) return; b = a.redo[idx]; }
     else { if (idx >= a.nblocks) return; b = idx; }
     const uint64_t off = (uint64_t)b * a.block_size;
-    const uint32_t len = (uint32_t)((a.n - off) < a.block_size ? (a.n - off) : a.block_size);
+    const uint32_t len = coder_block_len(a.n, off, a.block_size);
     const uint4 *Pb = a.P + off;
     const uint8_t *blk = a.in + off;
     Encoder enc;
@@ -68,6 +79,129 @@ __global__ void __launch_bounds__(64) k_coder(CoderArgs a) {
     const uint32_t produced = enc.flush();
     a.out_len[b] = produced;
     if (produced > a.stripe_cap) atomicOr(&a.flags[0], 1u);
+}
+
+// ---------------------------------------------------------------------------
+// Shared by the coder kernels: block extent and lane setup, output accumulator, mix
+// ---------------------------------------------------------------------------
+// Lane setup of the wave pipelines (x2 .. x5): every wave of the workgroup maps lane -> block, so all of them see the
+// same extents.  maxlen is the longest block of the 64; lenB (MINLEN only) the shorter of the (at most two) block lengths
+// in the wave, 0 < lenB <= maxlen.  Clears the n_sync progress words and ends with the workgroup barrier.
+struct CoderLanes {
+    uint32_t wave, lane, b;
+    bool act;          // b < nblocks
+    uint64_t off;      // (inactive lanes: block 0, len 0)
+    uint32_t len, maxlen, lenB;
+};
+template <bool MINLEN, class Args>
+__device__ __forceinline__ CoderLanes coder_lanes(const Args &a, uint32_t *sync_w, uint32_t n_sync) {
+    CoderLanes c;
+    c.wave = threadIdx.x >> 6; c.lane = threadIdx.x & 63u;
+    c.b = blockIdx.x * 64u + c.lane;
+    c.act = c.b < a.nblocks;
+    c.off = (uint64_t)(c.act ? c.b : 0u) * a.block_size;
+    c.len = c.act ? coder_block_len(a.n, c.off, a.block_size) : 0u;
+    uint32_t maxlen = c.len, lenB = c.len ? c.len : 0xFFFFFFFFu;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        maxlen = max(maxlen, (uint32_t)__shfl_xor((int)maxlen, d, 64));
+        if constexpr (MINLEN) lenB = min(lenB, (uint32_t)__shfl_xor((int)lenB, d, 64));
+    }
+    c.maxlen = __builtin_amdgcn_readfirstlane(maxlen);
+    c.lenB = MINLEN ? __builtin_amdgcn_readfirstlane(lenB) : 0u;
+    if (threadIdx.x < n_sync) sync_w[threadIdx.x] = 0u;
+    __syncthreads();
+    return c;
+}
+
+__device__ __forceinline__ uint32_t trailing_ones64(uint64_t v) {
+    const uint64_t z = ~v;
+    return z ? (uint32_t)(__ffsll((long long)z) - 1) : 64u;
+}
+
+// The slot/carry output accumulator of the header comment, once for the output waves of x2, x3 and x5.
+// The low nb bits of acc are valid and end with the slot (0) + one 1 per pending bit.  Per token the caller runs
+//     if (o.nb > limit) o.guard(out, cap, limit);   o.absorb(x1, s);
+// per input byte o.move32(out, cap), and at the end of the block o.finish(...).  out/cap: the lane's stripe.
+struct SlotAcc {
+    uint64_t acc;
+    uint32_t nb, pos;   // valid bits of acc; bytes written
+    uint32_t failed;    // a pending run outgrew the accumulator: the block goes to k_coder
+    __device__ __forceinline__ void init() { acc = 0ull; nb = 1u; pos = 0u; failed = 0u; }   // one slot: the first output bit
+
+    // bytes leave from the top, one at a time, while more than keep + 7 bits are held
+    __device__ __forceinline__ void put_bytes(uint8_t *out, uint32_t cap, uint32_t keep) {
+#pragma unroll 1
+        while (nb >= keep + 8u) {
+            const uint8_t v = (uint8_t)(acc >> (nb - 8u));
+            if (pos < cap) out[pos] = v;
+            pos += 1u; nb -= 8u;
+        }
+    }
+    // accumulator nearly full (nb > limit): drain the finalised bytes, those above the slot
+    __device__ __forceinline__ void guard(uint8_t *out, uint32_t cap, uint32_t limit) {
+        put_bytes(out, cap, trailing_ones64(acc) + 1u);
+        if (nb > limit) { failed = 1u; acc = 0ull; nb = 1u; }   // pending run longer than the accumulator: hand the block to k_coder
+    }
+    // one token: x1 after the update (true bit 31) and the shift count s.  b into the slot (0 when n == 0), then rest | new slot | pending ones
+    __device__ __forceinline__ void absorb(uint32_t x1, uint32_t s) {
+        acc += x1 >> 31;
+        acc = (acc << s) | __builtin_amdgcn_ubfe(x1, 31u - s, s);
+        nb += s;
+    }
+    // once per input byte: move 32 finalised bits out (never the slot or the pending ones)
+    __device__ __forceinline__ void move32(uint8_t *out, uint32_t cap) {
+        const uint32_t lo = (uint32_t)acc;
+        const uint32_t pend = (~lo ? (uint32_t)__builtin_ctz(~lo) : 32u) + 1u;   // slot + pending ones (>= 33: nothing to move)
+        if (nb >= pend + 32u) {
+            const uint32_t wv = (uint32_t)(acc >> (nb - 32u));
+            if (pos + 4u <= cap) { const uint32_t be = __builtin_bswap32(wv); __builtin_memcpy(out + pos, &be, 4); }
+            pos += 4u; nb -= 32u;
+        }
+    }
+    // ArithmeticCoder::flush -> ACWriter::flush(x2) (arithmetic_coder.rs:67-71, io.rs:91-100): first bit x2 >> 31 (= 1) resolves
+    // the slot and the pending bits, then x2's next bits pad to a byte.  Writes out_bits[b] (when count), then out_len[b]
+    // and the stripe-overflow flag, or appends b to redo.  Works on a copy: x4/x5 lanes keep absorbing after their block's end.
+    template <class Args>
+    __device__ __forceinline__ void finish(const Args &a, uint32_t b, uint32_t x2, uint8_t *out, uint32_t cap, bool count) const {
+        if (count && !failed) a.out_bits[b] = 8u * pos + nb - (trailing_ones64(acc) + 1u);   // ACStats (helpers.rs:60-90): all bits but the slot and the pending ones
+        SlotAcc f = *this;
+        f.acc += 1ull;
+        const uint32_t idx = f.nb & 7u;
+        if (idx) { const uint32_t k = 8u - idx; f.acc = (f.acc << k) | ((x2 << 1) >> (32u - k)); f.nb += k; }
+        f.put_bytes(out, cap, 0u);
+        if (failed) { const uint32_t k = atomicAdd(&a.flags[1], 1u); a.redo[k] = b; }
+        else { a.out_len[b] = f.pos; if (f.pos > cap) atomicOr(&a.flags[0], 1u); }
+    }
+};
+
+// OpinionMixer2 (leftmost leaf of maximal |p - 1/2|) over L leaf streams, for both steps of a dword at once with packed
+// 16-bit VALU (the M-wave, not the recurrence, was the slowest wave for L >= 2: a lone wave pays per instruction).
+// Distances |p - 32768| <= 32767 because Counter::p is in [1, 65535], so their difference fits an i16 and its sign is the
+// "strictly farther" mask (ties keep the left leaf).  w[l]: leaf l's dword (two u16 probabilities).
+template <int L>
+__device__ __forceinline__ uint32_t opinion_mix2(const uint32_t (&w)[L]) {
+    if constexpr (L == 1) {
+        return w[0];
+    } else {
+        u16x2 P = as_u16x2(w[0]), D = pk_opinion_dist(P);
+#pragma unroll
+        for (int l = 1; l < L; l++) {
+            const u16x2 Q = as_u16x2(w[l]), E = pk_opinion_dist(Q);
+            const uint32_t mask = pk_farther_mask(D, E);                   // 0xFFFF where E > D
+            P = as_u16x2((as_u32(Q) & mask) | (as_u32(P) & ~mask));
+            D = __builtin_elementwise_max(D, E);
+        }
+        return as_u32(P);
+    }
+}
+// dword q of the 8 x u16 probabilities of one input byte, for each of the L leaves
+template <int L, int N>
+__device__ __forceinline__ uint32_t opinion_mix2_at(const uint4 (&p)[L][N], uint32_t k, int q) {
+    uint32_t w[L];
+#pragma unroll
+    for (int l = 0; l < L; l++) w[l] = q == 0 ? p[l][k].x : q == 1 ? p[l][k].y : q == 2 ? p[l][k].z : p[l][k].w;
+    return opinion_mix2<L>(w);
 }
 
 // ---------------------------------------------------------------------------
@@ -100,16 +234,11 @@ __device__ __forceinline__ void fast_step(FastEnc &e, uint32_t bitmask, uint32_t
     e.x2 = ~((~e.x2 << c) >> 1);                                                              // == (x2 << s) | 0x80000000 | ones(s)
 }
 
-__device__ __forceinline__ uint32_t trailing_ones64(uint64_t v) {
-    const uint64_t z = ~v;
-    return z ? (uint32_t)(__ffsll((long long)z) - 1) : 64u;
-}
-
 __global__ void __launch_bounds__(64) k_coder_fast(CoderArgs a) {
     const uint32_t b = blockIdx.x * 64u + threadIdx.x;
     if (b >= a.nblocks) return;
     const uint64_t off = (uint64_t)b * a.block_size;
-    const uint32_t len = (uint32_t)((a.n - off) < a.block_size ? (a.n - off) : a.block_size);
+    const uint32_t len = coder_block_len(a.n, off, a.block_size);
     const uint4 *Pb = a.P + off;
     const uint8_t *blk = a.in + off;
     uint8_t *out = a.stripes + (uint64_t)b * a.stripe_cap;
@@ -229,17 +358,10 @@ __global__ void __launch_bounds__(128) k_coder_x2(CoderArgs a) {
     __shared__ uint2 tok[W3_X2_RING * 8u * 64u];   // [ring byte][bit][lane]
     __shared__ uint32_t fin_x2[64];
     __shared__ uint32_t sync_w[4];                  // [0] bytes produced, [1] bytes consumed, [2] abort
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const uint32_t b = blockIdx.x * 64u + lane;
-    const bool act = b < a.nblocks;
-    const uint64_t off = (uint64_t)(act ? b : 0u) * a.block_size;
-    const uint32_t len = act ? (uint32_t)((a.n - off) < a.block_size ? (a.n - off) : a.block_size) : 0u;
-    uint32_t maxlen = len;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) maxlen = max(maxlen, (uint32_t)__shfl_xor((int)maxlen, d, 64));
-    maxlen = __builtin_amdgcn_readfirstlane(maxlen);
-    if (threadIdx.x < 4) sync_w[threadIdx.x] = 0u;
-    __syncthreads();
+    const CoderLanes c = coder_lanes<false>(a, sync_w, 4);
+    const uint32_t wave = c.wave, lane = c.lane, b = c.b, len = c.len, maxlen = c.maxlen;
+    const bool act = c.act;
+    const uint64_t off = c.off;
     volatile uint32_t *prod = &sync_w[0], *cons = &sync_w[1], *abortf = &sync_w[2];
 
     if (wave == 0) {
@@ -298,8 +420,8 @@ __global__ void __launch_bounds__(128) k_coder_x2(CoderArgs a) {
     // -------------------------------- O-wave --------------------------------
     uint8_t *out = a.stripes + (uint64_t)(act ? b : 0u) * a.stripe_cap;
     const uint32_t cap = act ? a.stripe_cap : 0u, limit = a.acc_limit;
-    uint64_t acc = 0ull; uint32_t nb = 1u, pos = 0u;
-    bool failed = false, dead = false;
+    SlotAcc o; o.init();
+    bool dead = false;
     for (uint32_t i = 0; i < maxlen && !dead; i += 8) {
         const uint32_t need = min(i + 8u, maxlen);
         uint32_t spins = 0;
@@ -318,28 +440,10 @@ __global__ void __launch_bounds__(128) k_coder_x2(CoderArgs a) {
                 for (int j = 0; j < 8; j++) t[j] = slot[j * 64];
 #pragma unroll
                 for (int j = 0; j < 8; j++) {
-                    if (__builtin_expect(nb > limit, 0)) {
-                        const uint32_t pend = trailing_ones64(acc) + 1u;
-#pragma unroll 1
-                        while (nb >= pend + 8u) {
-                            const uint8_t v = (uint8_t)(acc >> (nb - 8u));
-                            if (pos < cap) out[pos] = v;
-                            pos += 1u; nb -= 8u;
-                        }
-                        if (nb > limit) { failed = true; acc = 0ull; nb = 1u; }
-                    }
-                    const uint32_t x1v = t[j].x, c = t[j].y, s = c - 1u;
-                    acc += x1v >> 31;
-                    acc = (acc << s) | __builtin_amdgcn_ubfe(x1v, 32u - c, s);
-                    nb += s;
+                    if (__builtin_expect(o.nb > limit, 0)) o.guard(out, cap, limit);
+                    o.absorb(t[j].x, t[j].y - 1u);   // token = (x1 after the update, c = s + 1)
                 }
-                const uint32_t lo = (uint32_t)acc;
-                const uint32_t pend = (~lo ? (uint32_t)__builtin_ctz(~lo) : 32u) + 1u;
-                if (nb >= pend + 32u) {
-                    const uint32_t wv = (uint32_t)(acc >> (nb - 32u));
-                    if (pos + 4u <= cap) { const uint32_t be = __builtin_bswap32(wv); __builtin_memcpy(out + pos, &be, 4); }
-                    pos += 4u; nb -= 32u;
-                }
+                o.move32(out, cap);
             }
         }
         __asm__ volatile("" ::: "memory");
@@ -347,25 +451,8 @@ __global__ void __launch_bounds__(128) k_coder_x2(CoderArgs a) {
     }
     if (dead) { if (lane == 0) atomicOr(&a.flags[0], 2u); return; }
     if (!act) return;
-    // ACWriter::flush(x2) (io.rs:91-100)
-    const uint32_t x2f = fin_x2[lane];
-    if (a.out_bits && !failed) a.out_bits[b] = 8u * pos + nb - (trailing_ones64(acc) + 1u);   // ACStats: all bits but the slot and the pending ones
-    acc += 1ull;
-    const uint32_t idx = nb & 7u;
-    if (idx) { const uint32_t k = 8u - idx; acc = (acc << k) | ((x2f << 1) >> (32u - k)); nb += k; }
-#pragma unroll 1
-    while (nb >= 8u) {
-        const uint8_t v = (uint8_t)(acc >> (nb - 8u));
-        if (pos < cap) out[pos] = v;
-        pos += 1u; nb -= 8u;
-    }
-    if (failed) { const uint32_t k = atomicAdd(&a.flags[1], 1u); a.redo[k] = b; }
-    else { a.out_len[b] = pos; if (pos > cap) atomicOr(&a.flags[0], 1u); }
+    o.finish(a, b, fin_x2[lane], out, cap, a.out_bits != nullptr);
 }
-
-}  // namespace w3
-
-namespace w3 {
 
 // ---------------------------------------------------------------------------
 // k_coder_x3<L> — three wavefronts per 64 blocks: MIX -> RECURRENCE -> OUTPUT.
@@ -415,17 +502,10 @@ __global__ void __launch_bounds__(192) k_coder_x3(Coder3Args a) {
     __shared__ uint2 tok[W3_X2_RING * 8u * 64u];   // X -> O: (x1 after update, s)      [ring byte][bit][lane]
     __shared__ uint32_t fin_x2[64];
     __shared__ uint32_t sync_w[8];                 // [0] M produced, [1] X consumed, [2] X produced, [3] O consumed, [4] abort
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const uint32_t b = blockIdx.x * 64u + lane;
-    const bool act = b < a.nblocks;
-    const uint64_t off = (uint64_t)(act ? b : 0u) * a.block_size;
-    const uint32_t len = act ? (uint32_t)((a.n - off) < a.block_size ? (a.n - off) : a.block_size) : 0u;
-    uint32_t maxlen = len;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) maxlen = max(maxlen, (uint32_t)__shfl_xor((int)maxlen, d, 64));
-    maxlen = __builtin_amdgcn_readfirstlane(maxlen);
-    if (threadIdx.x < 8) sync_w[threadIdx.x] = 0u;
-    __syncthreads();
+    const CoderLanes c = coder_lanes<false>(a, sync_w, 8);
+    const uint32_t wave = c.wave, lane = c.lane, b = c.b, len = c.len, maxlen = c.maxlen;
+    const bool act = c.act;
+    const uint64_t off = c.off;
     volatile uint32_t *m_prod = &sync_w[0], *x_cons = &sync_w[1], *x_prod = &sync_w[2], *o_cons = &sync_w[3], *abortf = &sync_w[4];
     bool dead = false;
 
@@ -467,23 +547,7 @@ __global__ void __launch_bounds__(192) k_coder_x3(Coder3Args a) {
                     uint2 *slot = opq + ((size_t)((i + k) & (W3_X2_RING - 1u)) * 8u) * 64u + lane;
 #pragma unroll
                     for (int q = 0; q < 4; q++) {   // one dword = two steps
-                        uint32_t w0 = q == 0 ? cur[0][k].x : q == 1 ? cur[0][k].y : q == 2 ? cur[0][k].z : cur[0][k].w;
-                        if constexpr (L > 1) {
-                            // OpinionMixer2 for both steps of the dword at once with packed 16-bit VALU (the M-wave, not the
-                            // recurrence, was the slowest wave for L >= 2: a lone wave pays per instruction).  Distances
-                            // |p - 32768| <= 32767 because Counter::p is in [1, 65535], so their difference fits an i16 and its
-                            // sign is the "strictly farther" mask (ties keep the left leaf).
-                            u16x2 P = as_u16x2(w0), D = pk_opinion_dist(P);
-#pragma unroll
-                            for (int l = 1; l < L; l++) {
-                                const uint32_t w = q == 0 ? cur[l][k].x : q == 1 ? cur[l][k].y : q == 2 ? cur[l][k].z : cur[l][k].w;
-                                const u16x2 Q = as_u16x2(w), E = pk_opinion_dist(Q);
-                                const uint32_t mask = pk_farther_mask(D, E);                   // 0xFFFF where E > D
-                                P = as_u16x2((as_u32(Q) & mask) | (as_u32(P) & ~mask));
-                                D = __builtin_elementwise_max(D, E);
-                            }
-                            w0 = as_u32(P);
-                        }
+                        const uint32_t w0 = opinion_mix2_at(cur, k, q);
                         const uint32_t plo = w0 & 0xFFFFu, phi = w0 >> 16;
                         slot[(2 * q) * 64] = make_uint2(plo << 16, (uint32_t)__builtin_amdgcn_sbfe((int)cb[k], 7 - 2 * q, 1));
                         slot[(2 * q + 1) * 64] = make_uint2(phi << 16, (uint32_t)__builtin_amdgcn_sbfe((int)cb[k], 6 - 2 * q, 1));
@@ -570,8 +634,7 @@ __global__ void __launch_bounds__(192) k_coder_x3(Coder3Args a) {
     // -------------------------------- O-wave --------------------------------
     uint8_t *out = a.stripes + (uint64_t)(act ? b : 0u) * a.stripe_cap;
     const uint32_t cap = act ? a.stripe_cap : 0u, limit = a.acc_limit;
-    uint64_t acc = 0ull; uint32_t nb = 1u, pos = 0u;
-    bool failed = false;
+    SlotAcc o; o.init();
     uint32_t seen_x = 0;
     for (uint32_t i = 0; i < maxlen && !dead; i += 8) {
         const uint32_t need = min(i + 8u, maxlen);
@@ -586,28 +649,10 @@ __global__ void __launch_bounds__(192) k_coder_x3(Coder3Args a) {
                 for (int j = 0; j < 8; j++) t[j] = slot[j * 64];
 #pragma unroll
                 for (int j = 0; j < 8; j++) {
-                    if (__builtin_expect(nb > limit, 0)) {
-                        const uint32_t pend = trailing_ones64(acc) + 1u;
-#pragma unroll 1
-                        while (nb >= pend + 8u) {
-                            const uint8_t v = (uint8_t)(acc >> (nb - 8u));
-                            if (pos < cap) out[pos] = v;
-                            pos += 1u; nb -= 8u;
-                        }
-                        if (nb > limit) { failed = true; acc = 0ull; nb = 1u; }
-                    }
-                    const uint32_t x1v = t[j].x, s = t[j].y;   // token = (x1 after the update, shift count)
-                    acc += x1v >> 31;
-                    acc = (acc << s) | __builtin_amdgcn_ubfe(x1v, 31u - s, s);
-                    nb += s;
+                    if (__builtin_expect(o.nb > limit, 0)) o.guard(out, cap, limit);
+                    o.absorb(t[j].x, t[j].y);   // token = (x1 after the update, shift count)
                 }
-                const uint32_t lo = (uint32_t)acc;
-                const uint32_t pend = (~lo ? (uint32_t)__builtin_ctz(~lo) : 32u) + 1u;
-                if (nb >= pend + 32u) {
-                    const uint32_t wv = (uint32_t)(acc >> (nb - 32u));
-                    if (pos + 4u <= cap) { const uint32_t be = __builtin_bswap32(wv); __builtin_memcpy(out + pos, &be, 4); }
-                    pos += 4u; nb -= 32u;
-                }
+                o.move32(out, cap);
             }
         }
         __asm__ volatile("" ::: "memory");
@@ -615,19 +660,7 @@ __global__ void __launch_bounds__(192) k_coder_x3(Coder3Args a) {
     }
     if (dead) { if (lane == 0) atomicOr(&a.flags[0], 2u); return; }
     if (!act) return;
-    const uint32_t x2f = fin_x2[lane];
-    if (a.out_bits && !failed) a.out_bits[b] = 8u * pos + nb - (trailing_ones64(acc) + 1u);   // ACStats: all bits but the slot and the pending ones
-    acc += 1ull;
-    const uint32_t idx = nb & 7u;
-    if (idx) { const uint32_t k = 8u - idx; acc = (acc << k) | ((x2f << 1) >> (32u - k)); nb += k; }
-#pragma unroll 1
-    while (nb >= 8u) {
-        const uint8_t v = (uint8_t)(acc >> (nb - 8u));
-        if (pos < cap) out[pos] = v;
-        pos += 1u; nb -= 8u;
-    }
-    if (failed) { const uint32_t k = atomicAdd(&a.flags[1], 1u); a.redo[k] = b; }
-    else { a.out_len[b] = pos; if (pos > cap) atomicOr(&a.flags[0], 1u); }
+    o.finish(a, b, fin_x2[lane], out, cap, a.out_bits != nullptr);
 }
 
 }  // namespace w3

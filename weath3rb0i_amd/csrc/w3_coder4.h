@@ -30,6 +30,13 @@
 // The OUTPUT wave checks its accumulator once per input byte (sum of the byte's shift counts) instead of once per step.
 // LDS: operands 16 B and tokens 8 B per step and lane -> 12 KiB per ring byte, 144 KiB for the rings of 3 chunks of 4 bytes
 // (with two chunks the three waves ran in lockstep and every hand-off latency showed: 21.7 ms instead of 15.8 for the X-wave alone).
+//
+// This file owns the asm loops (W3_X4_*, W3_O4_*), the step in C, k_coder_x4<L> itself (its ring of 3 chunks of 4 bytes, its
+// M-wave schedule, its run_end rule) and the C++ that k_coder_x5 shares with it around the loops: the M-wave's chunk loads
+// and operand baking (x4_load, x4_bake) and the ragged-chunk C path of the X-wave (x4_ragged_x).  The O-wave's C paths exist
+// twice: x4_byte_c / x4_ragged_o over SlotAcc serve k_coder_x5, while k_coder_x4's O-wave keeps byte_c / finish in its own body,
+// because with the shared form its kernel measured slower than the margin allows (profiles/coder_shared/README.md).
+// From w3_coder.h it takes the lane setup (coder_lanes) and the mix (opinion_mix2); k_coder_x5 also the accumulator (SlotAcc).
 #pragma once
 #include "w3_coder.h"
 
@@ -42,10 +49,6 @@ namespace w3 {
 #define W3_X4_SYNC_X 4
 #define W3_X4_SYNC_O 8
 #define W3_X4_SYNC_ABORT 12
-
-#ifndef W3_X4_EXP
-#define W3_X4_EXP 0                   // timing experiments (results WRONG): 1 = O-wave absorbs nothing, 2 = M-wave writes constant operands, 3 = both
-#endif
 
 #define W3S_(x) #x
 #define W3S(x) W3S_(x)
@@ -306,117 +309,160 @@ typedef uint32_t w3_u32x3 __attribute__((ext_vector_type(3)));
 typedef uint32_t w3_u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) uint8_t w3_lds_u8;
 
+// ---------------------------------------------------------------------------------------------------------------------
+// What k_coder_x4 and k_coder_x5 share around their asm loops, parameterised by the chunk length CH, the ring depth RING
+// (both in input bytes) and the ring position POS of an input byte (x4_ring_pos, x5_ring_pos).
+// ---------------------------------------------------------------------------------------------------------------------
+struct X4Lds {   // a workgroup's rings and progress words (bytes)
+    X4Op *opq;   // M -> X: (z, z, q) per step           [ring byte][bit][lane]
+    uint2 *tok;  // X -> O: (x1n raw, s) per step        [ring byte][bit][lane]
+    uint2 *fin;  // X -> O: (x1 raw, d) after the lane's last step
+    volatile uint32_t *m_prod, *x_done, *o_cons, *abortf;
+};
+
+// M-wave: the loads of chunk [i0, i0 + CH) of the lane's block, issued chunks ahead of their use and therefore unconditional
+// (hipcc waits vmcnt(0) after a load it has to branch around).  Positions past the end of the block are clamped to its last
+// byte: the X-wave codes them like any others and the O-wave ignores the tokens.
+template <int L, uint32_t CH>
+struct X4Buf { uint4 p[L][CH]; uint32_t bytes, sh; };
+struct X4Clamp {   // computed once per M-wave, not per load
+    uint32_t last;       // the block's last byte (0 for an empty lane)
+    uint64_t blk_end4;   // input offset of the block's last four bytes; n >= 4: stays inside the input
+};
+__device__ __forceinline__ X4Clamp x4_clamp(const CoderLanes &c) {
+    return X4Clamp{(c.act && c.len) ? c.len - 1u : 0u, c.off + (uint64_t)c.len >= 4u ? c.off + (uint64_t)c.len - 4u : 0ull};
+}
+template <int L, uint32_t CH>
+__device__ __forceinline__ void x4_load(X4Buf<L, CH> &bf, const Coder3Args &a, const CoderLanes &c, const X4Clamp &cl, uint32_t i0) {
+    static_assert(CH <= 4, "the byte fetch below is one dword");
+    const uint32_t last = cl.last;
+    const uint64_t blk_end4 = cl.blk_end4;
+    const uint64_t want = c.off + i0, at = want < blk_end4 ? want : blk_end4;
+    uint32_t w; __builtin_memcpy(&w, a.in + at, 4);
+    bf.bytes = w; bf.sh = (uint32_t)(want - at) * 8u;
+#pragma unroll
+    for (uint32_t k = 0; k < CH; k++) {
+        const uint32_t ic = min(i0 + k, last);
+#pragma unroll
+        for (int l = 0; l < L; l++) bf.p[l][k] = a.src[l][c.off + ic];
+    }
+}
+// the chunk's input bytes complemented, byte k at bits 8k .. 8k+7: z = ~0 when the coded bit is 0
+template <int L, uint32_t CH>
+__device__ __forceinline__ uint32_t x4_nbytes(const X4Buf<L, CH> &bf) { return ~(bf.sh < 32u ? bf.bytes >> bf.sh : 0u); }
+
+// The operand pairs (z, q) of the two steps of dword q of byte k, from the mixed dword w0: the M-wave bakes the coded
+// bit into them, q = bit ? p32 : 2^32 - p32 (header comment).
+struct X4OpPair { uint32_t z0, q0, z1, q1; };
+__device__ __forceinline__ X4OpPair x4_bake(uint32_t w0, uint32_t nbytes4, uint32_t k, int q) {
+    X4OpPair o;
+    o.z0 = (uint32_t)__builtin_amdgcn_sbfe((int)nbytes4, 8 * k + 7 - 2 * q, 1);
+    o.z1 = (uint32_t)__builtin_amdgcn_sbfe((int)nbytes4, 8 * k + 6 - 2 * q, 1);
+    o.q0 = ((w0 << 16) ^ o.z0) - o.z0;
+    o.q1 = ((w0 & 0xFFFF0000u) ^ o.z1) - o.z1;
+    return o;
+}
+
+// X-wave: a chunk outside the asm loop (one in which some lane's block ends before the chunk does, or the block's last,
+// partial one) with the step in C.  Publishes x_done; the caller advances i.
+template <uint32_t CH, uint32_t RING, uint32_t (*POS)(uint32_t)>
+__device__ __forceinline__ void x4_ragged_x(const X4Lds &r, const CoderLanes &c, uint32_t i, uint32_t &x1, uint32_t &d, uint32_t &seen_m, uint32_t &seen_o,
+                                            bool &dead) {
+    const uint32_t need = min(i + CH, c.maxlen);
+    if (seen_m < need) { seen_m = __builtin_amdgcn_readfirstlane(spin_until_ge(r.m_prod, need, r.abortf, dead)); if (dead) return; }
+    if (seen_o + RING < i + CH) { seen_o = __builtin_amdgcn_readfirstlane(spin_until_ge(r.o_cons, i + CH - RING, r.abortf, dead)); if (dead) return; }
+    for (uint32_t k = 0; k < CH && i + k < c.maxlen; k++) {
+        const size_t ring = ((size_t)POS(i + k) * 8u) * 64u + c.lane;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const X4Op op = r.opq[ring + j * 64];
+            r.tok[ring + j * 64] = x4_step_c(x1, d, op.z0, op.q);
+        }
+        if (i + k + 1u == c.len) r.fin[c.lane] = make_uint2(x1, d);
+    }
+    __asm__ volatile("" ::: "memory");
+    lds_store_u32(r.x_done, need);
+}
+
+// O-wave: one byte's eight tokens (at slot, stride 64) the careful way: per-step accumulator guard, hand-back to k_coder when
+// a pending run outgrows it.  xr: the raw x1 the next token grew from (its bit 31 is all that matters).
+__device__ __forceinline__ void x4_byte_c(SlotAcc &o, uint32_t &xr, const uint2 *slot, uint8_t *out, uint32_t cap, uint32_t limit) {
+#pragma unroll 1
+    for (int j = 0; j < 8; j++) {
+        const uint2 t = slot[j * 64];
+        if (o.nb > limit) o.guard(out, cap, limit);
+        const uint32_t xt = t.x ^ (xr & 0x80000000u), sj = t.y;   // the TRUE low end
+        xr = t.x << sj;
+        o.absorb(xt, sj);
+    }
+    o.move32(out, cap);
+}
+// the final x2 from fin = (x1 raw, d)
+__device__ __forceinline__ uint32_t x4_final_x2(uint2 f) { return ((f.x & 0x7FFFFFFFu) + f.y) | 0x80000000u; }
+
+// O-wave: a chunk outside the asm loop, byte by byte; finish() at the end of the lane's block.  Publishes o_cons; the caller advances i.
+template <uint32_t CH, class ByteC, class Finish>
+__device__ __forceinline__ void x4_ragged_o(const X4Lds &r, const CoderLanes &c, uint32_t i, uint32_t &seen_x, bool &dead, ByteC byte_c, Finish finish) {
+    const uint32_t need = min(i + CH, c.maxlen);
+    if (seen_x < need) { seen_x = __builtin_amdgcn_readfirstlane(spin_until_ge<1>(r.x_done, need, r.abortf, dead)); if (dead) return; }
+    __asm__ volatile("" ::: "memory");
+    for (uint32_t k = 0; i + k < need; k++) {
+        byte_c(i + k);
+        if (i + k + 1u == c.len) finish();
+    }
+    __asm__ volatile("" ::: "memory");
+    lds_store_u32(r.o_cons, need);
+}
+
 // L > 1 leaf streams: the mix makes the M-wave's chunk longer than the X-wave's, so TWO M-waves take alternate chunks
 // (workgroup = M0, M1, X, O: one wave per SIMD of the CU); with a single stream one M-wave keeps up (51 vs 72 cycles per step).
 template <int L>
 __global__ void __launch_bounds__(L > 1 ? 256 : 192) k_coder_x4(Coder3Args a) {
     constexpr uint32_t NM = L > 1 ? 2u : 1u;   // M-waves
-    __shared__ X4Op opq[W3_X4_RING * 8u * 64u];    // M -> X: (z, z, q) per step           [ring byte][bit][lane]
-    __shared__ uint2 tok[W3_X4_RING * 8u * 64u];   // X -> O: (x1n raw, s) per step        [ring byte][bit][lane]
-    __shared__ uint2 fin[64];                      // X -> O: (x1 raw, d) after the lane's last step
+    __shared__ X4Op opq[W3_X4_RING * 8u * 64u];
+    __shared__ uint2 tok[W3_X4_RING * 8u * 64u];
+    __shared__ uint2 fin[64];
     __shared__ uint32_t sync_w[8];                 // [0] M produced, [1] X done, [2] O consumed, [3] abort   (bytes)
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const uint32_t b = blockIdx.x * 64u + lane;
-    const bool act = b < a.nblocks;
-    const uint64_t off = (uint64_t)(act ? b : 0u) * a.block_size;
-    const uint32_t len = act ? (uint32_t)((a.n - off) < a.block_size ? (a.n - off) : a.block_size) : 0u;
-    uint32_t maxlen = len, lenB = len ? len : 0xFFFFFFFFu;
-#pragma unroll
-    for (int dd = 32; dd >= 1; dd >>= 1) {
-        maxlen = max(maxlen, (uint32_t)__shfl_xor((int)maxlen, dd, 64));
-        lenB = min(lenB, (uint32_t)__shfl_xor((int)lenB, dd, 64));
-    }
-    maxlen = __builtin_amdgcn_readfirstlane(maxlen);
-    lenB = __builtin_amdgcn_readfirstlane(lenB);     // the shorter of the (at most two) block lengths in this wave; 0 < lenB <= maxlen
-    if (threadIdx.x < 8) sync_w[threadIdx.x] = 0u;
-    __syncthreads();
-    volatile uint32_t *m_prod = &sync_w[0], *x_done = &sync_w[1], *o_cons = &sync_w[2], *abortf = &sync_w[3];
+    const CoderLanes c = coder_lanes<true>(a, sync_w, 8);
+    const uint32_t wave = c.wave, lane = c.lane, b = c.b, len = c.len, maxlen = c.maxlen, lenB = c.lenB;
+    const X4Lds r{opq, tok, fin, &sync_w[0], &sync_w[1], &sync_w[2], &sync_w[3]};
     bool dead = false;
     constexpr uint32_t CH = W3_X4_CH, RING = W3_X4_RING;
 
     if (wave < NM) {
         // ------------------------------ M-wave(s) ------------------------------
-        // Operands are fetched several chunks ahead with unconditional loads (hipcc waits vmcnt(0) after a load it has to branch
-        // around): a lane streams its own block, 64 B of probabilities per chunk, so every second chunk opens a new line
-        // with a full memory latency, and a chunk is coded in under a microsecond.  Positions past the end of a lane's block
-        // are clamped to its last byte: the X-wave codes them like any others and the O-wave ignores the tokens.
-        const uint32_t last = (act && len) ? len - 1u : 0u;
+        // Operands are fetched several chunks ahead (x4_load): a lane streams its own block, 64 B of probabilities per chunk, so
+        // every second chunk opens a new line with a full memory latency, and a chunk is coded in under a microsecond.
         const uint32_t ops_lane = (uint32_t)(uintptr_t)(w3_lds_u8 *)(opq + lane);
-        // the chunk's CH input bytes as ONE unaligned dword load at min(i, len - CH) (never past the block's end); shifted into place after
-        const uint64_t blk_end4 = off + (uint64_t)len >= CH ? off + (uint64_t)len - CH : 0ull;   // n >= 4: stays inside the input
-        static_assert(CH == 4, "the byte fetch below is one dword");
-        struct Buf { uint4 p[L][CH]; uint32_t bytes, sh; };
-        auto load = [&](Buf &bf, uint32_t i0) {
-#if W3_X4_EXP & 4
-            bf.bytes = i0 * 2654435761u; bf.sh = 0;
-            for (uint32_t k = 0; k < CH; k++) for (int l = 0; l < L; l++) bf.p[l][k] = make_uint4(i0 + 0x12345u, i0 * 77u + 0x4567u, i0 + 0x333u, i0 + 0x9999u);
-            return;
-#endif
-            const uint64_t want = off + i0, at = want < blk_end4 ? want : blk_end4;
-            uint32_t w; __builtin_memcpy(&w, a.in + at, 4);
-            bf.bytes = w; bf.sh = (uint32_t)(want - at) * 8u;
-#pragma unroll
-            for (uint32_t k = 0; k < CH; k++) {
-                const uint32_t ic = min(i0 + k, last);
-#pragma unroll
-                for (int l = 0; l < L; l++) bf.p[l][k] = a.src[l][off + ic];
-            }
-        };
+        typedef X4Buf<L, CH> Buf;
+        const X4Clamp cl = x4_clamp(c);
+        auto load = [&](Buf &bf, uint32_t i0) { x4_load(bf, a, c, cl, i0); };
         uint32_t seen = 0;   // last value read from x_done
         auto produce = [&](const Buf &bf, uint32_t i) {
-#if !(W3_X4_EXP & 16)
             if (i >= RING && seen + RING < i + CH) {    // this chunk's slots still hold bytes [i - RING, i - RING + CH): they must have been coded
-                seen = spin_until_ge<1>(x_done, i + CH - RING, abortf, dead);
+                seen = spin_until_ge<1>(r.x_done, i + CH - RING, r.abortf, dead);
                 if (dead) return;
             }
-#endif
-            const uint32_t nbytes4 = ~(bf.sh < 32u ? bf.bytes >> bf.sh : 0u);   // complemented: z = ~0 when the coded bit is 0; byte k at bits 8k..8k+7
+            const uint32_t nbytes4 = x4_nbytes(bf);
             const uint32_t slot = ops_lane + (x4_ring_pos(i) << 13);
-#if W3_X4_EXP & 2
-            if (i < RING) {
-                w3_u32x3 o0; o0.x = 0u; o0.y = 0u; o0.z = 0x80000000u;
-#pragma unroll
-                for (uint32_t k = 0; k < CH * 8; k++) asm volatile("ds_write_b96 %0, %1 offset:%2" : : "v"(slot), "v"(o0), "n"(k * 1024) : "memory");
-            }
-#else
 #pragma unroll
             for (uint32_t k = 0; k < CH; k++) {
 #pragma unroll
                 for (int q = 0; q < 4; q++) {   // one dword = two steps
-                    uint32_t w0 = q == 0 ? bf.p[0][k].x : q == 1 ? bf.p[0][k].y : q == 2 ? bf.p[0][k].z : bf.p[0][k].w;
-                    if constexpr (L > 1) {   // OpinionMixer2, both steps of the dword at once (see k_coder_x3)
-                        u16x2 P = as_u16x2(w0), D = pk_opinion_dist(P);
-#pragma unroll
-                        for (int l = 1; l < L; l++) {
-                            const uint32_t w = q == 0 ? bf.p[l][k].x : q == 1 ? bf.p[l][k].y : q == 2 ? bf.p[l][k].z : bf.p[l][k].w;
-                            const u16x2 Q = as_u16x2(w), E = pk_opinion_dist(Q);
-                            const uint32_t mask = pk_farther_mask(D, E);                   // 0xFFFF where E > D
-                            P = as_u16x2((as_u32(Q) & mask) | (as_u32(P) & ~mask));
-                            D = __builtin_elementwise_max(D, E);
-                        }
-                        w0 = as_u32(P);
-                    }
-                    const uint32_t z0 = (uint32_t)__builtin_amdgcn_sbfe((int)nbytes4, 8 * k + 7 - 2 * q, 1);
-                    const uint32_t z1 = (uint32_t)__builtin_amdgcn_sbfe((int)nbytes4, 8 * k + 6 - 2 * q, 1);
+                    const X4OpPair op = x4_bake(opinion_mix2_at(bf.p, k, q), nbytes4, k, q);
                     w3_u32x3 o0, o1;
-                    o0.x = z0; o0.y = z0; o0.z = ((w0 << 16) ^ z0) - z0;            // bit ? p32 : 2^32 - p32
-                    o1.x = z1; o1.y = z1; o1.z = ((w0 & 0xFFFF0000u) ^ z1) - z1;
-#if W3_X4_EXP & 8
-                    asm volatile("ds_write_b32 %0, %1 offset:%2" : : "v"(slot), "v"(o0.z ^ o0.x), "n"((k * 8 + 2 * q) * 1024) : "memory");
-                    asm volatile("ds_write_b32 %0, %1 offset:%2" : : "v"(slot), "v"(o1.z ^ o1.x), "n"((k * 8 + 2 * q + 1) * 1024) : "memory");
-#else
+                    o0.x = op.z0; o0.y = op.z0; o0.z = op.q0;
+                    o1.x = op.z1; o1.y = op.z1; o1.z = op.q1;
                     asm volatile("ds_write_b96 %0, %1 offset:%2" : : "v"(slot), "v"(o0), "n"((k * 8 + 2 * q) * 1024) : "memory");
                     asm volatile("ds_write_b96 %0, %1 offset:%2" : : "v"(slot), "v"(o1), "n"((k * 8 + 2 * q + 1) * 1024) : "memory");
-#endif
                 }
             }
-#endif
             __asm__ volatile("" ::: "memory");
             if (NM > 1u && i > 0u) {   // chunks are published in order: the other M-wave's chunk before this one
-                (void)spin_until_ge<1>(m_prod, i, abortf, dead);
+                (void)spin_until_ge<1>(r.m_prod, i, r.abortf, dead);
                 if (dead) return;
             }
-            lds_store_u32(m_prod, min(i + CH, maxlen));   // after the operands: the LDS executes one wave's operations in order
+            lds_store_u32(r.m_prod, min(i + CH, maxlen));   // after the operands: the LDS executes one wave's operations in order
         };
         // four buffers in flight per wave: a chunk's loads are issued three of this wave's chunk-times (>= 3 us) before its
         // operands are built.  M-wave w takes the chunks w, w + NM, w + 2 NM, ...
@@ -440,23 +486,24 @@ __global__ void __launch_bounds__(L > 1 ? 256 : 192) k_coder_x4(Coder3Args a) {
         return;
     }
 
+    const uint32_t tok_lane = (uint32_t)(uintptr_t)(w3_lds_u8 *)(tok + lane);
+    const uint32_t sync_addr = (uint32_t)(uintptr_t)(w3_lds_u8 *)sync_w;
+    const uint32_t full_end = maxlen / CH * CH;
+    // [i, run_end(i)): full chunks in which no lane's block ends except at run_end itself
+    auto asm_end = [&](uint32_t i) -> uint32_t {
+        uint32_t run_end = full_end;
+        if (lenB > i) run_end = min(run_end, lenB / CH * CH);   // the shorter lanes end at (or inside the chunk after) this boundary
+        return run_end;
+    };
+
     if (wave == NM) {
         // ------------------------------ X-wave ------------------------------
-#if W3_X4_EXP & 64
-        return;
-#endif
         __builtin_amdgcn_s_setprio(3);
         const uint32_t ops_lane = (uint32_t)(uintptr_t)(w3_lds_u8 *)(opq + lane);
-        const uint32_t tok_lane = (uint32_t)(uintptr_t)(w3_lds_u8 *)(tok + lane);
-        const uint32_t sync_addr = (uint32_t)(uintptr_t)(w3_lds_u8 *)sync_w;
         uint32_t x1 = 0u, d = 0xFFFFFFFFu;
         uint32_t seen_m = 0, seen_o = 0, i = 0;
-        const uint32_t full_end = maxlen / CH * CH;
-        const bool raggedB = lenB % CH != 0u;
         while (i < maxlen && !dead) {
-            // [i, run_end): full chunks in which no lane's block ends except at run_end itself
-            uint32_t run_end = full_end;
-            if (lenB > i) run_end = min(run_end, lenB / CH * CH);   // the shorter lanes end at (or inside the chunk after) this boundary
+            const uint32_t run_end = asm_end(i);
             if (run_end > i) {
                 uint32_t status = 0, slot = (i / CH) % W3_X4_NCH;
                 asm volatile(W3_X4_LOOP
@@ -466,31 +513,19 @@ __global__ void __launch_bounds__(L > 1 ? 256 : 192) k_coder_x4(Coder3Args a) {
                 if (status) { dead = true; break; }
                 if (len == run_end) fin[lane] = make_uint2(x1, d);
                 __asm__ volatile("" ::: "memory");
-                lds_store_u32(x_done, run_end);   // (the asm loop leaves the last chunk's hand-off to us: fin goes first)
+                lds_store_u32(r.x_done, run_end);   // (the asm loop leaves the last chunk's hand-off to us: fin goes first)
             } else {
-                // a chunk in which some lane's block ends before the chunk does (or the block's last, partial chunk)
-                const uint32_t need = min(i + CH, maxlen);
-                if (seen_m < need) { seen_m = __builtin_amdgcn_readfirstlane(spin_until_ge(m_prod, need, abortf, dead)); if (dead) break; }
-                if (seen_o + RING < i + CH) { seen_o = __builtin_amdgcn_readfirstlane(spin_until_ge(o_cons, i + CH - RING, abortf, dead)); if (dead) break; }
-                for (uint32_t k = 0; k < CH && i + k < maxlen; k++) {
-                    const size_t ring = ((size_t)x4_ring_pos(i + k) * 8u) * 64u + lane;
-#pragma unroll
-                    for (int j = 0; j < 8; j++) {
-                        const X4Op op = opq[ring + j * 64];
-                        tok[ring + j * 64] = x4_step_c(x1, d, op.z0, op.q);
-                    }
-                    if (i + k + 1u == len) fin[lane] = make_uint2(x1, d);
-                }
-                __asm__ volatile("" ::: "memory");
-                lds_store_u32(x_done, need);
+                x4_ragged_x<CH, RING, x4_ring_pos>(r, c, i, x1, d, seen_m, seen_o, dead);
+                if (dead) break;
                 i += CH;
             }
-            (void)raggedB;
         }
         return;
     }
 
     // -------------------------------- O-wave --------------------------------
+    const bool act = c.act;
+    volatile uint32_t *x_done = r.x_done, *o_cons = r.o_cons, *abortf = r.abortf;
     uint8_t *out = a.stripes + (uint64_t)(act ? b : 0u) * a.stripe_cap;
     uint32_t cap = act ? a.stripe_cap : 0u;
     const uint32_t limit = a.acc_limit, fast_fill = a.acc_limit + 18u;   // 64 for the default limit of 46
@@ -498,11 +533,8 @@ __global__ void __launch_bounds__(L > 1 ? 256 : 192) k_coder_x4(Coder3Args a) {
     uint32_t xr = 0u;   // the raw x1 the next token grew from (its bit 31 is all that matters)
     uint32_t failed = 0u;
     uint32_t seen_x = 0, i = 0;
-    const uint32_t tok_lane = (uint32_t)(uintptr_t)(w3_lds_u8 *)(tok + lane);
-    const uint32_t sync_addr = (uint32_t)(uintptr_t)(w3_lds_u8 *)sync_w;
     const uint8_t *wg_base = a.stripes + (uint64_t)blockIdx.x * 64u * a.stripe_cap;   // stripe of this workgroup's first block
     const uint32_t voff = lane * a.stripe_cap;                                       // (64 stripes: below 2^32 for every block size)
-    const uint32_t full_end = maxlen / CH * CH;
 
     // one byte's eight tokens the careful way: per-step accumulator guard, hand-back to k_coder when a pending run outgrows it
     auto byte_c = [&](uint32_t j0) {
@@ -559,18 +591,6 @@ __global__ void __launch_bounds__(L > 1 ? 256 : 192) k_coder_x4(Coder3Args a) {
     while (i < maxlen && !dead) {
         uint32_t run_end = full_end;
         if (lenB > i) run_end = min(run_end, lenB / CH * CH);
-#if W3_X4_EXP & 1
-        {
-            const uint32_t need = min(i + CH, maxlen);
-#if !(W3_X4_EXP & 32)
-            if (seen_x < need) { seen_x = __builtin_amdgcn_readfirstlane(spin_until_ge<1>(x_done, need, abortf, dead)); if (dead) break; }
-#endif
-            if (need == maxlen && act) a.out_len[b] = 0u;
-            lds_store_u32(o_cons, need);
-            i += CH;
-            continue;
-        }
-#endif
         if (run_end > i) {
             uint32_t status = 0, slot = (i / CH) % W3_X4_NCH, kbail = 0;
             uint32_t alo = (uint32_t)acc, ahi = (uint32_t)(acc >> 32);

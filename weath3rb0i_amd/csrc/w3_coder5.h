@@ -18,6 +18,10 @@
 //     1.5 chunk-times only: the wait must not be followed by the mix), and keeps 8 / 6 / 4 two-byte buffers of loads in
 //     flight (L = 1 / 2 / >= 3).  L > 1: two M-waves take alternate chunks and publish in order.
 // Tokens, operands, the O-wave's accumulator, the hand-back to the robust coder and the counting sink are k_coder_x4's.
+//
+// This file owns the one-revolution asm loops (W3_X5_*, W3_O5_*) and k_coder_x5<L> itself: its ring, its M-wave schedule and
+// its asm_end rule.  The chunk loads, the operand baking and the ragged-chunk C paths are w3_coder4.h's shared functions with
+// CH = 2, RING = 6 and x5_ring_pos; lane setup, mix and accumulator are w3_coder.h's.
 #pragma once
 #include "w3_coder4.h"
 
@@ -154,30 +158,20 @@ namespace w3 {
     "s_waitcnt lgkmcnt(0)\n"                                                                         \
     "v_mov_b32 %[alo], v84\n v_mov_b32 %[ahi], v85\n v_mov_b32 %[nb], v86\n v_mov_b32 %[pos], v87\n v_mov_b32 %[xr], v88\n"
 
+// ring position (in bytes) of input byte j: the ring never moves
+__device__ __forceinline__ uint32_t x5_ring_pos(uint32_t j) { return j % W3_X5_RING; }
+
 template <int L>
 __global__ void __launch_bounds__(L > 1 ? 256 : 192) k_coder_x5(Coder3Args a) {
     constexpr uint32_t NM = L > 1 ? 2u : 1u;   // M-waves
     constexpr uint32_t CH = W3_X5_CH, RING = W3_X5_RING;
-    __shared__ X4Op opq[RING * 8u * 64u];    // M -> X: (z, z, q) per step           [ring byte][bit][lane]
-    __shared__ uint2 tok[RING * 8u * 64u];   // X -> O: (x1n raw, s) per step        [ring byte][bit][lane]
-    __shared__ uint2 fin[64];                // X -> O: (x1 raw, d) after the lane's last step
+    __shared__ X4Op opq[RING * 8u * 64u];
+    __shared__ uint2 tok[RING * 8u * 64u];
+    __shared__ uint2 fin[64];
     __shared__ uint32_t sync_w[8];           // [0] M produced, [1] X done, [2] O consumed, [3] abort   (bytes)
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const uint32_t b = blockIdx.x * 64u + lane;
-    const bool act = b < a.nblocks;
-    const uint64_t off = (uint64_t)(act ? b : 0u) * a.block_size;
-    const uint32_t len = act ? (uint32_t)((a.n - off) < a.block_size ? (a.n - off) : a.block_size) : 0u;
-    uint32_t maxlen = len, lenB = len ? len : 0xFFFFFFFFu;
-#pragma unroll
-    for (int dd = 32; dd >= 1; dd >>= 1) {
-        maxlen = max(maxlen, (uint32_t)__shfl_xor((int)maxlen, dd, 64));
-        lenB = min(lenB, (uint32_t)__shfl_xor((int)lenB, dd, 64));
-    }
-    maxlen = __builtin_amdgcn_readfirstlane(maxlen);
-    lenB = __builtin_amdgcn_readfirstlane(lenB);     // the shorter of the (at most two) block lengths in this wave; 0 < lenB <= maxlen
-    if (threadIdx.x < 8) sync_w[threadIdx.x] = 0u;
-    __syncthreads();
-    volatile uint32_t *m_prod = &sync_w[0], *x_done = &sync_w[1], *o_cons = &sync_w[2], *abortf = &sync_w[3];
+    const CoderLanes c = coder_lanes<true>(a, sync_w, 8);
+    const uint32_t wave = c.wave, lane = c.lane, b = c.b, len = c.len, maxlen = c.maxlen, lenB = c.lenB;
+    const X4Lds r{opq, tok, fin, &sync_w[0], &sync_w[1], &sync_w[2], &sync_w[3]};
     bool dead = false;
     // [i, asm_end(i)): whole revolutions in which no lane's block ends except at the end of the last one; i must start a revolution
     auto asm_end = [&](uint32_t i) -> uint32_t {
@@ -189,60 +183,32 @@ __global__ void __launch_bounds__(L > 1 ? 256 : 192) k_coder_x5(Coder3Args a) {
     if (wave != NM && a.prio_mo) __builtin_amdgcn_s_setprio(2);
     if (wave < NM) {
         // ------------------------------ M-wave(s) ------------------------------
-        // Loads are issued NB chunks of this wave ahead (unconditional, clamped: hipcc waits vmcnt(0) after a load it has to branch
-        // around).  Positions past the end of a lane's block are clamped to its last byte: the X-wave codes them like any
-        // others and the O-wave ignores the tokens.
-        const uint32_t last = (act && len) ? len - 1u : 0u;
+        // Loads are issued NB chunks of this wave ahead (x4_load).
         const uint32_t ops_lane = (uint32_t)(uintptr_t)(w3_lds_u8 *)(opq + lane);
-        const uint64_t blk_end4 = off + (uint64_t)len >= 4u ? off + (uint64_t)len - 4u : 0ull;   // n >= 4: stays inside the input
-        struct Buf { uint4 p[L][CH]; uint32_t bytes, sh; };
-        auto load = [&](Buf &bf, uint32_t i0) {
-            // the chunk's input bytes as ONE unaligned dword load at min(i0, len - 4) (never past the block's end); shifted into place after
-            const uint64_t want = off + i0, at = want < blk_end4 ? want : blk_end4;
-            uint32_t w; __builtin_memcpy(&w, a.in + at, 4);
-            bf.bytes = w; bf.sh = (uint32_t)(want - at) * 8u;
-#pragma unroll
-            for (uint32_t k = 0; k < CH; k++) {
-                const uint32_t ic = min(i0 + k, last);
-#pragma unroll
-                for (int l = 0; l < L; l++) bf.p[l][k] = a.src[l][off + ic];
-            }
-        };
+        typedef X4Buf<L, CH> Buf;
+        const X4Clamp cl = x4_clamp(c);
+        auto load = [&](Buf &bf, uint32_t i0) { x4_load(bf, a, c, cl, i0); };
         uint32_t seen = 0;   // last value read from x_done
         auto produce = [&](const Buf &bf, uint32_t i) {
             // 1. the chunk's 16 operands, in registers
-            const uint32_t nbytes4 = ~(bf.sh < 32u ? bf.bytes >> bf.sh : 0u);   // complemented: z = ~0 when the coded bit is 0; byte k at bits 8k..8k+7
+            const uint32_t nbytes4 = x4_nbytes(bf);
             uint32_t qv[CH * 8], zv[CH * 8];
 #pragma unroll
             for (uint32_t k = 0; k < CH; k++) {
 #pragma unroll
                 for (int q = 0; q < 4; q++) {   // one dword = two steps
-                    uint32_t w0 = q == 0 ? bf.p[0][k].x : q == 1 ? bf.p[0][k].y : q == 2 ? bf.p[0][k].z : bf.p[0][k].w;
-                    if constexpr (L > 1) {   // OpinionMixer2, both steps of the dword at once (see k_coder_x3)
-                        u16x2 P = as_u16x2(w0), D = pk_opinion_dist(P);
-#pragma unroll
-                        for (int l = 1; l < L; l++) {
-                            const uint32_t w = q == 0 ? bf.p[l][k].x : q == 1 ? bf.p[l][k].y : q == 2 ? bf.p[l][k].z : bf.p[l][k].w;
-                            const u16x2 Q = as_u16x2(w), E = pk_opinion_dist(Q);
-                            const uint32_t mask = pk_farther_mask(D, E);                   // 0xFFFF where E > D
-                            P = as_u16x2((as_u32(Q) & mask) | (as_u32(P) & ~mask));
-                            D = __builtin_elementwise_max(D, E);
-                        }
-                        w0 = as_u32(P);
-                    }
-                    const uint32_t z0 = (uint32_t)__builtin_amdgcn_sbfe((int)nbytes4, 8 * k + 7 - 2 * q, 1);
-                    const uint32_t z1 = (uint32_t)__builtin_amdgcn_sbfe((int)nbytes4, 8 * k + 6 - 2 * q, 1);
-                    zv[k * 8 + 2 * q] = z0; qv[k * 8 + 2 * q] = ((w0 << 16) ^ z0) - z0;                 // bit ? p32 : 2^32 - p32
-                    zv[k * 8 + 2 * q + 1] = z1; qv[k * 8 + 2 * q + 1] = ((w0 & 0xFFFF0000u) ^ z1) - z1;
+                    const X4OpPair op = x4_bake(opinion_mix2_at(bf.p, k, q), nbytes4, k, q);
+                    zv[k * 8 + 2 * q] = op.z0; qv[k * 8 + 2 * q] = op.q0;
+                    zv[k * 8 + 2 * q + 1] = op.z1; qv[k * 8 + 2 * q + 1] = op.q1;
                 }
             }
             // 2. the chunk's ring slots still hold bytes [i - RING, i - RING + CH): they must have been coded
             if (i >= RING && seen + RING < i + CH) {
-                seen = spin_until_ge<1>(x_done, i + CH - RING, abortf, dead);
+                seen = spin_until_ge<1>(r.x_done, i + CH - RING, r.abortf, dead);
                 if (dead) return;
             }
             // 3. sixteen ds_write_b96
-            const uint32_t slot = ops_lane + ((i % RING) << 13);
+            const uint32_t slot = ops_lane + (x5_ring_pos(i) << 13);
 #pragma unroll
             for (uint32_t e = 0; e < CH * 8; e++) {
                 w3_u32x3 o; o.x = zv[e]; o.y = zv[e]; o.z = qv[e];
@@ -250,10 +216,10 @@ __global__ void __launch_bounds__(L > 1 ? 256 : 192) k_coder_x5(Coder3Args a) {
             }
             __asm__ volatile("" ::: "memory");
             if (NM > 1u && i > 0u) {   // chunks are published in order: the other M-wave's chunk before this one
-                (void)spin_until_ge<1>(m_prod, i, abortf, dead);
+                (void)spin_until_ge<1>(r.m_prod, i, r.abortf, dead);
                 if (dead) return;
             }
-            lds_store_u32(m_prod, min(i + CH, maxlen));   // after the operands: the LDS executes one wave's operations in order
+            lds_store_u32(r.m_prod, min(i + CH, maxlen));   // after the operands: the LDS executes one wave's operations in order
         };
         constexpr uint32_t NB = L == 1 ? W3_X5_NB1 : L == 2 ? 6u : 4u;   // chunk buffers in flight per wave
         constexpr uint32_t ST = NM * CH;                          // bytes between two chunks of one M-wave
@@ -272,12 +238,12 @@ __global__ void __launch_bounds__(L > 1 ? 256 : 192) k_coder_x5(Coder3Args a) {
         return;
     }
 
+    const uint32_t tok_lane = (uint32_t)(uintptr_t)(w3_lds_u8 *)(tok + lane);
+    const uint32_t sync_addr = (uint32_t)(uintptr_t)(w3_lds_u8 *)sync_w;
     if (wave == NM) {
         // ------------------------------ X-wave ------------------------------
         __builtin_amdgcn_s_setprio(3);
         const uint32_t ops_lane = (uint32_t)(uintptr_t)(w3_lds_u8 *)(opq + lane);
-        const uint32_t tok_lane = (uint32_t)(uintptr_t)(w3_lds_u8 *)(tok + lane);
-        const uint32_t sync_addr = (uint32_t)(uintptr_t)(w3_lds_u8 *)sync_w;
         uint32_t x1 = 0u, d = 0xFFFFFFFFu;
         uint32_t seen_m = 0, seen_o = 0, i = 0;
         while (i < maxlen && !dead) {
@@ -291,23 +257,10 @@ __global__ void __launch_bounds__(L > 1 ? 256 : 192) k_coder_x5(Coder3Args a) {
                 if (status) { dead = true; break; }
                 if (len == run_end) fin[lane] = make_uint2(x1, d);
                 __asm__ volatile("" ::: "memory");
-                lds_store_u32(x_done, run_end);   // (the asm loop leaves the last chunk's hand-off to us: fin goes first)
-            } else {
-                // a chunk outside a whole revolution: the block's tail, or one in which some lane's block ends
-                const uint32_t need = min(i + CH, maxlen);
-                if (seen_m < need) { seen_m = __builtin_amdgcn_readfirstlane(spin_until_ge(m_prod, need, abortf, dead)); if (dead) break; }
-                if (seen_o + RING < i + CH) { seen_o = __builtin_amdgcn_readfirstlane(spin_until_ge(o_cons, i + CH - RING, abortf, dead)); if (dead) break; }
-                for (uint32_t k = 0; k < CH && i + k < maxlen; k++) {
-                    const size_t ring = ((size_t)((i + k) % RING) * 8u) * 64u + lane;
-#pragma unroll
-                    for (int j = 0; j < 8; j++) {
-                        const X4Op op = opq[ring + j * 64];
-                        tok[ring + j * 64] = x4_step_c(x1, d, op.z0, op.q);
-                    }
-                    if (i + k + 1u == len) fin[lane] = make_uint2(x1, d);
-                }
-                __asm__ volatile("" ::: "memory");
-                lds_store_u32(x_done, need);
+                lds_store_u32(r.x_done, run_end);   // (the asm loop leaves the last chunk's hand-off to us: fin goes first)
+            } else {   // a chunk outside a whole revolution: the block's tail, or one in which some lane's block ends
+                x4_ragged_x<CH, RING, x5_ring_pos>(r, c, i, x1, d, seen_m, seen_o, dead);
+                if (dead) break;
                 i += CH;
             }
         }
@@ -315,67 +268,17 @@ __global__ void __launch_bounds__(L > 1 ? 256 : 192) k_coder_x5(Coder3Args a) {
     }
 
     // -------------------------------- O-wave --------------------------------
-    uint8_t *out = a.stripes + (uint64_t)(act ? b : 0u) * a.stripe_cap;
-    uint32_t cap = act ? a.stripe_cap : 0u;
+    uint8_t *out = a.stripes + (uint64_t)(c.act ? b : 0u) * a.stripe_cap;
+    uint32_t cap = c.act ? a.stripe_cap : 0u;
     const uint32_t limit = a.acc_limit, fast_fill = a.acc_limit + 18u;   // 64 for the default limit of 46
-    uint64_t acc = 0ull; uint32_t nb = 1u, pos = 0u;
+    SlotAcc o; o.init();
     uint32_t xr = 0u;   // the raw x1 the next token grew from (its bit 31 is all that matters)
-    uint32_t failed = 0u;
     uint32_t seen_x = 0, i = 0;
-    const uint32_t tok_lane = (uint32_t)(uintptr_t)(w3_lds_u8 *)(tok + lane);
-    const uint32_t sync_addr = (uint32_t)(uintptr_t)(w3_lds_u8 *)sync_w;
     const uint8_t *wg_base = a.stripes + (uint64_t)blockIdx.x * 64u * a.stripe_cap;   // stripe of this workgroup's first block
     const uint32_t voff = lane * a.stripe_cap;                                       // (64 stripes: below 2^32 for every block size)
-
-    // one byte's eight tokens the careful way: per-step accumulator guard, hand-back to k_coder when a pending run outgrows it
-    auto byte_c = [&](uint32_t j0) {
-        const uint2 *slot = tok + ((size_t)(j0 % RING) * 8u) * 64u + lane;
-#pragma unroll 1
-        for (int j = 0; j < 8; j++) {
-            const uint2 t = slot[j * 64];
-            if (nb > limit) {
-                // accumulator nearly full: drain finalised bytes (those above the slot) one at a time
-                const uint32_t pend = trailing_ones64(acc) + 1u;
-#pragma unroll 1
-                while (nb >= pend + 8u) {
-                    const uint8_t v = (uint8_t)(acc >> (nb - 8u));
-                    if (pos < cap) out[pos] = v;
-                    pos += 1u; nb -= 8u;
-                }
-                if (nb > limit) { failed = 1u; acc = 0ull; nb = 1u; }   // pending run longer than the accumulator: k_coder re-codes the block
-            }
-            const uint32_t xt = t.x ^ (xr & 0x80000000u), sj = t.y;   // the TRUE low end
-            xr = t.x << sj;
-            acc += xt >> 31;
-            acc = (acc << sj) | __builtin_amdgcn_ubfe(xt, 31u - sj, sj);
-            nb += sj;
-        }
-        // once per input byte: move 32 finalised bits out (never the slot or the pending ones)
-        const uint32_t lo = (uint32_t)acc;
-        const uint32_t pend = (~lo ? (uint32_t)__builtin_ctz(~lo) : 32u) + 1u;
-        if (nb >= pend + 32u) {
-            const uint32_t wv = (uint32_t)(acc >> (nb - 32u));
-            if (pos + 4u <= cap) { const uint32_t be = __builtin_bswap32(wv); __builtin_memcpy(out + pos, &be, 4); }
-            pos += 4u; nb -= 32u;
-        }
-    };
-    // ArithmeticCoder::flush -> ACWriter::flush(x2) (arithmetic_coder.rs:67-71, io.rs:91-100): first bit x2 >> 31 (= 1) resolves
-    // the slot and the pending bits, then x2's next bits pad to a byte
+    auto byte_c = [&](uint32_t j0) { x4_byte_c(o, xr, tok + ((size_t)x5_ring_pos(j0) * 8u) * 64u + lane, out, cap, limit); };
     auto finish = [&]() {
-        const uint2 f = fin[lane];
-        const uint32_t x2f = ((f.x & 0x7FFFFFFFu) + f.y) | 0x80000000u;
-        if (a.out_bits && !failed && cap) a.out_bits[b] = 8u * pos + nb - (trailing_ones64(acc) + 1u);   // ACStats (helpers.rs:60-90): all bits but the slot and the pending ones
-        uint64_t fa = acc + 1ull; uint32_t fnb = nb, fpos = pos;
-        const uint32_t idx = fnb & 7u;
-        if (idx) { const uint32_t kk = 8u - idx; fa = (fa << kk) | ((x2f << 1) >> (32u - kk)); fnb += kk; }
-#pragma unroll 1
-        while (fnb >= 8u) {
-            const uint8_t v = (uint8_t)(fa >> (fnb - 8u));
-            if (fpos < cap) out[fpos] = v;
-            fpos += 1u; fnb -= 8u;
-        }
-        if (failed) { const uint32_t kk = atomicAdd(&a.flags[1], 1u); a.redo[kk] = b; }
-        else { a.out_len[b] = fpos; if (fpos > cap) atomicOr(&a.flags[0], 1u); }
+        o.finish(a, b, x4_final_x2(fin[lane]), out, cap, a.out_bits && cap);
         cap = 0u;   // the lane keeps absorbing the tokens of clamped operands; nothing of it is stored any more
     };
 
@@ -383,35 +286,28 @@ __global__ void __launch_bounds__(L > 1 ? 256 : 192) k_coder_x5(Coder3Args a) {
         const uint32_t run_end = asm_end(i);
         if (run_end > i) {
             uint32_t status = 0, kbail = 0;
-            uint32_t alo = (uint32_t)acc, ahi = (uint32_t)(acc >> 32);
+            uint32_t alo = (uint32_t)o.acc, ahi = (uint32_t)(o.acc >> 32);
             asm volatile(W3_O5_LOOP
-                         : [alo] "+v"(alo), [ahi] "+v"(ahi), [nb] "+v"(nb), [pos] "+v"(pos), [xr] "+v"(xr), [i] "+s"(i),
+                         : [alo] "+v"(alo), [ahi] "+v"(ahi), [nb] "+v"(o.nb), [pos] "+v"(o.pos), [xr] "+v"(xr), [i] "+s"(i),
                            [sx] "+s"(seen_x), [st] "+s"(status), [k] "+s"(kbail)
                          : [iend] "s"(run_end), [tkl] "v"(tok_lane), [sync] "v"(sync_addr), [cap] "v"(cap), [voff] "v"(voff),
                            [base] "s"(wg_base), [fill] "s"(fast_fill), [k31] "s"(0x80000000u), [bsw] "s"(0x00010203u)
                          : W3_O4_CLOBBERS);
-            acc = ((uint64_t)ahi << 32) | alo;
+            o.acc = ((uint64_t)ahi << 32) | alo;
             if (status == 1u) { dead = true; break; }
             if (status == 2u) {   // ring byte kbail of the revolution at i the careful way, to the end of its chunk (x_done already covers it)
                 const uint32_t j0 = i + kbail, cend = (j0 / CH + 1u) * CH;
                 for (uint32_t j = j0; j < cend; j++) byte_c(j);
                 if (len == cend) finish();
                 __asm__ volatile("" ::: "memory");
-                lds_store_u32(o_cons, cend);
+                lds_store_u32(r.o_cons, cend);
                 i = cend;
                 continue;
             }
             if (len == run_end) finish();
         } else {
-            const uint32_t need = min(i + CH, maxlen);
-            if (seen_x < need) { seen_x = __builtin_amdgcn_readfirstlane(spin_until_ge<1>(x_done, need, abortf, dead)); if (dead) break; }
-            __asm__ volatile("" ::: "memory");
-            for (uint32_t k = 0; i + k < need; k++) {
-                byte_c(i + k);
-                if (i + k + 1u == len) finish();
-            }
-            __asm__ volatile("" ::: "memory");
-            lds_store_u32(o_cons, need);
+            x4_ragged_o<CH>(r, c, i, seen_x, dead, byte_c, finish);
+            if (dead) break;
             i += CH;
         }
     }

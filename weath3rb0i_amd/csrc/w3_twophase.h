@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "w3_apm.h"
@@ -928,30 +929,21 @@ static inline int tp_code_stage(TwoPhaseWs &ws, hipStream_t s_pred, hipStream_t 
         c3.acc_limit = limit;
         c3.out_bits = ws.out_bits;
         c3.prio_mo = (ws.tune >> 7) & 1u;
-        const dim3 grid((nb + 63) / 64), blk(192);
-        if (coder == 4) {
-            switch (ws.mix.n_src) {
-            case 1: hipLaunchKernelGGL(w3::k_coder_x3<1>, grid, blk, 0, s, c3); break;
-            case 2: hipLaunchKernelGGL(w3::k_coder_x3<2>, grid, blk, 0, s, c3); break;
-            case 3: hipLaunchKernelGGL(w3::k_coder_x3<3>, grid, blk, 0, s, c3); break;
-            default: hipLaunchKernelGGL(w3::k_coder_x3<4>, grid, blk, 0, s, c3); break;
-            }
-        } else if (coder == 5) {   // half the LDS: leaves room beside it for the next call's predict workgroups
-            const dim3 blk2(256);
-            switch (ws.mix.n_src) {
-            case 1: hipLaunchKernelGGL(w3::k_coder_x5<1>, grid, blk, 0, s, c3); break;
-            case 2: hipLaunchKernelGGL(w3::k_coder_x5<2>, grid, blk2, 0, s, c3); break;
-            case 3: hipLaunchKernelGGL(w3::k_coder_x5<3>, grid, blk2, 0, s, c3); break;
-            default: hipLaunchKernelGGL(w3::k_coder_x5<4>, grid, blk2, 0, s, c3); break;
-            }
-        } else {
-            const dim3 blk2(256);   // two M-waves when the leaves are mixed on the fly
-            switch (ws.mix.n_src) {
-            case 1: hipLaunchKernelGGL(w3::k_coder_x4<1>, grid, blk, 0, s, c3); break;
-            case 2: hipLaunchKernelGGL(w3::k_coder_x4<2>, grid, blk2, 0, s, c3); break;
-            case 3: hipLaunchKernelGGL(w3::k_coder_x4<3>, grid, blk2, 0, s, c3); break;
-            default: hipLaunchKernelGGL(w3::k_coder_x4<4>, grid, blk2, 0, s, c3); break;
-            }
+        const dim3 grid((nb + 63) / 64);
+        // x3: three waves.  x4 / x5: M, X, O, and a second M-wave when the leaves are mixed on the fly (L > 1).
+        // x5 has half the LDS: it leaves room beside it for the next call's predict workgroups.
+        auto launch = [&](auto lc) {
+            constexpr int L = decltype(lc)::value;
+            const dim3 blk(L > 1 && coder != 4 ? 256 : 192);
+            if (coder == 4) hipLaunchKernelGGL(w3::k_coder_x3<L>, grid, blk, 0, s, c3);
+            else if (coder == 5) hipLaunchKernelGGL(w3::k_coder_x5<L>, grid, blk, 0, s, c3);
+            else hipLaunchKernelGGL(w3::k_coder_x4<L>, grid, blk, 0, s, c3);
+        };
+        switch (ws.mix.n_src) {
+        case 1: launch(std::integral_constant<int, 1>()); break;
+        case 2: launch(std::integral_constant<int, 2>()); break;
+        case 3: launch(std::integral_constant<int, 3>()); break;
+        default: launch(std::integral_constant<int, 4>()); break;
         }
         if (tm) tm->coder_bytes = (uint64_t)n * (16 * ws.mix.n_src + 1);
     } else {
