@@ -283,3 +283,94 @@ def test_variant_reset_reaches_every_job_slot(ctx, oracle):
     for k, j in enumerate(jobs):
         ctx.encode_wait(j)
         assert bufs[k][0][: int(bufs[k][2].item())].cpu().numpy().tobytes() == want.tobytes(), k
+
+
+@pytest.mark.parametrize("first", [0, 1])
+def test_timed_job_across_a_synchronous_submit(oracle, first):
+    """A timed job on slot 0, then a submit that runs synchronously on job 0's workspace (seven bytes of Order1: too short for the
+    predict kernels) and records job 0's events again: slot 0's event times were collected before that, and its wait still reports
+    them.  Both outputs are the oracle's, whichever job is waited for first."""
+    import torch
+    bs = 2048
+    data = markov_text(100 * 1024 + 1, seed=94)
+    short = data[:7]
+    dev, orc = pair(oracle, "best012")
+    want, wlens = oracle.encode_blocks(orc(), data, bs, nthreads=8)
+    swant, swlens = oracle.encode_blocks(oracle.Order1(), short, bs, nthreads=1)
+    nb = (len(data) + bs - 1) // bs
+    d_in = torch.from_numpy(np.frombuffer(data, dtype=np.uint8).copy()).cuda()
+    d_short = torch.from_numpy(np.frombuffer(short, dtype=np.uint8).copy()).cuda()
+    big = (torch.empty(2 * len(data) + 64 * nb + 64, dtype=torch.uint8, device="cuda"), torch.zeros(nb, dtype=torch.int32, device="cuda"),
+           torch.zeros(1, dtype=torch.int64, device="cuda"))
+    small = (torch.empty(256, dtype=torch.uint8, device="cuda"), torch.zeros(1, dtype=torch.int32, device="cuda"),
+             torch.zeros(1, dtype=torch.int64, device="cuda"))
+    torch.cuda.synchronize()
+    c = w3.Context(0)   # (a context of its own: its first submit takes slot 0)
+    try:
+        c.set_timing(True)
+        jobs = [c.encode_submit(dev(), d_in, bs, *big), c.encode_submit(w3.Order1(), d_short, bs, *small)]
+        assert jobs == [0, 1]
+        for k in (first, 1 - first):
+            c.encode_wait(jobs[k])
+            t = c.timing()
+            d_out, d_lens, d_total = (big, small)[k]
+            w_out, w_lens = ((want, wlens), (swant, swlens))[k]
+            assert d_lens.cpu().numpy().astype(np.uint32).tolist() == w_lens.tolist(), k
+            assert d_out[: int(d_total.item())].cpu().numpy().tobytes() == w_out.tobytes(), k
+            if k == 0:
+                print("job 0 timing: path %d predict_ms %.4f coder_ms %.4f total_ms %.4f n_parts %d" % (t["path"], t["predict_ms"], t["coder_ms"], t["total_ms"], t["n_parts"]))
+                assert t["path"] == 2 and t["predict_ms"] > 0 and t["coder_ms"] > 0 and t["total_ms"] >= t["predict_ms"] and t["n_parts"] == 1
+            else:
+                assert t["path"] == 1
+    finally:
+        c.close()
+
+
+def test_every_option_reaches_every_job_slot(ctx, oracle):
+    """The options travel to a job slot as one block.  The input is one whose hand-back depends on them: tests/steer.py's run coverage
+    of best012 over the lengths every coder keeps (KEPT, runs released at 37 pending bits), gaps of 60 bytes, seed 5, in blocks of
+    2,048 bytes (four, the last one ragged).  No run grows past 38 pending bits, so at the default limit of 46 no coder hands a block
+    back (the guard gives up only with 40 or more: tests/test_gpu_steer.py); three blocks hold a run of 20 or more, and a fast coder
+    limited to 19 bits cannot hold those.  So four free-running jobs at the default settings re-code nothing, and with coder fast and
+    limit 19 every one of the four slots re-codes blocks; the streams are the oracle's each time.  A slot that had missed the coder
+    or the limit would report 0."""
+    import torch
+    from tests import steer
+    bs = 2048
+    dev, orc = pair(oracle, "best012")
+    data, tr = steer.run_coverage(orc, bs, gap_bytes=60, seed=5, want=steer.KEPT, cap=37)
+    assert tr.nblocks == 4 and not any(tr.handback)
+    assert max(tr.longest) <= 38                       # nothing is handed back at limit 46
+    assert sum(1 for v in tr.longest if v >= 20) == 3   # ... and these blocks are at limit 19
+    want, wlens = np.frombuffer(tr.stream(), dtype=np.uint8), np.array(tr.lens(), dtype=np.uint32)
+    n, nb = len(data), len(wlens)
+    assert ctx.max_in_flight(n, bs, dev()) == 4
+    d_in = torch.from_numpy(np.frombuffer(data, dtype=np.uint8).copy()).cuda()
+    bufs = [(torch.empty(2 * n + 64 * nb + 64, dtype=torch.uint8, device="cuda"), torch.zeros(nb, dtype=torch.int32, device="cuda"),
+             torch.zeros(1, dtype=torch.int64, device="cuda")) for _ in range(4)]
+    torch.cuda.synchronize()
+
+    def four_jobs():
+        jobs = [ctx.encode_submit(dev(), d_in, bs, *bufs[k]) for k in range(4)]
+        assert sorted(jobs) == [0, 1, 2, 3]
+        recoded = {}
+        for k, j in enumerate(jobs):
+            ctx.encode_wait(j)
+            recoded[j] = ctx.timing()["n_recoded_blocks"]
+            d_out, d_lens, d_total = bufs[k]
+            assert d_lens.cpu().numpy().astype(np.uint32).tolist() == wlens.tolist(), (k, j)
+            assert d_out[: int(d_total.item())].cpu().numpy().tobytes() == want.tobytes(), (k, j)
+        return recoded
+
+    at_default = four_jobs()
+    print("n_recoded_blocks per slot at the default settings: %r" % at_default)
+    assert all(v == 0 for v in at_default.values()), at_default
+    ctx.set_coder("fast")
+    ctx.set_acc_limit(19)
+    try:
+        limited = four_jobs()
+    finally:
+        ctx.set_acc_limit(46)
+        ctx.set_coder("x4")
+    print("n_recoded_blocks per slot with coder fast, limit 19: %r" % limited)
+    assert all(v > 0 for v in limited.values()), limited

@@ -53,13 +53,25 @@ enum { W3_EV_PREDICT = 0, W3_EV_CODER = 1, W3_EV_PACK = 2, W3_EV_TOTAL = 3, W3_E
        W3_EV_SLOTS = 16 };
 #define W3_NEV (2 * W3_EV_SLOTS)
 
+// What w3_ctx_set_option sets for the two-phase path.  The context owns the block; a workspace takes a copy when a call is prepared.
+struct TwoPhaseOptions {
+    int coder_mode = 0;        // 0 = k_coder_x4 (mix + asm recurrence + output waves), 1 = k_coder_fast, 2 = k_coder only, 3 = k_coder_x2, 4 = k_coder_x3, 5 = k_coder_x5 (x4 with 72 KiB rings)
+    uint32_t acc_limit = 46;   // test hook: lower values force the fast coder's fallback
+    uint32_t variant = 0;      // W3_VAR_* (W3_OPT_VARIANT)
+    uint32_t slot_budget_mb = 0;   // W3_OPT_SLOT_BUDGET_MB: cap on the slot leaves' hash-map batch (0 = from the free device memory)
+    int verify = 1;            // W3_OPT_VERIFY: sampled re-prediction with ballot rounds after every predict phase that used LDS-add rounds
+    uint32_t tune = 0;         // W3_OPT_TUNE: scheduling experiments (bit 1: k_apm0 padded to one workgroup per CU in the half-CU shapes)
+    uint32_t fault_block = 0xFFFFFFFFu;   // W3_OPT_FAULT_BLOCK (with W3_VAR_INJECT_LDS_FAULT)
+    uint32_t fault_kernels = 1u;          // W3_OPT_FAULT_KERNELS: which kernels the injected fault hits (1 k_predict_small, 2 k_rank_sorted, 4 k_partition8)
+    int debug_stamps = 0;      // W3_OPT_DEBUG_STAMPS
+};
+
 struct TwoPhaseWs {
     void *P = nullptr, *keys = nullptr, *perm = nullptr, *redo = nullptr, *streams = nullptr, *rec = nullptr, *splits = nullptr;
     size_t P_cap = 0, keys_cap = 0, perm_cap = 0, redo_cap = 0, streams_cap = 0, rec_cap = 0, splits_cap = 0;
     w3::MixArgs mix{};         // leaf streams of the last predict (sources of k_mix / k_coder_x3)
     bool P_valid = false;      // ws.P holds the merged stream of the last predict
     void *dbg = nullptr;       // 8 x u64 phase stamps of the last wide predict kernel (W3_OPT_DEBUG_STAMPS)
-    int debug_stamps = 0;
     bool achash_timed = false; // the last predict call recorded ev[12]/ev[13]
     hipEvent_t ev_pred_done = nullptr;   // two-stream form of twophase_encode: the predict phase is through (the code stream waits for it)
     int lds_order = -1;        // k_lds_order_selftest: -1 not run yet, 1 = returning LDS adds are lane-ordered (atomic rounds allowed), 0 = not
@@ -84,7 +96,6 @@ struct TwoPhaseWs {
     } pst;
     uint32_t *order_fault = nullptr;   // the call's flag word 2 (k_slot_replay reports a sort that lost its order there), or null
     uint32_t *apm_oob = nullptr;   // -DW3_TUNING builds: the call's flag word 3 (W3_APM_CHECK_STORE), else null
-    uint32_t tune = 0;         // W3_OPT_TUNE: scheduling experiments (bit 1: k_apm0 padded to one workgroup per CU in the half-CU shapes)
     bool half_cu = false;      // half-CU kernel shapes (w3_predict.h W3_HALF_CU_LDS, k_coder_x5): the call shares every CU with another call's stage
     int n_wide = 0; bool small_timed = false;   // what the last predict recorded events for (W3_EV_PART0.., W3_EV_RANK0.., W3_EV_SMALL)
     hipEvent_t ev_fork = nullptr, ev_join[4] = {nullptr, nullptr, nullptr, nullptr}, ev_small = nullptr;
@@ -100,14 +111,8 @@ struct TwoPhaseWs {
     void *wave_tables = nullptr; size_t wave_tables_cap = 0;  // k_predict_wave: one Counter table per resident wavefront
     void *huff_redo = nullptr;          // k_huffkeys: per-block "recompute serially" flags
     size_t huff_redo_cap = 0;
-    int coder_mode = 0;        // 0 = k_coder_x4 (mix + asm recurrence + output waves), 1 = k_coder_fast, 2 = k_coder only, 3 = k_coder_x2, 4 = k_coder_x3, 5 = k_coder_x5 (x4 with 72 KiB rings)
-    uint32_t acc_limit = 46;   // test hook: lower values force the fast coder's fallback
-    uint32_t variant = 0;      // W3_VAR_* (W3_OPT_VARIANT)
-    uint32_t slot_budget_mb = 0;   // W3_OPT_SLOT_BUDGET_MB: cap on the slot leaves' hash-map batch (0 = from the free device memory)
+    TwoPhaseOptions opt;       // the context's options as of the call being made (w3hip.hip hands them over when it prepares a call)
     uint64_t verify_calls = 0; // the call's number for the sample's rotation (w3_verify.h: counted per shape by the context)
-    uint32_t fault_block = 0xFFFFFFFFu;   // W3_OPT_FAULT_BLOCK (with W3_VAR_INJECT_LDS_FAULT)
-    uint32_t fault_kernels = 1u;          // W3_OPT_FAULT_KERNELS: which kernels the injected fault hits (1 k_predict_small, 2 k_rank_sorted, 4 k_partition8)
-    int verify = 1;            // W3_OPT_VERIFY: sampled re-prediction with ballot rounds after every predict phase that used LDS-add rounds
     TwoPhaseWs *vws = nullptr; // workspace of that re-prediction (owned)
     void *vin = nullptr; size_t vin_cap = 0;   // the sampled blocks, gathered
     bool used_lds_atomics = false;              // the last predict ran LDS-add rounds in some kernel
@@ -223,7 +228,7 @@ static inline void launch_small(int H, dim3 grid, hipStream_t s, const w3::Predi
 }
 // time-ordered Counter leaf in the shape the workspace asks for
 static inline void launch_small_shaped(const TwoPhaseWs &ws, int H, uint32_t nb, hipStream_t s, const w3::PredictArgs &pa) {
-    if (ws.half_cu && (ws.tune & 32u)) launch_small<false, W3_NW_SMALL>(H, dim3(std::min<uint32_t>((nb + W3_NW_SMALL - 1) / W3_NW_SMALL, 2 * W3_HALF_CU_GRID)), s, pa);
+    if (ws.half_cu && (ws.opt.tune & 32u)) launch_small<false, W3_NW_SMALL>(H, dim3(std::min<uint32_t>((nb + W3_NW_SMALL - 1) / W3_NW_SMALL, 2 * W3_HALF_CU_GRID)), s, pa);
     else launch_small<false>(H, dim3(std::min<uint32_t>(nb, 256 * 20)), s, pa);
 }
 
@@ -244,7 +249,7 @@ static inline int twophase_mix(TwoPhaseWs &ws, hipStream_t s, size_t n, std::str
 static inline bool twophase_lds_order_ok(TwoPhaseWs &ws, hipStream_t s) {
     if (ws.lds_order >= 0) return ws.lds_order == 1;
     ws.lds_order = 0;
-    if (ws.variant & W3_VAR_NO_LDS_ATOMICS) return false;
+    if (ws.opt.variant & W3_VAR_NO_LDS_ATOMICS) return false;
     const uint32_t waves = 64, rounds = 32, n = waves * rounds * 64;
     uint32_t *d_old = nullptr;
     if (hipMalloc(&d_old, (size_t)n * 4) != hipSuccess) { (void)hipGetLastError(); return false; }
@@ -333,7 +338,7 @@ static inline int twophase_predict_a(TwoPhaseWs &ws, hipStream_t s, const Parsed
     if (ev) (void)hipEventRecord(ev[2 * W3_EV_PREDICT], s);
     // fork: the partition passes of the wide leaves go to the side stream (they are bound by scattered line requests, the
     // time-ordered kernels by VALU issue); the rank kernels follow on the main stream after the join
-    const bool forked = need_perm && !(ws.variant & W3_VAR_NO_SIDE_STREAM) && !(ws.half_cu && (ws.tune & 32u));
+    const bool forked = need_perm && !(ws.opt.variant & W3_VAR_NO_SIDE_STREAM) && !(ws.half_cu && (ws.opt.tune & 32u));
     hipStream_t sp = forked ? ws.side : s;
     if (forked) { (void)hipEventRecord(ws.ev_fork, s); (void)hipStreamWaitEvent(ws.side, ws.ev_fork, 0); }
     ws.wide1_slot = -1;
@@ -434,8 +439,8 @@ static inline int twophase_predict_a(TwoPhaseWs &ws, hipStream_t s, const Parsed
         pa.maxseg = W3_ATOMIC_MAXSEG;
         if (const char *ev_ = w3_tune_env("W3_ATOMIC_MAXSEG")) pa.maxseg = (uint32_t)std::max(0, atoi(ev_));   // tuning hook
         if (!lds_atomics) pa.dbg_flags |= 2u;
-        if (ws.variant & W3_VAR_INJECT_LDS_FAULT) pa.dbg_flags |= (ws.fault_kernels & 7u) << 3;   // bits 3 / 4 / 5: see PredictArgs::dbg_flags
-        pa.fault_block = ws.fault_block;
+        if (ws.opt.variant & W3_VAR_INJECT_LDS_FAULT) pa.dbg_flags |= (ws.opt.fault_kernels & 7u) << 3;   // bits 3 / 4 / 5: see PredictArgs::dbg_flags
+        pa.fault_block = ws.opt.fault_block;
         bytes += n * 17;
         if (c == LEAF_SMALL_AC) {
             w3::HashArgs ha;
@@ -472,7 +477,7 @@ static inline int twophase_predict_a(TwoPhaseWs &ws, hipStream_t s, const Parsed
             // beside a wide leaf's rank kernel (bound by its scattered stores) instead of beside the partition passes: see below
             // (Two encodes in flight — join_all: at once on the launch stream, beside the partition passes on the side stream: the first
             // predict half 15.4 -> 14.3 ms, 68.3 -> 67.6 ms per step; W3_OPT_TUNE bit 11 keeps the deferred order there too.)
-            if (n_small_def < 8 && (!join_all || (ws.tune & 2048u))) small_def[n_small_def++] = pa;
+            if (n_small_def < 8 && (!join_all || (ws.opt.tune & 2048u))) small_def[n_small_def++] = pa;
             else {
                 const bool timed = ev && !ws.small_timed;
                 if (timed) { (void)hipEventRecord(ev[2 * W3_EV_SMALL], s); ws.small_timed = true; }
@@ -482,7 +487,7 @@ static inline int twophase_predict_a(TwoPhaseWs &ws, hipStream_t s, const Parsed
         } else {
             const int w = n_def;
             pa.perm = (uint32_t *)ws.perm_w[w];
-            if (ws.debug_stamps) {
+            if (ws.opt.debug_stamps) {
                 if (!ws.dbg && hipMalloc(&ws.dbg, 64) != hipSuccess) ws.dbg = nullptr;
                 if (ws.dbg) { (void)hipMemsetAsync(ws.dbg, 0, 64, s); pa.dbg = (unsigned long long *)ws.dbg; }
             }
@@ -499,16 +504,16 @@ static inline int twophase_predict_a(TwoPhaseWs &ws, hipStream_t s, const Parsed
             if (const char *ev_ = w3_tune_env("W3_RANK_GRID")) rank_waves = (uint32_t)std::max(64, atoi(ev_));   // tuning hook
             // half-CU shapes: the FIRST rank kernel starts beside the previous call's coder and must leave it its half of every CU's
             // LDS whichever of the two is dispatched first; the later ones are single wavefronts again (they fill what is free)
-            const uint32_t nw_rank = (ws.tune & 32768u) ? W3_NW_RANK8 : W3_NW_RANK;
-            const uint32_t grid_rank = (ws.half_cu && (w == 0 || (ws.tune & (32u | 64u))) && !(ws.tune & 8u)) ? std::min<uint32_t>((nb * W3_SLICES + nw_rank - 1) / nw_rank, W3_HALF_CU_GRID)
+            const uint32_t nw_rank = (ws.opt.tune & 32768u) ? W3_NW_RANK8 : W3_NW_RANK;
+            const uint32_t grid_rank = (ws.half_cu && (w == 0 || (ws.opt.tune & (32u | 64u))) && !(ws.opt.tune & 8u)) ? std::min<uint32_t>((nb * W3_SLICES + nw_rank - 1) / nw_rank, W3_HALF_CU_GRID)
                                                               : std::min<uint32_t>(nb * W3_SLICES, rank_waves);
             // an order-2 leaf behind an Order1 leaf starts from that leaf's records (sorted by c1; same stream, so they are ready)
-            const bool chained = c == LEAF_WIDE2 && ws.wide1_slot >= 0 && !(ws.variant & W3_VAR_NO_CHAINED_PARTITION);
+            const bool chained = c == LEAF_WIDE2 && ws.wide1_slot >= 0 && !(ws.opt.variant & W3_VAR_NO_CHAINED_PARTITION);
             if (chained) pa.rec_src = (const uint2 *)ws.rec_w[ws.wide1_slot];
             // one 8-bit pass through LDS tiles (k_partition8) needs the lane-ordered LDS adds; otherwise 4-bit passes
-            const bool p8 = lds_atomics && !(ws.variant & W3_VAR_PARTITION4);
+            const bool p8 = lds_atomics && !(ws.opt.variant & W3_VAR_PARTITION4);
             const uint32_t grid_p8h = std::min<uint32_t>((nb + W3_NW_PART - 1) / W3_NW_PART, 2 * W3_HALF_CU_GRID);
-            const bool p8h = p8 && ws.half_cu && (ws.tune & 32u);   // W3_OPT_TUNE bit 5: the first predict half in half-CU shapes too
+            const bool p8h = p8 && ws.half_cu && (ws.opt.tune & 32u);   // W3_OPT_TUNE bit 5: the first predict half in half-CU shapes too
             if (ev && w < 4) (void)hipEventRecord(ev[2 * (W3_EV_PART0 + w)], sp);
             const bool f8 = (pa.dbg_flags & 32u) != 0u;   // (the instance with the fault hook: tests of the sampled verification)
             if (c == LEAF_WIDE1 && p8h) launch_partition8<1, W3_NW_PART>(f8, dim3(grid_p8h), sp, pa);
@@ -572,13 +577,13 @@ static inline int twophase_predict_b(TwoPhaseWs &ws, hipStream_t s, const Parsed
         if (ev) (void)hipEventRecord(ev[2 * (W3_EV_RANK0 + w)], s);
         const bool w1 = deferred[w].cls == LEAF_WIDE1, fr = (deferred[w].pa.dbg_flags & 16u) != 0u;   // (fr: the instance with the fault hook)
         const dim3 gr(deferred[w].grid_rank);
-        if (ws.half_cu && (w == 0 || (ws.tune & (32u | 64u))) && !(ws.tune & 8u) && (ws.tune & 32768u)) {
+        if (ws.half_cu && (w == 0 || (ws.opt.tune & (32u | 64u))) && !(ws.opt.tune & 8u) && (ws.opt.tune & 32768u)) {
             if (w1) launch_rank<1, W3_NW_RANK8, 4>(fr, gr, s, deferred[w].pa);
             else launch_rank<2, W3_NW_RANK8, 4>(fr, gr, s, deferred[w].pa);
-        } else if (ws.half_cu && (ws.tune & 32768u)) {   // the later rank kernels: single wavefronts of 10 KiB (eight beside the coder's 74 KiB)
+        } else if (ws.half_cu && (ws.opt.tune & 32768u)) {   // the later rank kernels: single wavefronts of 10 KiB (eight beside the coder's 74 KiB)
             if (w1) launch_rank<1, 1, 4>(fr, gr, s, deferred[w].pa);
             else launch_rank<2, 1, 4>(fr, gr, s, deferred[w].pa);
-        } else if (ws.half_cu && (w == 0 || (ws.tune & (32u | 64u))) && !(ws.tune & 8u)) {
+        } else if (ws.half_cu && (w == 0 || (ws.opt.tune & (32u | 64u))) && !(ws.opt.tune & 8u)) {
             if (w1) launch_rank<1, W3_NW_RANK, W3_PF>(fr, gr, s, deferred[w].pa);
             else launch_rank<2, W3_NW_RANK, W3_PF>(fr, gr, s, deferred[w].pa);
         } else if (w1) launch_rank<1, 1, W3_PF>(fr, gr, s, deferred[w].pa);
@@ -594,8 +599,8 @@ static inline int twophase_predict_b(TwoPhaseWs &ws, hipStream_t s, const Parsed
     // ~7,000: k_slot 375 ms against 460 at 15,259 blocks): k_slot.  The replay needs the lane-ordered LDS adds (its partition).
     bool slot_sorted = false;
     ws.slot_sorted = false;
-    if (sa.n_leaves && !(ws.variant & W3_VAR_SLOT_TABLE) && st.lds_atomics && block_size <= (1ull << 31)) {
-        slot_sorted = nb < W3_SLOT_SORTED_MAX_BLOCKS || (ws.variant & W3_VAR_SLOT_SORTED);
+    if (sa.n_leaves && !(ws.opt.variant & W3_VAR_SLOT_TABLE) && st.lds_atomics && block_size <= (1ull << 31)) {
+        slot_sorted = nb < W3_SLOT_SORTED_MAX_BLOCKS || (ws.opt.variant & W3_VAR_SLOT_SORTED);
         bool two_passes = false;
         for (int l = 0; l < sa.n_leaves; l++) { slot_sorted &= sa.leaf[l].log_cells <= 16u; two_passes |= sa.leaf[l].log_cells > 8u; }
         const size_t key_bytes = (size_t)sa.n_leaves * 2 * n * 8, hist_bytes = (size_t)sa.n_leaves * nb * (512 + 1024) * 4;   // (digit counts + fine-bin prefixes)
@@ -631,12 +636,12 @@ static inline int twophase_predict_b(TwoPhaseWs &ws, hipStream_t s, const Parsed
                 // lane owns only 16 Cells and the wavefront runs as long as its busiest lane (hashed text contexts are very unevenly used: 6.6 us per
                 // event round against 2.2 with 256 Cells per lane); whether the ranges come from a binary search or from this prefix table made no
                 // difference.  W3_OPT_TUNE bits 9 / 10: 16 / 1.
-                const uint32_t wcap = (ws.tune & 1024u) ? 1u : (ws.tune & 512u) ? 16u : 4u;
+                const uint32_t wcap = (ws.opt.tune & 1024u) ? 1u : (ws.opt.tune & 512u) ? 16u : 4u;
                 s2.leaf_w[l] = std::min<uint32_t>(wcap, std::max<uint32_t>(1u, std::min<uint32_t>(cells, 1024u) / 64u));
                 s2.jobs_per_block += s2.leaf_w[l];
             }
 #ifdef W3_TUNING
-            s2.dbg = (ws.tune >> 8) & 1u;   // (-DW3_TUNING builds only — W3_OPT_TUNE bit 8: timing experiment, results WRONG)
+            s2.dbg = (ws.opt.tune >> 8) & 1u;   // (-DW3_TUNING builds only — W3_OPT_TUNE bit 8: timing experiment, results WRONG)
 #endif
             s2.job_counter = (uint32_t *)((uint8_t *)ws.slot_keys + 2 * key_bytes + hist_bytes);
             (void)hipMemsetAsync(s2.job_counter, 0, 4, s);
@@ -669,7 +674,7 @@ static inline int twophase_predict_b(TwoPhaseWs &ws, hipStream_t s, const Parsed
         }
         const uint64_t avail = (uint64_t)free_b + ws.slot_tables_cap;
         uint64_t budget = avail > later ? avail - later : 0;
-        if (ws.slot_budget_mb) budget = (uint64_t)ws.slot_budget_mb << 20;   // W3_OPT_SLOT_BUDGET_MB (tests: several batches on a small input)
+        if (ws.opt.slot_budget_mb) budget = (uint64_t)ws.opt.slot_budget_mb << 20;   // W3_OPT_SLOT_BUDGET_MB (tests: several batches on a small input)
         uint64_t lanes = std::min<uint64_t>(budget / slot_stride, nb);
         if (lanes < nb) {
             // equal batches: a batch costs at least the lone-wave latency of a whole block, however few lanes it has
@@ -725,9 +730,9 @@ static inline int twophase_predict(TwoPhaseWs &ws, hipStream_t s, const ParsedSp
 // and, when it is not zero, re-encodes the whole call on the ballot path and keeps the context there.
 static inline int twophase_verify(TwoPhaseWs &ws, hipStream_t s, const ParsedSpec &ps, const uint8_t *d_in, size_t n, size_t block_size,
                                   uint32_t nb, uint32_t *d_mismatch, std::string &err) {
-    if (!ws.verify || !ws.used_lds_atomics || nb == 0) return W3_OK;
-    // ws.verify = v >= 1: v / 256 of the blocks (W3_OPT_VERIFY; 1 = the default sample), at most 64 MiB x v of input
-    const uint32_t S = w3::verify_sample_size(nb, block_size, (uint32_t)std::max(1, ws.verify));
+    if (!ws.opt.verify || !ws.used_lds_atomics || nb == 0) return W3_OK;
+    // ws.opt.verify = v >= 1: v / 256 of the blocks (W3_OPT_VERIFY; 1 = the default sample), at most 64 MiB x v of input
+    const uint32_t S = w3::verify_sample_size(nb, block_size, (uint32_t)std::max(1, ws.opt.verify));
     const uint32_t rot = w3::verify_rotation(ws.verify_calls, nb, S);
     const uint64_t last_off = (uint64_t)w3::verify_block(rot, S - 1u, nb, S) * block_size;   // only the last slot can hold the short last block
     const size_t vn = (size_t)(S - 1u) * block_size + (size_t)std::min<uint64_t>(block_size, n - last_off);
@@ -743,9 +748,12 @@ static inline int twophase_verify(TwoPhaseWs &ws, hipStream_t s, const ParsedSpe
     if (!ws.vws) ws.vws = new TwoPhaseWs();
     TwoPhaseWs &v = *ws.vws;
     // (no side stream of its own: the sample is small, and every stream a context creates is one more claim on the hardware queues)
-    v.variant = (ws.variant | W3_VAR_NO_LDS_ATOMICS | W3_VAR_PARTITION4 | W3_VAR_NO_SIDE_STREAM) & ~(uint32_t)W3_VAR_INJECT_LDS_FAULT;
-    v.lds_order = 0; v.verify = 0;
-    v.stretch = ws.stretch; v.squash = ws.squash; v.st = ws.st; v.huff = ws.huff; v.slot_budget_mb = ws.slot_budget_mb;
+    // its options: the call's variant on the ballot rounds and the call's slot budget, everything else at its default
+    v.opt = TwoPhaseOptions();
+    v.opt.variant = (ws.opt.variant | W3_VAR_NO_LDS_ATOMICS | W3_VAR_PARTITION4 | W3_VAR_NO_SIDE_STREAM) & ~(uint32_t)W3_VAR_INJECT_LDS_FAULT;
+    v.opt.verify = 0; v.opt.slot_budget_mb = ws.opt.slot_budget_mb;
+    v.lds_order = 0;
+    v.stretch = ws.stretch; v.squash = ws.squash; v.st = ws.st; v.huff = ws.huff;
     // only the leaves whose kernels use the property are re-predicted (not the slot-state leaves, not k_predict_wave's)
     ParsedSpec vps;
     int map[W3_MAX_LEAVES], nmap = 0;   // vps leaf -> index among ws.mix.src (the live leaves of ps, in order)
@@ -792,7 +800,7 @@ static inline int twophase_apm(TwoPhaseWs &ws, hipStream_t s, const ParsedSpec &
             else { if ((rc = twophase_mix(ws, s, n, err))) return rc; aa.src[0] = (const uint16_t *)ws.P; bytes += n * 16 * (ws.mix.n_src + 1); }
             const dim3 grid((nb + W3_APM_WAVES - 1) / W3_APM_WAVES), blk(128 * W3_APM_WAVES);   // two wavefronts per block
             // W3_OPT_TUNE bit 1: dynamic LDS on top of the kernel's 79,968 B, so that two of its workgroups do not fit a CU
-            const uint32_t dyn = (ws.half_cu && (ws.tune & 2u)) ? 2048u : 0u;
+            const uint32_t dyn = (ws.half_cu && (ws.opt.tune & 2u)) ? 2048u : 0u;
 #define W3_LAUNCH_APM0(LL)                                                                                                   \
             do {                                                                                                             \
                 if (dyn) (void)hipFuncSetAttribute((const void *)w3::k_apm0<LL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn); \
@@ -856,7 +864,7 @@ static inline TpPlan tp_plan(const TwoPhaseWs &ws, const ParsedSpec &ps) {
     TpPlan p;
     p.n_live = 0;
     for (int l = 0; l < ps.n_leaves; l++) p.n_live += leaf_class(ps.leaf[l]) != LEAF_FROZEN;
-    p.coder = ws.half_cu && ws.coder_mode == 0 ? 5 : ws.coder_mode;   // half-CU shapes: k_coder_x5 in k_coder_x4's place
+    p.coder = ws.half_cu && ws.opt.coder_mode == 0 ? 5 : ws.opt.coder_mode;   // half-CU shapes: k_coder_x5 in k_coder_x4's place
     p.x3 = (p.coder == 0 || p.coder == 4 || p.coder == 5) && (p.n_live <= 4 || ps.n_apm > 0);   // more leaves: merge with k_mix first, then k_coder_x2
     p.need_P = !p.x3 && ps.n_apm == 0;
     p.verify_on = false; p.verify_in_place = false;
@@ -870,7 +878,7 @@ static inline int tp_after_predict(TwoPhaseWs &ws, hipStream_t s_pred, const Par
     // small launches otherwise) beside the CODER kernel, which leaves the chip's memory system and most of its issue slots
     // idle (beside k_apm0 its workgroups displaced some of that kernel's for ~1.4 ms per step, measured) — unless an APM stage
     // is about to rewrite the single leaf's stream in place: then it runs first, on the predict stream.
-    const bool verify_on = ws.verify && ws.used_lds_atomics;
+    const bool verify_on = ws.opt.verify && ws.used_lds_atomics;
     const bool verify_in_place = verify_on && pl.n_live == 1 && ps.n_apm > 0;
     int rc;
     if (verify_in_place && (rc = twophase_verify(ws, s_pred, ps, d_in, n, block_size, nb, d_flag + 2, err))) return rc;
@@ -889,7 +897,7 @@ static inline int tp_code_stage(TwoPhaseWs &ws, hipStream_t s_pred, hipStream_t 
     const bool x3 = pl.x3;
     int rc;
     bool verify_forked = false;
-    const bool verify_on = ws.verify && ws.used_lds_atomics;
+    const bool verify_on = ws.opt.verify && ws.used_lds_atomics;
     const bool verify_in_place = verify_on && n_live == 1 && ps.n_apm > 0;
     if (verify_on && !verify_in_place && (!ws.vstream || !ws.ev_v0)) {
         // (lowest priority level: its own hardware queues, apart from the launch streams'; and the re-prediction is in nobody's way)
@@ -918,7 +926,7 @@ static inline int tp_code_stage(TwoPhaseWs &ws, hipStream_t s_pred, hipStream_t 
     if (verify_on && !verify_in_place && (rc = fork_verify(s))) return rc;
     if (w3_tune_env("W3_DEBUG_NOSTORE")) { err = "W3_DEBUG_NOSTORE: predict-only timing experiment"; return W3_E_UNSUPPORTED; }
     if ((rc = tp_ensure(ws.redo, ws.redo_cap, (size_t)nb * 4, err))) return rc;
-    const uint32_t limit = std::min<uint32_t>(ws.acc_limit, 46u);
+    const uint32_t limit = std::min<uint32_t>(ws.opt.acc_limit, 46u);
     if (ev) (void)hipEventRecord(ev[2 * W3_EV_CODER], s);
     if (x3) {
         w3::Coder3Args c3;
@@ -928,7 +936,7 @@ static inline int tp_code_stage(TwoPhaseWs &ws, hipStream_t s_pred, hipStream_t 
         c3.stripes = stripes; c3.stripe_cap = stripe_cap; c3.out_len = d_lens; c3.flags = d_flag; c3.redo = (uint32_t *)ws.redo;
         c3.acc_limit = limit;
         c3.out_bits = ws.out_bits;
-        c3.prio_mo = (ws.tune >> 7) & 1u;
+        c3.prio_mo = (ws.opt.tune >> 7) & 1u;
         const dim3 grid((nb + 63) / 64);
         // x3: three waves.  x4 / x5: M, X, O, and a second M-wave when the leaves are mixed on the fly (L > 1).
         // x5 has half the LDS: it leaves room beside it for the next call's predict workgroups.

@@ -21,6 +21,7 @@
 #include "w3_decode_spec.h"
 #include "w3_pack.h"
 #include "w3_tables_plan.h"
+#include "w3_jobs.h"
 #include "w3_twophase.h"
 #include "w3_selftest.h"
 #include "w3_sweep.h"
@@ -41,37 +42,43 @@ struct DevBuf {
     size_t cap = 0;
 };
 
+// A submitted call, kept for the rare redo (stripe overflow, fast-coder hand-back, LDS-order fault, output beyond the realistic bound).
+// The spec and its HuffHistory tables are the caller's memory: both are copied, and the copies point at each other.
+struct KeptCall {
+    w3_model_spec spec{};
+    ParsedSpec ps;
+    w3_huff_table huff_copy[W3_MAX_HUFF];
+    const uint8_t *d_in = nullptr; size_t n = 0, block_size = 0;
+    uint64_t vcall = 0;            // the call's number for the verification's rotation (a redo keeps it; w3_encode_blocks: the same for all its pieces)
+    void keep(const w3_model_spec *s, const ParsedSpec &p, const uint8_t *d_in_, size_t n_, size_t block_size_) {
+        spec = *s; ps = p; d_in = d_in_; n = n_; block_size = block_size_;
+        if (p.n_huff) { memcpy(huff_copy, p.huff, sizeof(w3_huff_table) * p.n_huff); spec.huff = ps.huff = huff_copy; }
+    }
+    KeptCall() = default;
+    KeptCall(const KeptCall &) = delete;   // (it points into itself)
+    KeptCall &operator=(const KeptCall &) = delete;
+};
+
 // One encode in flight: its own workspace, so that call k+1's predict phase can run beside call k's APM and coder kernels
-// (w3_encode_submit / w3_encode_wait).  Job 0's members live in w3_ctx itself (every synchronous call uses them).
-struct JobState {
+// (w3_encode_submit / w3_encode_wait).  Every synchronous call uses jobs[0]'s.
+struct Job {
+    int index = 0;                 // its place in w3_ctx::jobs
+    TwoPhaseWs tp; DevBuf stripes, flag, bits, offs, huff; hipEvent_t ev[W3_NEV]{};   // the workspace (ev: W3_OPT_TIMING)
     int state = 0;                 // 0 idle, 1 enqueued (w3_encode_wait completes it), 2 ran synchronously inside w3_encode_submit
     hipEvent_t ev_done = nullptr, ev_in = nullptr;
     hipEvent_t ev_a = nullptr, ev_apm = nullptr;   // first predict half through / APM stages through (what the other job's kernels wait for)
     bool code_pending = false;     // the APM + coder + pack stage is not enqueued yet (it goes behind the NEXT job's first predict half)
-    ParsedSpec ps; uint32_t nb = 0, cap = 0;
-    uint32_t *h_status = nullptr;  // pinned: [0..3] the coder's flag words, [4..5] total compressed bytes
-    // the submitted call, kept for the rare synchronous redo in w3_encode_wait (stripe overflow, fast-coder hand-back, LDS-order fault)
-    w3_model_spec spec{};
-    w3_huff_table huff_copy[W3_MAX_HUFF];
-    const uint8_t *d_in = nullptr; size_t n = 0, block_size = 0; uint8_t *d_out = nullptr; size_t out_cap = 0;
-    uint32_t *d_block_lens = nullptr; uint64_t *d_total = nullptr;
-    uint64_t vcall = 0;            // the call's number for the verification's rotation (the redo keeps it)
+    uint32_t nb = 0, cap = 0;
+    uint32_t *h_status = nullptr;  // pinned: [0, ST_WORDS) the call's status words (w3_jobs.h), then the total compressed bytes
+    KeptCall call;                 // for the rare synchronous redo in w3_encode_wait
+    uint8_t *d_out = nullptr; size_t out_cap = 0; uint32_t *d_block_lens = nullptr; uint64_t *d_total = nullptr;
     w3_timing tm{};
     w3_timing tm_ev{}; bool tm_snap = false;   // the event times, collected early (a synchronous fallback is about to reuse job 0's events)
     int sync_rc = W3_OK;           // state 2: what the synchronous run inside w3_encode_submit returned
     uint64_t total_out = 0; bool total_valid = false;   // the compressed size w3_encode_wait read from the job's pinned status words
-    bool has_apm = false, has_slot = false, timed = false;
+    bool timed = false;
     hipStream_t sc = nullptr;      // the stream this job's code stage runs on (free-running jobs: one each; ordered jobs share s_code[0])
 };
-
-// Jobs in flight: free-running — every code stage on its own stream, the calls' coders overlapping one another — while a call's
-// coder leaves a good part of the chip idle: four up to W3_FREE_RUN4_BLOCKS blocks (64 coder workgroups), three up to
-// W3_FREE_RUN_BLOCKS (measured: 7,629 blocks 36.6 ms per step with three, 39.1 with four, 43.8 with the ordered pair; 11,444 blocks
-// 53.6 against 56.0 ordered; at 15,259 the two forms meet at 68-70 ms); beyond that the ordered pair of DESIGN.md section 2.8
-// (a job workspace is ~70 bytes per input byte).
-#define W3_MAX_JOBS 4
-#define W3_FREE_RUN_BLOCKS 12288u
-#define W3_FREE_RUN4_BLOCKS 4096u
 
 // One host-buffer encode in flight (w3_encode_host_submit / w3_encode_host_wait): its own device input / output buffers, so that call
 // k+1's input can travel over PCIe while call k is being encoded and call k-1's streams travel back.  One more than the device jobs:
@@ -82,12 +89,10 @@ struct HostJob {
                                    // 3 through on the device (rc / total known), output not fetched yet
     int djob = -1, rc = W3_OK;
     uint64_t seq = 0, total = 0;
-    uint64_t vcall = 0;            // the call's number for the verification's rotation (w3_encode_blocks: the same for all its pieces)
     DevBuf d_in, d_out, d_lens, d_total;
     hipEvent_t ev_d2h = nullptr;
-    w3_model_spec spec{};
-    w3_huff_table huff_copy[W3_MAX_HUFF];
-    size_t n = 0, block_size = 0, nb = 0, dcap = 0;
+    KeptCall call;
+    size_t nb = 0, dcap = 0;
     uint8_t *out = nullptr; size_t out_cap = 0; uint32_t *block_lens = nullptr;
     w3_timing tm{};
 };
@@ -99,9 +104,8 @@ struct w3_ctx {
     int opt_path = W3_PATH_AUTO;
     int opt_timing = 0;
     w3_timing timing{};
-    hipEvent_t ev[W3_NEV]{};
-    // workspace
-    DevBuf tables, stripes, lens, offs, total, flag, io_in, io_out, coffs, misc, cm_luts, achash_luts, huff, bits, sweep;
+    // workspace that is not a job's
+    DevBuf tables, lens, total, io_in, io_out, coffs, misc, cm_luts, achash_luts, sweep;
     DevBuf aoh;   // AC over Huffman (w3_aoh.h): code tables in device form, configurations, block bit lengths, maxima and flags
     // the random-access decode (w3_decode_ranges*): the staging buffer the jobs decode into, the job table + gather pieces (+ for the
     // host variant the compact length table and the selected streams behind them), and the host variant's pinned host copy of those
@@ -111,17 +115,21 @@ struct w3_ctx {
     // crc_tab: a table on its way to or from a host caller; crc_res: where the result lands on the host
     DevBuf crc_ws, crc_tab;
     uint64_t crc_res[2] = {~0ull, 0};
-    TwoPhaseWs tp;
-    // the second job of the submit / wait pipeline
-    struct JobWs { TwoPhaseWs tp; DevBuf stripes, flag, bits, offs, huff; hipEvent_t ev[W3_NEV]{}; } jx[W3_MAX_JOBS - 1];
-    JobState js[W3_MAX_JOBS];
+    // What a job takes from the context when a call is prepared (hand_options): the two-phase options (w3_ctx_set_option), the
+    // context-mixing look-up tables in cm_luts, and the lane-order self-test's verdict (-1 not run yet under this variant, 1 = returning
+    // LDS adds are lane-ordered, 0 = not: ballot rounds).
+    TwoPhaseOptions opt;
+    const int16_t *stretch = nullptr; const uint16_t *squash = nullptr; const uint2 *st = nullptr;
+    int lds_order = -1;
+    Job jobs[W3_MAX_JOBS];
+    w3_ctx() { for (int j = 0; j < W3_MAX_JOBS; j++) jobs[j].index = j; }
     hipStream_t s_pred = nullptr, s_code[W3_MAX_JOBS] = {};   // created by the first w3_encode_submit
     int next_job = 0, last_job = -1;
     bool pooled_streams = false;
     hipStream_t s_side = nullptr, s_verify[W3_MAX_JOBS] = {};   // the workspaces' side stream (one: predict phases never overlap) and re-prediction streams
     // sharded calls in flight (w3_encode_sharded_submit / w3_encode_sharded_wait): this context's shard of step `slot`, in staging
     // buffers of its own until the step is gathered
-    struct ShardSlot { int state = 0, djob = -1; DevBuf out, lens, total; size_t nb = 0, n = 0, cap = 0; const uint8_t *d_in = nullptr; size_t block_size = 0; w3_model_spec spec{}; w3_huff_table huff_copy[W3_MAX_HUFF]; } ss[W3_MAX_JOBS];
+    struct ShardSlot { int state = 0, djob = -1; DevBuf out, lens, total; size_t nb = 0, cap = 0; KeptCall call; } ss[W3_MAX_JOBS];
     // host-buffer calls in flight (w3_encode_host_submit / w3_encode_host_wait; w3_encode_blocks cuts its input into such calls)
     HostJob hj[W3_MAX_HOST_JOBS];
     hipStream_t s_h2d = nullptr, s_d2h = nullptr;   // where the copies go: the context's stream, or (W3_OPT_TUNE bit 16) the two below
@@ -144,16 +152,6 @@ struct VcallPin {
     VcallPin(w3_ctx *c_, uint64_t v) : c(c_), saved(c_->vcall_pin) { c->vcall_pin = (int64_t)v; }
     ~VcallPin() { c->vcall_pin = saved; }
 };
-
-// the members of job j under one name
-struct JobRef {
-    TwoPhaseWs &tp; DevBuf &stripes, &flag, &bits, &offs, &huff; hipEvent_t *ev; JobState &st;
-};
-static JobRef jobref(w3_ctx *c, int j) {
-    if (j == 0) return JobRef{c->tp, c->stripes, c->flag, c->bits, c->offs, c->huff, c->ev, c->js[0]};
-    w3_ctx::JobWs &x = c->jx[j - 1];
-    return JobRef{x.tp, x.stripes, x.flag, x.bits, x.offs, x.huff, x.ev, c->js[j]};
-}
 
 #define HIPCHK(ctx, expr)                                                                       \
     do {                                                                                        \
@@ -183,8 +181,8 @@ static int ensure(w3_ctx *ctx, DevBuf &b, size_t bytes) {
 // Every entry point but w3_encode_submit / w3_encode_wait (and their host-buffer forms) works on job 0's workspace and the context's
 // options: none of them may run while a submitted call is in flight (include/w3hip.h).
 static int jobs_idle(w3_ctx *ctx) {
-    for (const auto &st : ctx->js)
-        if (st.state == 1) { ctx->err = "asynchronous jobs are in flight on this context: w3_encode_wait them first"; return W3_E_INVALID; }
+    for (const auto &J : ctx->jobs)
+        if (J.state == 1) { ctx->err = "asynchronous jobs are in flight on this context: w3_encode_wait them first"; return W3_E_INVALID; }
     for (const auto &h : ctx->hj)
         if (h.state != 0) { ctx->err = "host-buffer jobs are in flight on this context: w3_encode_host_wait them first"; return W3_E_INVALID; }
     for (const auto &x : ctx->ss)
@@ -243,7 +241,7 @@ extern "C" int w3_ctx_create(int device, w3_ctx **out) {
     // had lived before, against 71.0 in a fresh process).
     c->stream = stream_pool().take(device * 8L + 4);
     if (!c->stream && hipStreamCreate(&c->stream) != hipSuccess) { delete c; return W3_E_HIP; }
-    for (auto &e : c->ev)
+    for (auto &e : c->jobs[0].ev)   // (a synchronous call can be timed; the other jobs' are created with the pipeline)
         if (hipEventCreate(&e) != hipSuccess) { delete c; return W3_E_HIP; }
     *out = c;
     return W3_OK;
@@ -253,26 +251,18 @@ extern "C" void w3_ctx_destroy(w3_ctx *ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
-    DevBuf *bufs[] = {&ctx->tables, &ctx->stripes, &ctx->lens, &ctx->offs, &ctx->total, &ctx->flag,
-                      &ctx->io_in, &ctx->io_out, &ctx->coffs, &ctx->misc, &ctx->cm_luts, &ctx->achash_luts, &ctx->huff, &ctx->bits, &ctx->sweep, &ctx->aoh,
-                      &ctx->rg_stage, &ctx->rg_meta, &ctx->crc_ws, &ctx->crc_tab};
+    DevBuf *bufs[] = {&ctx->tables, &ctx->lens, &ctx->total, &ctx->io_in, &ctx->io_out, &ctx->coffs, &ctx->misc, &ctx->cm_luts, &ctx->achash_luts,
+                      &ctx->sweep, &ctx->aoh, &ctx->rg_stage, &ctx->rg_meta, &ctx->crc_ws, &ctx->crc_tab};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (ctx->h_rg) (void)hipHostFree(ctx->h_rg);
-    ctx->tp.release();
-    for (auto &x : ctx->jx) {
-        x.tp.release();
-        DevBuf *bufs1[] = {&x.stripes, &x.flag, &x.bits, &x.offs, &x.huff};
-        for (DevBuf *b : bufs1)
+    for (auto &J : ctx->jobs) {
+        J.tp.release();
+        for (DevBuf *b : {&J.stripes, &J.flag, &J.bits, &J.offs, &J.huff})
             if (b->p) (void)hipFree(b->p);
-        for (auto &e : x.ev) if (e) (void)hipEventDestroy(e);
-    }
-    for (auto &st : ctx->js) {
-        if (st.ev_done) (void)hipEventDestroy(st.ev_done);
-        if (st.ev_in) (void)hipEventDestroy(st.ev_in);
-        if (st.ev_a) (void)hipEventDestroy(st.ev_a);
-        if (st.ev_apm) (void)hipEventDestroy(st.ev_apm);
-        if (st.h_status) (void)hipHostFree(st.h_status);
+        for (auto &e : J.ev) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : {J.ev_done, J.ev_in, J.ev_a, J.ev_apm}) if (e) (void)hipEventDestroy(e);
+        if (J.h_status) (void)hipHostFree(J.h_status);
     }
     if (ctx->s_side) stream_pool().give(ctx->device * 8L + 2, ctx->s_side);
     for (auto &sv : ctx->s_verify) if (sv) stream_pool().give(ctx->device * 8L + 3, sv);
@@ -296,8 +286,6 @@ extern "C" void w3_ctx_destroy(w3_ctx *ctx) {
     }
     if (ctx->s_h2d_own) (void)hipStreamDestroy(ctx->s_h2d_own);
     if (ctx->s_d2h_own) (void)hipStreamDestroy(ctx->s_d2h_own);
-    for (auto &e : ctx->ev)
-        if (e) (void)hipEventDestroy(e);
     if (ctx->stream) stream_pool().give(ctx->device * 8L + 4, ctx->stream);   // (idle: the device was synchronised above)
     delete ctx;
 }
@@ -316,41 +304,40 @@ extern "C" int w3_ctx_set_option(w3_ctx *ctx, int opt, int64_t value) {
     case W3_OPT_TIMING: ctx->opt_timing = value ? 1 : 0; return W3_OK;
     case W3_OPT_CODER:
         if (value < 0 || value > 5) return W3_E_INVALID;
-        ctx->tp.coder_mode = (int)value;
+        ctx->opt.coder_mode = (int)value;
         return W3_OK;
-    case W3_OPT_DEBUG_STAMPS: ctx->tp.debug_stamps = value ? 1 : 0; return W3_OK;
+    case W3_OPT_DEBUG_STAMPS: ctx->opt.debug_stamps = value ? 1 : 0; return W3_OK;
     case W3_OPT_ACC_LIMIT:
         if (value < 19 || value > 46) return W3_E_INVALID;
-        ctx->tp.acc_limit = (uint32_t)value;
+        ctx->opt.acc_limit = (uint32_t)value;
         return W3_OK;
     case W3_OPT_VARIANT:
         if (value < 0 || value > 4095) return W3_E_INVALID;
         // the fault-injection hook exists for the test of the sampled verification: without the verification it would only corrupt output
-        if ((value & W3_VAR_INJECT_LDS_FAULT) && !ctx->tp.verify) { ctx->err = "W3_OPT_VARIANT bit 32 (fault injection) needs W3_OPT_VERIFY on"; return W3_E_INVALID; }
-        ctx->tp.variant = (uint32_t)value;
-        ctx->tp.lds_order = -1;   // re-run the lane-order self-test under the new setting
-        for (auto &x : ctx->jx) x.tp.lds_order = -1;   // (the other job slots follow job 0: sync_job_options)
+        if ((value & W3_VAR_INJECT_LDS_FAULT) && !ctx->opt.verify) { ctx->err = "W3_OPT_VARIANT bit 32 (fault injection) needs W3_OPT_VERIFY on"; return W3_E_INVALID; }
+        ctx->opt.variant = (uint32_t)value;
+        ctx->lds_order = -1;   // re-run the lane-order self-test under the new setting
         return W3_OK;
     case W3_OPT_VERIFY:
-        if (!value && (ctx->tp.variant & W3_VAR_INJECT_LDS_FAULT)) { ctx->err = "W3_OPT_VERIFY cannot be switched off while the fault-injection variant is set"; return W3_E_INVALID; }
+        if (!value && (ctx->opt.variant & W3_VAR_INJECT_LDS_FAULT)) { ctx->err = "W3_OPT_VERIFY cannot be switched off while the fault-injection variant is set"; return W3_E_INVALID; }
         if (value < 0 || value > 256) return W3_E_INVALID;
-        ctx->tp.verify = (int)value;   // 0 = off, v >= 1: v / 256 of the blocks are re-predicted per call (twophase_verify)
+        ctx->opt.verify = (int)value;   // 0 = off, v >= 1: v / 256 of the blocks are re-predicted per call (twophase_verify)
         return W3_OK;
     case W3_OPT_SLOT_BUDGET_MB:
         if (value < 0 || value > (1 << 20)) return W3_E_INVALID;
-        ctx->tp.slot_budget_mb = (uint32_t)value;
+        ctx->opt.slot_budget_mb = (uint32_t)value;
         return W3_OK;
     case W3_OPT_TUNE:
         if (value < 0 || value > 0xFFFFF) return W3_E_INVALID;
-        ctx->tp.tune = (uint32_t)value;
+        ctx->opt.tune = (uint32_t)value;
         return W3_OK;
     case W3_OPT_FAULT_BLOCK:
         if (value < -1 || value > 0x7FFFFFFF) return W3_E_INVALID;
-        ctx->tp.fault_block = value < 0 ? 0xFFFFFFFFu : (uint32_t)value;
+        ctx->opt.fault_block = value < 0 ? 0xFFFFFFFFu : (uint32_t)value;
         return W3_OK;
     case W3_OPT_FAULT_KERNELS:
         if (value < 1 || value > 7) return W3_E_INVALID;
-        ctx->tp.fault_kernels = (uint32_t)value;
+        ctx->opt.fault_kernels = (uint32_t)value;
         return W3_OK;
     case W3_OPT_HOST_CHUNK_BLOCKS:
         if (value < 0 || value > 0x7FFFFFFF) return W3_E_INVALID;
@@ -437,8 +424,10 @@ static int parse_spec(const w3_model_spec *spec, ParsedSpec &ps) {
     return depth == 1 ? W3_OK : W3_E_INVALID;
 }
 
-// HuffHistory table sets of the spec -> device (per call: the tables are the caller's memory); job 0's copy
+// HuffHistory table sets of the spec -> device (per call: the tables are the caller's memory); job 0's copy, which is where the
+// lane-per-block kernels (they run on job 0 only) find them
 static int stage_huff(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps);
+static const w3_huff_table *lane_huff(const w3_ctx *ctx, const ParsedSpec &ps) { return ps.n_huff ? (const w3_huff_table *)ctx->jobs[0].huff.p : nullptr; }
 
 extern "C" int w3_spec_validate(const w3_model_spec *spec) {
     ParsedSpec ps;
@@ -495,7 +484,7 @@ static int check_len_table(w3_ctx *ctx, hipStream_t s, const uint32_t *d_lens, u
 // ---------------------------------------------------------------------------
 // pack: scan block lengths, compact stripes into d_out
 // ---------------------------------------------------------------------------
-static int run_pack(w3_ctx *ctx, JobRef &J, hipStream_t s, const uint8_t *stripes, uint64_t stride, const uint32_t *d_lens, uint32_t nb,
+static int run_pack(w3_ctx *ctx, Job &J, hipStream_t s, const uint8_t *stripes, uint64_t stride, const uint32_t *d_lens, uint32_t nb,
                     uint8_t *d_out, size_t out_cap, uint64_t *d_total) {
     ENSURE(ctx, J.offs, (size_t)nb * 8);
     hipLaunchKernelGGL(k_scan_lens, dim3(1), dim3(1024), 0, s, d_lens, (uint64_t *)J.offs.p, d_total, nb);
@@ -564,7 +553,7 @@ static int prepare_achash_luts(w3_ctx *ctx, hipStream_t s, GenericArgs &ga) {
 // instead of two, and a quarter of the wavefronts to hide them (profiles/r3_decode_spec/).  Kept as a tested variant.
 static int decode_group_bits(const w3_ctx *ctx, uint32_t blocks_in_batch) {
     (void)blocks_in_batch;
-    return (ctx->tp.tune & 16384u) ? 2 : 4;
+    return (ctx->opt.tune & 16384u) ? 2 : 4;
 }
 
 // k_generic over cnt lanes; 1-4 leaves: all Counter loads of a step in flight together
@@ -591,14 +580,14 @@ static int generic_encode(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, cons
     if ((rc = prepare_achash_luts(ctx, s, ga))) return rc;
     ENSURE(ctx, ctx->tables, (size_t)lanes * lane_stride);
     ga.n = n; ga.block_size = (uint32_t)block_size;
-    ga.huff = ctx->tp.huff; ga.n_huff = (int)ps.n_huff;
+    ga.huff = lane_huff(ctx, ps); ga.n_huff = (int)ps.n_huff;
     ga.tables = (uint8_t *)ctx->tables.p; ga.lane_stride = lane_stride;
-    ga.in = d_in; ga.stripe_cap = stripe_cap; ga.out_len = d_lens; ga.overflow = (uint32_t *)ctx->flag.p;
-    ga.out_bits = (uint32_t *)ctx->bits.p;
+    ga.in = d_in; ga.stripe_cap = stripe_cap; ga.out_len = d_lens; ga.overflow = (uint32_t *)ctx->jobs[0].flag.p;
+    ga.out_bits = (uint32_t *)ctx->jobs[0].bits.p;
     for (uint32_t first = 0; first < nb; first += lanes) {
         uint32_t cnt = std::min(lanes, nb - first);
         ga.first_block = first; ga.n_lanes = cnt;
-        ga.stripes = (uint8_t *)ctx->stripes.p + (uint64_t)first * stripe_cap;
+        ga.stripes = (uint8_t *)ctx->jobs[0].stripes.p + (uint64_t)first * stripe_cap;
         HIPCHK(ctx, hipMemsetAsync(ctx->tables.p, 0, (size_t)cnt * lane_stride, s));
         launch_generic<false>(ga, cnt, s);
         HIPCHK(ctx, hipGetLastError());
@@ -622,7 +611,7 @@ static int generic_decode(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, cons
     if ((rc = prepare_achash_luts(ctx, s, ga))) return rc;
     ENSURE(ctx, ctx->tables, (size_t)lanes * lane_stride);
     ga.n = orig_len; ga.block_size = (uint32_t)block_size;
-    ga.huff = ctx->tp.huff; ga.n_huff = (int)ps.n_huff;
+    ga.huff = lane_huff(ctx, ps); ga.n_huff = (int)ps.n_huff;
     ga.tables = (uint8_t *)ctx->tables.p; ga.lane_stride = lane_stride;
     ga.cin = d_cin; ga.coffs = (const uint64_t *)ctx->coffs.p; ga.clens = d_lens; ga.dout = d_out;
     ga.jobs = d_jobs;
@@ -634,8 +623,8 @@ static int generic_decode(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, cons
             CmArgs ca;
             memset(&ca, 0, sizeof ca);
             ca.g = ga;
-            ca.dflags = (ctx->tp.tune >> 17) & 7u;
-            if (decode_spec_covers(ca) && !(ctx->tp.variant & W3_VAR_DECODE_LANE)) {
+            ca.dflags = (ctx->opt.tune >> 17) & 7u;
+            if (decode_spec_covers(ca) && !(ctx->opt.variant & W3_VAR_DECODE_LANE)) {
                 launch_decode_spec(ca, cnt, s, decode_group_bits(ctx, cnt));
                 HIPCHK(ctx, hipGetLastError());
                 continue;
@@ -701,10 +690,10 @@ static int cm_run(w3_ctx *ctx, hipStream_t s, CmArgs &ca, uint64_t lane_stride, 
     for (uint32_t first = 0; first < nb; first += lanes) {
         uint32_t cnt = std::min(lanes, nb - first);
         ca.g.first_block = first; ca.g.n_lanes = cnt;
-        if (!DECODE) ca.g.stripes = (uint8_t *)ctx->stripes.p + (uint64_t)first * stripe_cap;
+        if (!DECODE) ca.g.stripes = (uint8_t *)ctx->jobs[0].stripes.p + (uint64_t)first * stripe_cap;
         HIPCHK(ctx, hipMemsetAsync(ctx->tables.p, 0, (size_t)cnt * lane_stride, s));
-        const bool spec_dec = DECODE && decode_spec_covers(ca) && !(ctx->tp.variant & W3_VAR_DECODE_LANE);
-        ca.dflags = (ctx->tp.tune >> 17) & 7u;
+        const bool spec_dec = DECODE && decode_spec_covers(ca) && !(ctx->opt.variant & W3_VAR_DECODE_LANE);
+        ca.dflags = (ctx->opt.tune >> 17) & 7u;
         const bool nm_tables = spec_dec && decode_spec_nibble_major(ca, cnt, decode_group_bits(ctx, cnt));   // (the APM tables' layout follows the kernel's)
         for (int k = 0; k < ca.n_apm; k++)
             hipLaunchKernelGGL(k_cm_init_apm, dim3(2048), dim3(256), 0, s, ca.g.tables, lane_stride, ca.apm[k].off,
@@ -723,7 +712,7 @@ static int cm_run(w3_ctx *ctx, hipStream_t s, CmArgs &ca, uint64_t lane_stride, 
         } else {
             int n_slot = 0;
             for (int l = 0; l < ca.g.n_leaves; l++) n_slot += ca.g.leaf[l].kind == 1;
-            if (n_slot <= W3_CM_STAGED_MAX && !(ctx->tp.variant & W3_VAR_CM_UNSTAGED)) hipLaunchKernelGGL(k_cm_staged<DECODE>, grid, blk, 0, s, ca);   // slot cells staged in LDS
+            if (n_slot <= W3_CM_STAGED_MAX && !(ctx->opt.variant & W3_VAR_CM_UNSTAGED)) hipLaunchKernelGGL(k_cm_staged<DECODE>, grid, blk, 0, s, ca);   // slot cells staged in LDS
             else hipLaunchKernelGGL(k_cm<DECODE>, grid, blk, 0, s, ca);
         }
         HIPCHK(ctx, hipGetLastError());
@@ -738,9 +727,9 @@ static int cm_encode(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, const uin
     const uint64_t lane_stride = layout_cm(ps, block_size, ca);
     { int rc_ = prepare_achash_luts(ctx, s, ca.g); if (rc_) return rc_; }
     ca.g.n = n; ca.g.block_size = (uint32_t)block_size;
-    ca.g.huff = ctx->tp.huff; ca.g.n_huff = (int)ps.n_huff;
-    ca.g.in = d_in; ca.g.stripe_cap = stripe_cap; ca.g.out_len = d_lens; ca.g.overflow = (uint32_t *)ctx->flag.p;
-    ca.g.out_bits = (uint32_t *)ctx->bits.p;
+    ca.g.huff = lane_huff(ctx, ps); ca.g.n_huff = (int)ps.n_huff;
+    ca.g.in = d_in; ca.g.stripe_cap = stripe_cap; ca.g.out_len = d_lens; ca.g.overflow = (uint32_t *)ctx->jobs[0].flag.p;
+    ca.g.out_bits = (uint32_t *)ctx->jobs[0].bits.p;
     return cm_run<false>(ctx, s, ca, lane_stride, nb, stripe_cap);
 }
 
@@ -752,7 +741,7 @@ static int cm_decode(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, const uin
     const uint64_t lane_stride = layout_cm(ps, block_size, ca);
     { int rc_ = prepare_achash_luts(ctx, s, ca.g); if (rc_) return rc_; }
     ca.g.n = orig_len; ca.g.block_size = (uint32_t)block_size;
-    ca.g.huff = ctx->tp.huff; ca.g.n_huff = (int)ps.n_huff;
+    ca.g.huff = lane_huff(ctx, ps); ca.g.n_huff = (int)ps.n_huff;
     ca.g.cin = d_cin; ca.g.coffs = (const uint64_t *)ctx->coffs.p; ca.g.clens = d_lens; ca.g.dout = d_out;
     ca.g.jobs = d_jobs;
     return cm_run<true>(ctx, s, ca, lane_stride, d_jobs ? n_jobs : nb, 0);   // (the lanes: blocks, or jobs)
@@ -800,7 +789,7 @@ static void collect_timing(hipEvent_t *ev, const TwoPhaseWs &ws, bool has_apm, b
     t.total_ms = elapsed_ev(ev, W3_EV_TOTAL);
 }
 
-static int stage_huff_job(w3_ctx *ctx, JobRef &J, hipStream_t s, const ParsedSpec &ps) {
+static int stage_huff_job(w3_ctx *ctx, Job &J, hipStream_t s, const ParsedSpec &ps) {
     J.tp.huff = nullptr;
     if (!ps.n_huff) return W3_OK;
     ENSURE(ctx, J.huff, sizeof(w3_huff_table) * W3_MAX_HUFF);
@@ -810,47 +799,86 @@ static int stage_huff_job(w3_ctx *ctx, JobRef &J, hipStream_t s, const ParsedSpe
     return W3_OK;
 }
 
-static int stage_huff(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps) {
-    JobRef J = jobref(ctx, 0);
-    return stage_huff_job(ctx, J, s, ps);
+static int stage_huff(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps) { return stage_huff_job(ctx, ctx->jobs[0], s, ps); }
+
+// What the context owns reaches a job's workspace here, when a call is prepared: the options as one block, the look-up tables, and the
+// lane-order self-test's verdict (one run per variant setting, on the workspace that asks first).
+static void hand_options(w3_ctx *ctx, Job &J, bool two) {
+    J.tp.opt = ctx->opt;
+    if (J.index) J.tp.opt.debug_stamps = 0;   // (w3_debug_get_stamps reads job 0's)
+    J.tp.stretch = ctx->stretch; J.tp.squash = ctx->squash; J.tp.st = ctx->st;
+    J.tp.lds_order = ctx->lds_order;
+    if (two && ctx->lds_order < 0) { (void)twophase_lds_order_ok(J.tp, ctx->stream); ctx->lds_order = J.tp.lds_order; }
 }
 
-// options live in job 0's workspace (w3_ctx_set_option); job 1 follows it
-static void sync_job_options(w3_ctx *ctx, JobRef &J) {
-    if (&J.tp == &ctx->tp) return;
-    J.tp.coder_mode = ctx->tp.coder_mode; J.tp.acc_limit = ctx->tp.acc_limit; J.tp.debug_stamps = 0;
-    J.tp.variant = ctx->tp.variant; J.tp.slot_budget_mb = ctx->tp.slot_budget_mb; J.tp.verify = ctx->tp.verify;
-    J.tp.stretch = ctx->tp.stretch; J.tp.squash = ctx->tp.squash; J.tp.st = ctx->tp.st; J.tp.fault_block = ctx->tp.fault_block; J.tp.fault_kernels = ctx->tp.fault_kernels; J.tp.tune = ctx->tp.tune;
-    // the lane-order self-test runs once, on job 0's workspace; the other slots take its verdict (and lose a stale one when
-    // W3_OPT_VARIANT has reset job 0's)
-    if (ctx->tp.lds_order < 0) (void)twophase_lds_order_ok(ctx->tp, ctx->stream);
-    J.tp.lds_order = ctx->tp.lds_order;
+// The sampled verification saw the LDS-add rounds misbehave: this context codes with the ballot rounds from now on, on every slot.
+static void use_ballot_rounds(w3_ctx *ctx) {
+    ctx->opt.variant |= W3_VAR_NO_LDS_ATOMICS; ctx->lds_order = 0;
+    for (auto &J : ctx->jobs) { J.tp.opt.variant |= W3_VAR_NO_LDS_ATOMICS; J.tp.lds_order = 0; }
 }
 
 // The side stream of the predict phase and the job's re-prediction stream: the context's (taken from the process-wide pool), so that
 // a context does not create streams — and with them hardware-queue assignments — of its own for every workspace.
-static int attach_aux_streams(w3_ctx *ctx, JobRef &J, int j) {
+static int attach_aux_streams(w3_ctx *ctx, Job &J) {
     if (!ctx->s_side) {
         ctx->s_side = stream_pool().take(ctx->device * 8L + 2);
         if (!ctx->s_side) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->s_side, hipStreamNonBlocking));
     }
-    if (!ctx->s_verify[j]) {
-        ctx->s_verify[j] = stream_pool().take(ctx->device * 8L + 3);
-        if (!ctx->s_verify[j]) {
+    hipStream_t &sv = ctx->s_verify[J.index];
+    if (!sv) {
+        sv = stream_pool().take(ctx->device * 8L + 3);
+        if (!sv) {
             int lo_p = 0, hi_p = 0;
             HIPCHK(ctx, hipDeviceGetStreamPriorityRange(&lo_p, &hi_p));
-            HIPCHK(ctx, hipStreamCreateWithPriority(&ctx->s_verify[j], hipStreamNonBlocking, lo_p));
+            HIPCHK(ctx, hipStreamCreateWithPriority(&sv, hipStreamNonBlocking, lo_p));
         }
     }
-    J.tp.side = ctx->s_side; J.tp.vstream = ctx->s_verify[j]; J.tp.ext_streams = true;
+    J.tp.side = ctx->s_side; J.tp.vstream = sv; J.tp.ext_streams = true;
     return W3_OK;
+}
+
+static int stage_cm_luts(w3_ctx *ctx, hipStream_t s) {
+    CmArgs lut;
+    const int rc = cm_luts(ctx, s, lut);
+    if (!rc) { ctx->stretch = lut.stretch; ctx->squash = lut.squash; ctx->st = lut.st; }
+    return rc;
+}
+
+// Everything a call needs in job J before its first attempt, enqueued on s where it touches the device: the status and bit-count
+// buffers, the spec's HuffHistory tables, the context-mixing look-up tables, the context's options, the side streams, the call's
+// number for the verification's rotation and the places its kernels report to.  two: the call takes the two-phase path.  What repeats per attempt (stripes at the attempt's cap, cleared status words) is the caller's.
+static int job_prepare(w3_ctx *ctx, Job &J, const ParsedSpec &ps, hipStream_t s, bool two, bool half_cu, size_t n, size_t block_size, uint32_t nb) {
+    int rc;
+    ENSURE(ctx, J.flag, 4 * ST_WORDS);
+    ENSURE(ctx, J.bits, (size_t)nb * 4);
+    if ((rc = stage_huff_job(ctx, J, s, ps))) return rc;
+    if (two && ps.is_cm() && (rc = stage_cm_luts(ctx, s))) return rc;
+    hand_options(ctx, J, two);
+    if ((rc = attach_aux_streams(ctx, J))) return rc;
+    J.tp.half_cu = half_cu;
+    J.tp.verify_calls = verify_call(ctx, n, block_size);   // (counted per shape by the context: a call's job slot does not matter)
+    J.tp.out_bits = (uint32_t *)J.bits.p;
+    J.tp.order_fault = (uint32_t *)J.flag.p + ST_ORDER_FAULT;
+#ifdef W3_TUNING
+    J.tp.apm_oob = (uint32_t *)J.flag.p + ST_APM_OOB;
+#endif
+    return W3_OK;
+}
+
+// ctx->timing of a finished two-phase call: the launch statistics its enqueueing collected in ptm, and (timed calls) the event times
+static void fill_timing(w3_ctx *ctx, Job &J, const w3_timing &ptm, uint64_t total, const ParsedSpec &ps, bool timed, bool packed) {
+    ctx->timing.path = W3_PATH_TWOPHASE;
+    ctx->timing.coder_bytes = ptm.coder_bytes + total; ctx->timing.predict_bytes = ptm.predict_bytes;
+    ctx->timing.n_coder_launches = ptm.n_coder_launches; ctx->timing.n_slot_launches = ptm.n_slot_launches;
+    ctx->timing.n_parts = 1;
+    if (timed) collect_timing(J.ev, J.tp, ps.n_apm > 0, ps.has_slot, packed, ctx->timing);
 }
 
 // d_out == nullptr: counting-sink mode (ACStats, helpers.rs:60-90) — the streams are coded into the stripes as usual, the
 // pack is skipped and only J.bits (per-block bit counts) is of interest; d_block_lens may then be a scratch buffer.
-// Synchronous: returns when the output is complete.  J = the job whose workspace is used (job 0 for every synchronous entry point;
+// Synchronous: returns when the output is complete.  J = the job whose workspace is used (jobs[0] for every synchronous entry point;
 // w3_encode_wait redoes a job of its own here).
-static int encode_core(w3_ctx *ctx, JobRef J, const w3_model_spec *spec, const uint8_t *d_in, size_t n, size_t block_size,
+static int encode_core(w3_ctx *ctx, Job &J, const w3_model_spec *spec, const uint8_t *d_in, size_t n, size_t block_size,
                        uint8_t *d_out, size_t out_cap, uint32_t *d_block_lens, uint64_t *d_total, void *stream) {
     int rc = check_args(ctx, n, block_size);
     if (rc) return rc;
@@ -868,23 +896,10 @@ static int encode_core(w3_ctx *ctx, JobRef J, const w3_model_spec *spec, const u
         return W3_OK;
     }
     if (!d_in || !d_block_lens) return W3_E_INVALID;
-    ENSURE(ctx, J.flag, 16);
-    ENSURE(ctx, J.bits, (size_t)nb * 4);
-    if ((rc = stage_huff_job(ctx, J, s, ps))) return rc;
-
-    bool two = twophase_supported(ps, block_size, n);   // Counter and slot-state leaves + APM chain (decode: k_generic / k_cm)
-    if (ctx->opt_path == W3_PATH_GENERIC) two = false;
-    if (two && ps.is_cm()) {
-        CmArgs lut;
-        if ((rc = cm_luts(ctx, s, lut))) return rc;
-        ctx->tp.stretch = lut.stretch; ctx->tp.squash = lut.squash; ctx->tp.st = lut.st;
-    }
+    const bool two = twophase_supported(ps, block_size, n) && ctx->opt_path != W3_PATH_GENERIC;   // Counter and slot-state leaves + APM chain (decode: k_generic / k_cm)
     if (ctx->opt_path == W3_PATH_TWOPHASE && !two) { ctx->err = "spec/block size not covered by the two-phase path"; return W3_E_UNSUPPORTED; }
-    if (!two && &J.tp != &ctx->tp) { ctx->err = "internal: the lane-per-block path runs on job 0"; return W3_E_INVALID; }
-    sync_job_options(ctx, J);
-    if ((rc = attach_aux_streams(ctx, J, &J.tp == &ctx->tp ? 0 : (int)(&J.st - ctx->js)))) return rc;
-    J.tp.half_cu = (ctx->tp.variant & W3_VAR_HALF_CU) != 0;
-    J.tp.verify_calls = verify_call(ctx, n, block_size);
+    if (!two && J.index) { ctx->err = "internal: the lane-per-block path runs on job 0"; return W3_E_INVALID; }
+    if ((rc = job_prepare(ctx, J, ps, s, two, (ctx->opt.variant & W3_VAR_HALF_CU) != 0, n, block_size, nb))) return rc;
 
     hipEvent_t *evp = ctx->opt_timing ? J.ev : nullptr;
     uint32_t cap = default_stripe_cap(block_size);
@@ -892,17 +907,16 @@ static int encode_core(w3_ctx *ctx, JobRef J, const w3_model_spec *spec, const u
     memset(&ptm, 0, sizeof ptm);
     bool cap_raised = false, fault_seen = false;
     uint32_t lds_faults = 0;
+    auto read_status = [&](JobStatus &st) -> int {
+        HIPCHK(ctx, hipMemcpyAsync(st.w, J.flag.p, sizeof st.w, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        return W3_OK;
+    };
     for (int attempt = 0; attempt < 4; attempt++) {
         ENSURE(ctx, J.stripes, (size_t)nb * cap);
-        HIPCHK(ctx, hipMemsetAsync(J.flag.p, 0, 16, s));
+        HIPCHK(ctx, hipMemsetAsync(J.flag.p, 0, 4 * ST_WORDS, s));
         if (evp) HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_TOTAL], s));
-        uint32_t fl[4] = {0, 0, 0, 0};
         if (two) {
-            J.tp.out_bits = (uint32_t *)J.bits.p;
-            J.tp.order_fault = (uint32_t *)J.flag.p + 2;
-#ifdef W3_TUNING
-            J.tp.apm_oob = (uint32_t *)J.flag.p + 3;
-#endif
             memset(&ptm, 0, sizeof ptm);
             rc = twophase_encode(J.tp, s, s, ps, d_in, n, block_size, nb, (uint8_t *)J.stripes.p, cap, d_block_lens, (uint32_t *)J.flag.p, evp, &ptm, ctx->err);
             if (rc) return rc;
@@ -915,33 +929,31 @@ static int encode_core(w3_ctx *ctx, JobRef J, const w3_model_spec *spec, const u
             ctx->timing.path = W3_PATH_GENERIC;
             if (rc) return rc;
         }
-        HIPCHK(ctx, hipMemcpyAsync(fl, J.flag.p, sizeof fl, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipStreamSynchronize(s));
-        if (two && fl[2]) {
-            // sampled verification of the LDS-add rounds (twophase_verify): a mismatch means the hardware did not resolve returning LDS
-            // adds in lane order under this load.  The streams just coded cannot be trusted: code the call again with the ballot
-            // rounds, and keep this context on them.
-            if (fault_seen) { ctx->err = "predict streams differ from their ballot-round re-prediction even without LDS-add rounds (internal error)"; return W3_E_HIP; }
+        JobStatus st{};
+        if ((rc = read_status(st))) return rc;
+        JobAction act = job_classify(st, cap_raised, fault_seen, two);
+        if (act == JOB_RECODE) {
+            ctx->timing.n_recoded_blocks += st.handed_back();
+            rc = twophase_recode(J.tp, s, d_in, n, block_size, nb, (uint8_t *)J.stripes.p, cap, d_block_lens, (uint32_t *)J.flag.p, st.handed_back(), ctx->err);
+            if (rc || (rc = read_status(st))) return rc;
+            act = job_classify_coded(st, cap_raised);
+        }
+        if (act == JOB_DONE) break;
+        switch (act) {
+        case JOB_BALLOT_ROUNDS:   // (w3_jobs.h)
             fault_seen = true;
-            lds_faults += fl[2];
-            ctx->tp.variant |= W3_VAR_NO_LDS_ATOMICS; ctx->tp.lds_order = 0;
-            for (auto &x : ctx->jx) { x.tp.variant |= W3_VAR_NO_LDS_ATOMICS; x.tp.lds_order = 0; }
-            ctx->timing.n_recoded_blocks = 0;
-            continue;
+            lds_faults += st.order_fault();
+            use_ballot_rounds(ctx);
+            break;
+        case JOB_RAISE_CAP:
+            cap = worst_stripe_cap(block_size);
+            cap_raised = true;
+            break;
+        case JOB_ERR_ORDER_FAULT: ctx->err = "predict streams differ from their ballot-round re-prediction even without LDS-add rounds (internal error)"; return W3_E_HIP;
+        case JOB_ERR_TIMEOUT: ctx->err = "coder pipeline timeout (internal error)"; return W3_E_HIP;
+        case JOB_ERR_APM_OOB: ctx->err = "APM kernel: " + std::to_string(st.apm_oob()) + " stores outside the stage's stream and the sink (W3_TUNING store guard)"; return W3_E_HIP;
+        default: ctx->err = "stripe overflow at the worst-case bound (internal error)"; return W3_E_HIP;
         }
-        if (two && fl[1]) {   // blocks the fast coder handed back (pending-bit run longer than its accumulator)
-            ctx->timing.n_recoded_blocks += fl[1];
-            rc = twophase_recode(J.tp, s, d_in, n, block_size, nb, (uint8_t *)J.stripes.p, cap, d_block_lens, (uint32_t *)J.flag.p, fl[1], ctx->err);
-            if (rc) return rc;
-            HIPCHK(ctx, hipMemcpyAsync(fl, J.flag.p, sizeof fl, hipMemcpyDeviceToHost, s));
-            HIPCHK(ctx, hipStreamSynchronize(s));
-        }
-        if (fl[0] & 2u) { ctx->err = "coder pipeline timeout (internal error)"; return W3_E_HIP; }
-        if (fl[3]) { ctx->err = "APM kernel: " + std::to_string(fl[3]) + " stores outside the stage's stream and the sink (W3_TUNING store guard)"; return W3_E_HIP; }
-        if (!(fl[0] & 1u)) break;
-        if (cap_raised) { ctx->err = "stripe overflow at the worst-case bound (internal error)"; return W3_E_HIP; }
-        cap = worst_stripe_cap(block_size);  // rare: a block expanded past 2N+64
-        cap_raised = true;
         ctx->timing.n_recoded_blocks = 0;
     }
     ctx->timing.n_lds_faults = lds_faults;
@@ -957,14 +969,8 @@ static int encode_core(w3_ctx *ctx, JobRef J, const w3_model_spec *spec, const u
         if (evp) HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_TOTAL + 1], s));
         HIPCHK(ctx, hipStreamSynchronize(s));
     }
-    if (two) {
-        ctx->timing.coder_bytes = ptm.coder_bytes + total; ctx->timing.predict_bytes = ptm.predict_bytes;
-        ctx->timing.n_coder_launches = ptm.n_coder_launches; ctx->timing.n_slot_launches = ptm.n_slot_launches;
-    }
-    if (evp) {
-        if (!two) { ctx->timing.generic_ms = elapsed_ev(evp, W3_EV_PREDICT); ctx->timing.pack_ms = d_out ? elapsed_ev(evp, W3_EV_PACK) : 0.f; ctx->timing.total_ms = elapsed_ev(evp, W3_EV_TOTAL); }
-        else collect_timing(evp, J.tp, ps.n_apm > 0, ps.has_slot, d_out != nullptr, ctx->timing);
-    }
+    if (two) fill_timing(ctx, J, ptm, total, ps, evp != nullptr, d_out != nullptr);
+    else if (evp) { ctx->timing.generic_ms = elapsed_ev(evp, W3_EV_PREDICT); ctx->timing.pack_ms = d_out ? elapsed_ev(evp, W3_EV_PACK) : 0.f; ctx->timing.total_ms = elapsed_ev(evp, W3_EV_TOTAL); }
     ctx->timing.n_parts = 1;
     if (d_out && total > out_cap) { ctx->err = "out_cap too small"; return W3_E_NOSPACE; }
     return W3_OK;
@@ -976,7 +982,7 @@ extern "C" int w3_encode_blocks_device(w3_ctx *ctx, const w3_model_spec *spec, c
     if (n && !d_out) return W3_E_INVALID;
     int rc = jobs_idle(ctx);
     if (rc) return rc;
-    return encode_core(ctx, jobref(ctx, 0), spec, d_in, n, block_size, d_out, out_cap, d_block_lens, d_total, stream);
+    return encode_core(ctx, ctx->jobs[0], spec, d_in, n, block_size, d_out, out_cap, d_block_lens, d_total, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -999,24 +1005,11 @@ static bool slot_sorted_by_default(const ParsedSpec &ps, uint32_t nb, size_t blo
     return 32ull * n_slot * n <= (48ull << 30);
 }
 
-// How submitted calls of this spec and size are kept in flight (w3_encode_submit and w3_encode_max_in_flight must agree).
-//   ordered pair   step k's coder beside step k+1's rank kernels, APM stage in between: large inputs of models with
-//                  wide (sorted) leaves AND an APM stage — the bench model: 14,1xx MiB/s against 13,570 free-running;
-//   free-running   every code stage on its own stream as soon as it is submitted: small and medium inputs of any model, and large inputs
-//                  of models WITHOUT rank kernels to put the coder beside (1e9 B: Order0 38,099 -> 52,642 MiB/s with three in flight,
-//                  main.rs's default model 15,578 -> 17,566; order012, wide leaves but no APM stage, 16,038 -> 16,313 with two).
-struct PipelinePlan { bool free_run; int depth; };
-static PipelinePlan pipeline_plan(const ParsedSpec &ps, uint32_t nb, uint32_t tune) {
+// How submitted calls of this spec and size are kept in flight (w3_jobs.h)
+static PipelinePlan pipeline_plan(const ParsedSpec &ps, size_t nb, uint32_t tune) {
     int n_wide = 0;
     for (int l = 0; l < ps.n_leaves; l++) { const int c = leaf_class(ps.leaf[l]); n_wide += c == LEAF_WIDE1 || c == LEAF_WIDE2 || c == LEAF_WAVE; }
-    PipelinePlan p;
-    p.free_run = (nb <= W3_FREE_RUN_BLOCKS || n_wide == 0 || ps.n_apm == 0 || (tune & 8192u)) && !(tune & 4096u);   // (W3_OPT_TUNE bit 12: ordered, 13: free-running, whatever the size)
-    if (ps.has_slot) p.depth = 2;                       // (event records: 32 bytes per input byte and leaf)
-    else if (!p.free_run) p.depth = 2;
-    else if (nb <= W3_FREE_RUN4_BLOCKS) p.depth = W3_MAX_JOBS;
-    else if (nb <= W3_FREE_RUN_BLOCKS) p.depth = 3;
-    else p.depth = n_wide == 0 ? 3 : 2;                 // large inputs: a workspace is 16 bytes per input byte and live leaf (+ 40 per wide leaf)
-    return p;
+    return pipeline_plan(n_wide, ps.n_apm, ps.has_slot, (uint32_t)std::min<size_t>(nb, 0xFFFFFFFFu), tune);
 }
 
 // Does w3_encode_submit only enqueue this call (true), or run it to completion inside the call (false: specs outside the predict kernels,
@@ -1025,7 +1018,7 @@ static bool submit_pipelines(const w3_ctx *ctx, const ParsedSpec &ps, uint32_t n
     const bool two = nb > 0 && twophase_supported(ps, block_size, n) && ctx->opt_path != W3_PATH_GENERIC;
     // Specs with slot-state leaves are pipelined when the leaves run as the sorted replay (w3_slot2.h: no hash maps sized from the memory
     // that happens to be free) — two jobs at most: a job's event records are 32 bytes per input byte and leaf.
-    const bool slot_async = ps.has_slot && slot_sorted_by_default(ps, nb, block_size, n) && !(ctx->tp.variant & (W3_VAR_SLOT_TABLE | W3_VAR_NO_LDS_ATOMICS)) && ctx->tp.lds_order != 0;
+    const bool slot_async = ps.has_slot && slot_sorted_by_default(ps, nb, block_size, n) && !(ctx->opt.variant & (W3_VAR_SLOT_TABLE | W3_VAR_NO_LDS_ATOMICS)) && ctx->lds_order != 0;
     return two && !(ps.has_slot && !slot_async);
 }
 
@@ -1036,48 +1029,44 @@ static int ensure_pipeline(w3_ctx *ctx) {
     if (!ctx->s_pred || !ctx->s_code[W3_MAX_JOBS - 1]) {
         int lo_p = 0, hi_p = 0;
         HIPCHK(ctx, hipDeviceGetStreamPriorityRange(&lo_p, &hi_p));
-        const bool pred_high = (ctx->tp.tune & 1u) != 0;   // W3_OPT_TUNE bit 0
-        const bool plain = !(ctx->tp.tune & (1u | 16u));   // (tuning variants create their own)
+        const bool pred_high = (ctx->opt.tune & 1u) != 0;   // W3_OPT_TUNE bit 0
+        const bool plain = !(ctx->opt.tune & (1u | 16u));   // (tuning variants create their own)
         if (!ctx->s_pred && plain) ctx->s_pred = stream_pool().take(ctx->device * 8L);
         if (!ctx->s_pred) HIPCHK(ctx, hipStreamCreateWithPriority(&ctx->s_pred, hipStreamNonBlocking, pred_high ? hi_p : 0));
         // (created one after the other on one level: HIP deals that level's hardware queues out round-robin, so the W3_MAX_JOBS = 4 code
         // streams get a queue each and the free-running jobs' coders really run side by side)
         for (auto &sc : ctx->s_code) {
             if (!sc && plain) sc = stream_pool().take(ctx->device * 8L + 1);
-            if (!sc) HIPCHK(ctx, hipStreamCreateWithPriority(&sc, hipStreamNonBlocking, (pred_high || (ctx->tp.tune & 16u)) ? 0 : hi_p));
+            if (!sc) HIPCHK(ctx, hipStreamCreateWithPriority(&sc, hipStreamNonBlocking, (pred_high || (ctx->opt.tune & 16u)) ? 0 : hi_p));
         }
         ctx->pooled_streams = plain;
     }
-    for (int j = 0; j < W3_MAX_JOBS; j++) {
-        JobState &st = ctx->js[j];
-        if (!st.ev_done) HIPCHK(ctx, hipEventCreateWithFlags(&st.ev_done, hipEventDisableTiming));
-        if (!st.ev_in) HIPCHK(ctx, hipEventCreateWithFlags(&st.ev_in, hipEventDisableTiming));
-        if (!st.ev_a) HIPCHK(ctx, hipEventCreateWithFlags(&st.ev_a, hipEventDisableTiming));
-        if (!st.ev_apm) HIPCHK(ctx, hipEventCreateWithFlags(&st.ev_apm, hipEventDisableTiming));
-        if (!st.h_status) HIPCHK(ctx, hipHostMalloc((void **)&st.h_status, 32, hipHostMallocDefault));
-    }
-    for (auto &x : ctx->jx)
-        for (auto &e : x.ev)
+    for (auto &J : ctx->jobs) {
+        for (hipEvent_t *e : {&J.ev_done, &J.ev_in, &J.ev_a, &J.ev_apm})
+            if (!*e) HIPCHK(ctx, hipEventCreateWithFlags(e, hipEventDisableTiming));
+        if (!J.h_status) HIPCHK(ctx, hipHostMalloc((void **)&J.h_status, 32, hipHostMallocDefault));
+        for (auto &e : J.ev)
             if (!e) HIPCHK(ctx, hipEventCreate(&e));
+    }
     return W3_OK;
 }
 
 // APM stages + coder + pack + status read-back of an enqueued job, on the code stream
-static int enqueue_code(w3_ctx *ctx, JobRef &J, hipEvent_t wait_ev, hipEvent_t rec_after_apm) {
-    JobState &st = J.st;
-    hipStream_t sp = ctx->s_pred, sc = st.sc;
-    hipEvent_t *evp = st.timed ? J.ev : nullptr;
-    int rc = tp_code_stage(J.tp, sp, sc, st.ps, st.d_in, st.n, st.block_size, st.nb, (uint8_t *)J.stripes.p, st.cap, st.d_block_lens, (uint32_t *)J.flag.p,
-                           wait_ev, rec_after_apm, evp, &st.tm, ctx->err);
+static int enqueue_code(w3_ctx *ctx, Job &J, hipEvent_t wait_ev, hipEvent_t rec_after_apm) {
+    const KeptCall &c = J.call;
+    hipStream_t sp = ctx->s_pred, sc = J.sc;
+    hipEvent_t *evp = J.timed ? J.ev : nullptr;
+    int rc = tp_code_stage(J.tp, sp, sc, c.ps, c.d_in, c.n, c.block_size, J.nb, (uint8_t *)J.stripes.p, J.cap, J.d_block_lens, (uint32_t *)J.flag.p,
+                           wait_ev, rec_after_apm, evp, &J.tm, ctx->err);
     if (rc) return rc;
     if (evp) HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_PACK], sc));
-    rc = run_pack(ctx, J, sc, (const uint8_t *)J.stripes.p, st.cap, st.d_block_lens, st.nb, st.d_out, st.out_cap, st.d_total);
+    rc = run_pack(ctx, J, sc, (const uint8_t *)J.stripes.p, J.cap, J.d_block_lens, J.nb, J.d_out, J.out_cap, J.d_total);
     if (evp) { HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_PACK + 1], sc)); HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_TOTAL + 1], sc)); }
     if (rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(st.h_status, J.flag.p, 16, hipMemcpyDeviceToHost, sc));
-    HIPCHK(ctx, hipMemcpyAsync(st.h_status + 4, st.d_total, 8, hipMemcpyDeviceToHost, sc));
-    HIPCHK(ctx, hipEventRecord(st.ev_done, sc));
-    st.code_pending = false;
+    HIPCHK(ctx, hipMemcpyAsync(J.h_status, J.flag.p, 4 * ST_WORDS, hipMemcpyDeviceToHost, sc));
+    HIPCHK(ctx, hipMemcpyAsync(J.h_status + ST_WORDS, J.d_total, 8, hipMemcpyDeviceToHost, sc));
+    HIPCHK(ctx, hipEventRecord(J.ev_done, sc));
+    J.code_pending = false;
     return W3_OK;
 }
 
@@ -1092,83 +1081,58 @@ extern "C" int w3_encode_submit(w3_ctx *ctx, const w3_model_spec *spec, const ui
     ParsedSpec ps;
     if ((rc = parse_spec(spec, ps))) { ctx->err = "malformed model spec"; return rc; }
     const uint32_t nb = (uint32_t)((n + block_size - 1) / block_size);
-    const PipelinePlan plan = pipeline_plan(ps, nb, ctx->tp.tune);
-    const bool free_run = plan.free_run;
-    const int depth = plan.depth;
-    int in_flight = 0;
-    for (const auto &o : ctx->js) in_flight += o.state != 0;
-    int j = ctx->next_job % depth;
-    if (ctx->js[j].state != 0) {   // (a free slot further on: jobs may be waited for in any order)
-        for (int k = 0; k < depth; k++)
-            if (ctx->js[k].state == 0) { j = k; break; }
-    }
-    if (in_flight >= depth || ctx->js[j].state != 0) {
-        ctx->err = std::to_string(in_flight) + " jobs are in flight already (at most " + std::to_string(depth) + " for an input of this size): w3_encode_wait the oldest one first";
+    const PipelinePlan plan = pipeline_plan(ps, nb, ctx->opt.tune);
+    int busy[W3_MAX_JOBS];
+    for (int k = 0; k < W3_MAX_JOBS; k++) busy[k] = ctx->jobs[k].state;
+    const SlotPick pick = pick_slot(busy, W3_MAX_JOBS, ctx->next_job, plan.depth);
+    if (pick.slot < 0) {
+        ctx->err = std::to_string(pick.in_flight) + " jobs are in flight already (at most " + std::to_string(plan.depth) + " for an input of this size): w3_encode_wait the oldest one first";
         return W3_E_INVALID;
     }
+    const int j = pick.slot;
+    Job &J = ctx->jobs[j];
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (!submit_pipelines(ctx, ps, nb, block_size, n)) {
         // Not pipelined: the lane-per-block kernels (any spec the predict kernels do not cover) and specs whose slot-state leaves walk
         // hash maps in HBM (k_slot: sized from the memory that is free at the time) run to completion here, on job 0's workspace.
-        for (int k = 0; k < W3_MAX_JOBS; k++) {   // let the other jobs' kernels finish first; their status is in pinned memory already
-            if (ctx->js[k].state != 1) continue;
-            if (ctx->js[k].code_pending) { JobRef O = jobref(ctx, k); if ((rc = enqueue_code(ctx, O, nullptr, nullptr))) return rc; }
-            HIPCHK(ctx, hipEventSynchronize(ctx->js[k].ev_done));
-            if (k == 0 && ctx->js[0].timed && !ctx->js[0].tm_snap) {   // job 0's events are about to be recorded again
-                JobRef O = jobref(ctx, 0);
-                memset(&O.st.tm_ev, 0, sizeof O.st.tm_ev);
-                collect_timing(O.ev, O.tp, O.st.has_apm, O.st.has_slot, true, O.st.tm_ev);
-                O.st.tm_snap = true;
+        for (auto &O : ctx->jobs) {   // let the other jobs' kernels finish first; their status is in pinned memory already
+            if (O.state != 1) continue;
+            if (O.code_pending && (rc = enqueue_code(ctx, O, nullptr, nullptr))) return rc;
+            HIPCHK(ctx, hipEventSynchronize(O.ev_done));
+            if (O.index == 0 && O.timed && !O.tm_snap) {   // job 0's events are about to be recorded again
+                memset(&O.tm_ev, 0, sizeof O.tm_ev);
+                collect_timing(O.ev, O.tp, O.call.ps.n_apm > 0, O.call.ps.has_slot, true, O.tm_ev);
+                O.tm_snap = true;
             }
         }
         // Completed by w3_encode_wait like any other job: THAT call returns what the synchronous call returned (W3_E_NOSPACE with
         // d_total = the need included), so a caller that follows the submit / wait contract sees one behaviour for every spec.
         const w3_timing keep = ctx->timing;
-        ctx->js[j].sync_rc = encode_core(ctx, jobref(ctx, 0), spec, d_in, n, block_size, d_out, out_cap, d_block_lens, d_total, stream);
-        ctx->js[j].state = 2; ctx->js[j].tm = ctx->timing;
+        J.sync_rc = encode_core(ctx, ctx->jobs[0], spec, d_in, n, block_size, d_out, out_cap, d_block_lens, d_total, stream);
+        J.state = 2; J.tm = ctx->timing;
         ctx->timing = keep;
         *job = j; ctx->next_job = j + 1; ctx->last_job = j;
         return W3_OK;
     }
     if ((rc = ensure_pipeline(ctx))) return rc;
-    JobRef J = jobref(ctx, j);
-    JobState &st = J.st;
-    // keep the call (the spec and its HuffHistory tables are the caller's memory)
-    st.spec = *spec;
-    if (ps.n_huff) { memcpy(st.huff_copy, ps.huff, sizeof(w3_huff_table) * ps.n_huff); st.spec.huff = st.huff_copy; ps.huff = st.huff_copy; }
-    st.ps = ps;
-    st.d_in = d_in; st.n = n; st.block_size = block_size; st.d_out = d_out; st.out_cap = out_cap; st.d_block_lens = d_block_lens; st.d_total = d_total;
-    st.has_apm = ps.n_apm > 0; st.has_slot = ps.has_slot; st.timed = ctx->opt_timing != 0; st.tm_snap = false;
-    st.nb = nb;
-    st.sc = free_run ? ctx->s_code[j] : ctx->s_code[0];
-    memset(&st.tm, 0, sizeof st.tm);
+    J.call.keep(spec, ps, d_in, n, block_size);
+    J.d_out = d_out; J.out_cap = out_cap; J.d_block_lens = d_block_lens; J.d_total = d_total;
+    J.timed = ctx->opt_timing != 0; J.tm_snap = false;
+    J.nb = nb;
+    J.sc = plan.free_run ? ctx->s_code[j] : ctx->s_code[0];
+    memset(&J.tm, 0, sizeof J.tm);
     hipStream_t sp = ctx->s_pred;
     // after whatever produced d_in on the caller's stream
     hipStream_t s_in = stream ? (hipStream_t)stream : ctx->stream;
-    HIPCHK(ctx, hipEventRecord(st.ev_in, s_in));
-    HIPCHK(ctx, hipStreamWaitEvent(sp, st.ev_in, 0));
-    ENSURE(ctx, J.flag, 16);
-    ENSURE(ctx, J.bits, (size_t)nb * 4);
-    if ((rc = stage_huff_job(ctx, J, sp, ps))) return rc;
-    if (ps.is_cm()) {
-        CmArgs lut;
-        if ((rc = cm_luts(ctx, sp, lut))) return rc;
-        ctx->tp.stretch = lut.stretch; ctx->tp.squash = lut.squash; ctx->tp.st = lut.st;
-    }
-    sync_job_options(ctx, J);
-    if ((rc = attach_aux_streams(ctx, J, j))) return rc;
-    J.tp.half_cu = !(ctx->tp.variant & W3_VAR_FULL_CU);
-    J.tp.verify_calls = st.vcall = verify_call(ctx, n, block_size);   // (counted per shape by the context: a call's job slot does not matter)
-    st.cap = default_stripe_cap(block_size);
-    ENSURE(ctx, J.stripes, (size_t)nb * st.cap);
-    hipEvent_t *evp = st.timed ? J.ev : nullptr;
-    HIPCHK(ctx, hipMemsetAsync(J.flag.p, 0, 16, sp));
+    HIPCHK(ctx, hipEventRecord(J.ev_in, s_in));
+    HIPCHK(ctx, hipStreamWaitEvent(sp, J.ev_in, 0));
+    if ((rc = job_prepare(ctx, J, J.call.ps, sp, true, !(ctx->opt.variant & W3_VAR_FULL_CU), n, block_size, nb))) return rc;
+    J.call.vcall = J.tp.verify_calls;
+    J.cap = default_stripe_cap(block_size);
+    ENSURE(ctx, J.stripes, (size_t)nb * J.cap);
+    hipEvent_t *evp = J.timed ? J.ev : nullptr;
+    HIPCHK(ctx, hipMemsetAsync(J.flag.p, 0, 4 * ST_WORDS, sp));
     if (evp) HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_TOTAL], sp));
-    J.tp.out_bits = (uint32_t *)J.bits.p;
-    J.tp.order_fault = (uint32_t *)J.flag.p + 2;
-#ifdef W3_TUNING
-    J.tp.apm_oob = (uint32_t *)J.flag.p + 3;
-#endif
     // The order in which the two jobs' kernels reach the chip (measured, profiles/r3_pipeline/: kernels that fill the LDS — the
     // partition passes, the time-ordered leaves, k_apm0 — only slow each other down when they share CUs; the rank kernels, bound
     // by their scattered stores, and the coder, one latency chain per lane, run well side by side):
@@ -1176,30 +1140,28 @@ extern "C" int w3_encode_submit(w3_ctx *ctx, const w3_model_spec *spec, const ui
     // So the other job's code stage is enqueued here, between this job's two predict halves (W3_OPT_TUNE bit 2: no such order).
     // Free-running jobs (small inputs) need no such order: the chip is mostly idle while a call is coded, so every job's code stage
     // goes to its own stream at once and the coders of up to W3_MAX_JOBS calls run side by side (each a latency chain on a few CUs).
-    const bool ordered = !(ctx->tp.tune & 4u) && !free_run;
-    const int prev = ctx->last_job >= 0 && ctx->last_job != j && ctx->js[ctx->last_job].state == 1 && ctx->js[ctx->last_job].code_pending ? ctx->last_job : -1;
-    if (prev >= 0 && !ordered) {   // (an ordered job before a free-running one: its code stage goes out now)
-        JobRef O = jobref(ctx, prev);
-        if ((rc = enqueue_code(ctx, O, nullptr, nullptr))) return rc;
-    }
-    rc = twophase_predict_a(J.tp, sp, ps, d_in, n, block_size, nb, evp, ctx->err, ordered);
+    const bool ordered = !(ctx->opt.tune & 4u) && !plan.free_run;
+    Job *prev = ctx->last_job >= 0 && ctx->last_job != j ? &ctx->jobs[ctx->last_job] : nullptr;
+    if (prev && !(prev->state == 1 && prev->code_pending)) prev = nullptr;
+    if (prev && !ordered && (rc = enqueue_code(ctx, *prev, nullptr, nullptr))) return rc;   // (an ordered job before a free-running one: its code stage goes out now)
+    const ParsedSpec &kps = J.call.ps;
+    rc = twophase_predict_a(J.tp, sp, kps, d_in, n, block_size, nb, evp, ctx->err, ordered);
     if (!rc && ordered) {
-        HIPCHK(ctx, hipEventRecord(st.ev_a, sp));
-        if (prev >= 0) {
-            JobRef O = jobref(ctx, prev);
-            rc = enqueue_code(ctx, O, st.ev_a, O.st.ev_apm);
-            if (!rc) HIPCHK(ctx, hipStreamWaitEvent(sp, O.st.ev_apm, 0));
+        HIPCHK(ctx, hipEventRecord(J.ev_a, sp));
+        if (prev) {
+            rc = enqueue_code(ctx, *prev, J.ev_a, prev->ev_apm);
+            if (!rc) HIPCHK(ctx, hipStreamWaitEvent(sp, prev->ev_apm, 0));
         }
     }
-    if (!rc) rc = twophase_predict_b(J.tp, sp, ps, d_in, n, block_size, nb, tp_plan(J.tp, ps).need_P, nullptr, evp, &st.tm, ctx->err);
-    if (!rc) rc = tp_after_predict(J.tp, sp, ps, d_in, n, block_size, nb, (uint32_t *)J.flag.p, ctx->err);
+    if (!rc) rc = twophase_predict_b(J.tp, sp, kps, d_in, n, block_size, nb, tp_plan(J.tp, kps).need_P, nullptr, evp, &J.tm, ctx->err);
+    if (!rc) rc = tp_after_predict(J.tp, sp, kps, d_in, n, block_size, nb, (uint32_t *)J.flag.p, ctx->err);
     if (!rc) {
-        st.state = 1; st.code_pending = true;
+        J.state = 1; J.code_pending = true;
         if (!ordered) rc = enqueue_code(ctx, J, nullptr, nullptr);
     }
     if (rc) {   // leave nothing of either job running behind an error return
         (void)hipDeviceSynchronize();
-        st.state = 0; st.code_pending = false;
+        J.state = 0; J.code_pending = false;
         return rc;
     }
     *job = j; ctx->next_job = j + 1; ctx->last_job = j;
@@ -1212,55 +1174,48 @@ extern "C" int w3_encode_max_in_flight(const w3_model_spec *spec, size_t n, size
     ParsedSpec ps;   // (no spec: a model with wide leaves and an APM stage, the most conservative answer)
     if (spec) { if (parse_spec(spec, ps)) return 0; }
     else { ps.n_leaves = 1; ps.leaf[0] = w3_node{}; ps.leaf[0].kind = W3_NODE_ORDERN; ps.leaf[0].bits = 19; ps.leaf[0].align = 3; ps.n_apm = 1; }
-    return pipeline_plan(ps, (uint32_t)std::min<size_t>(nb, 0xFFFFFFFFu), 0u).depth;
+    return pipeline_plan(ps, nb, 0u).depth;
 }
 
 extern "C" int w3_encode_wait(w3_ctx *ctx, int job) {
     if (!ctx || job < 0 || job >= W3_MAX_JOBS) return W3_E_INVALID;
-    JobRef J = jobref(ctx, job);
-    JobState &st = J.st;
-    if (st.state == 0) { ctx->err = "no such job in flight"; return W3_E_INVALID; }
-    st.total_valid = false;
+    Job &J = ctx->jobs[job];
+    if (J.state == 0) { ctx->err = "no such job in flight"; return W3_E_INVALID; }
+    J.total_valid = false;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (st.state == 2) { st.state = 0; ctx->timing = st.tm; return st.sync_rc; }
-    if (st.code_pending) {   // no later submit has placed this job's code stage: it goes out now
+    if (J.state == 2) { J.state = 0; ctx->timing = J.tm; return J.sync_rc; }
+    if (J.code_pending) {   // no later submit has placed this job's code stage: it goes out now
         const int rc = enqueue_code(ctx, J, nullptr, nullptr);
-        if (rc) { (void)hipDeviceSynchronize(); st.state = 0; st.code_pending = false; return rc; }
+        if (rc) { (void)hipDeviceSynchronize(); J.state = 0; J.code_pending = false; return rc; }
     }
-    HIPCHK(ctx, hipEventSynchronize(st.ev_done));
-    st.state = 0;
-    const uint32_t f0 = st.h_status[0], redo = st.h_status[1], mism = st.h_status[2];
+    HIPCHK(ctx, hipEventSynchronize(J.ev_done));
+    J.state = 0;
+    JobStatus st;
     uint64_t total;
-    memcpy(&total, st.h_status + 4, 8);
-    if ((f0 & 2u) && !mism) { ctx->err = "coder pipeline timeout (internal error)"; return W3_E_HIP; }
-    if (st.h_status[3]) { ctx->err = "APM kernel: stores outside the stage's stream and the sink (W3_TUNING store guard)"; return W3_E_HIP; }
-    if (f0 || redo || mism) {
+    memcpy(st.w, J.h_status, sizeof st.w);
+    memcpy(&total, J.h_status + ST_WORDS, 8);
+    const KeptCall &c = J.call;
+    switch (const JobAction act = job_classify_waited(st)) {
+    case JOB_DONE: break;
+    case JOB_ERR_TIMEOUT: ctx->err = "coder pipeline timeout (internal error)"; return W3_E_HIP;
+    case JOB_ERR_APM_OOB: ctx->err = "APM kernel: stores outside the stage's stream and the sink (W3_TUNING store guard)"; return W3_E_HIP;
+    default: {
         // Rare: a stripe overflowed the 2N+64 bound, the fast coder handed blocks back, or the sampled verification saw the LDS-add
         // rounds misbehave.  Let the other job's kernels finish (its output is complete then, its status in pinned memory) and
         // run this call again synchronously on this job's workspace: encode_core's own retry loop deals with each case.
         HIPCHK(ctx, hipDeviceSynchronize());
-        if (mism) {
-            ctx->tp.variant |= W3_VAR_NO_LDS_ATOMICS; ctx->tp.lds_order = 0;
-            for (auto &x : ctx->jx) { x.tp.variant |= W3_VAR_NO_LDS_ATOMICS; x.tp.lds_order = 0; }
-        }
-        VcallPin pin(ctx, st.vcall);   // (the same call: the same rotation)
-        const int rc = encode_core(ctx, J, &st.spec, st.d_in, st.n, st.block_size, st.d_out, st.out_cap, st.d_block_lens, st.d_total, ctx->stream);
-        ctx->timing.n_lds_faults += mism;
+        if (act == JOB_BALLOT_ROUNDS) use_ballot_rounds(ctx);
+        VcallPin pin(ctx, c.vcall);   // (the same call: the same rotation)
+        const int rc = encode_core(ctx, J, &c.spec, c.d_in, c.n, c.block_size, J.d_out, J.out_cap, J.d_block_lens, J.d_total, ctx->stream);
+        ctx->timing.n_lds_faults += st.order_fault();
         return rc;
     }
-    st.total_out = total; st.total_valid = true;
+    }
+    J.total_out = total; J.total_valid = true;
     memset(&ctx->timing, 0, sizeof ctx->timing);
-    ctx->timing.path = W3_PATH_TWOPHASE;
-    ctx->timing.coder_bytes = st.tm.coder_bytes + total; ctx->timing.predict_bytes = st.tm.predict_bytes;
-    ctx->timing.n_coder_launches = st.tm.n_coder_launches; ctx->timing.n_slot_launches = st.tm.n_slot_launches;
-    ctx->timing.n_parts = 1;
-    if (st.timed && st.tm_snap) {
-        const w3_timing &e = st.tm_ev;
-        ctx->timing.predict_ms = e.predict_ms; ctx->timing.coder_ms = e.coder_ms; ctx->timing.apm_ms = e.apm_ms; ctx->timing.slot_ms = e.slot_ms;
-        ctx->timing.achash_ms = e.achash_ms; ctx->timing.n_wide = e.n_wide; ctx->timing.small_ms = e.small_ms; ctx->timing.pack_ms = e.pack_ms; ctx->timing.total_ms = e.total_ms;
-        memcpy(ctx->timing.part_ms, e.part_ms, sizeof e.part_ms); memcpy(ctx->timing.rank_ms, e.rank_ms, sizeof e.rank_ms);
-    } else if (st.timed) collect_timing(J.ev, J.tp, st.has_apm, st.has_slot, true, ctx->timing);
-    if (total > st.out_cap) { ctx->err = "out_cap too small"; return W3_E_NOSPACE; }
+    if (J.timed && J.tm_snap) ctx->timing = J.tm_ev;   // (the event times; everything else in it is zero)
+    fill_timing(ctx, J, J.tm, total, c.ps, J.timed && !J.tm_snap, true);
+    if (total > J.out_cap) { ctx->err = "out_cap too small"; return W3_E_NOSPACE; }
     return W3_OK;
 }
 
@@ -1279,7 +1234,7 @@ static int host_streams(w3_ctx *ctx) {
     // copy stream that lands on the predict stream's queue holds that call's kernels back for the length of a copy (measured: 84.5 ms
     // per call with two copy streams of their own against 72.6 with 8 hardware queues in the environment, profiles/r4_host_path/).
     // W3_OPT_TUNE bit 16: two copy streams of their own, one per direction (for hosts that do raise GPU_MAX_HW_QUEUES).
-    if (ctx->tp.tune & 65536u) {
+    if (ctx->opt.tune & 65536u) {
         if (!ctx->s_h2d_own) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->s_h2d_own, hipStreamNonBlocking));
         if (!ctx->s_d2h_own) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->s_d2h_own, hipStreamNonBlocking));
         ctx->s_h2d = ctx->s_h2d_own; ctx->s_d2h = ctx->s_d2h_own;
@@ -1302,15 +1257,29 @@ static void host_start_pending(w3_ctx *ctx) {
         for (auto &x : ctx->hj)
             if (x.state == 1 && (!h || x.seq < h->seq)) h = &x;
         if (!h) return;
+        const KeptCall &c = h->call;
         int in_flight = 0;
-        for (const auto &o : ctx->js) in_flight += o.state != 0;
-        if (in_flight >= w3_encode_max_in_flight(&h->spec, h->n, h->block_size)) return;
+        for (const auto &o : ctx->jobs) in_flight += o.state != 0;
+        if (in_flight >= pipeline_plan(c.ps, h->nb, 0u).depth) return;
         // (the job starts behind everything enqueued on the H2D stream so far: its own input was the last of it)
-        VcallPin pin(ctx, h->vcall);
-        h->rc = w3_encode_submit(ctx, &h->spec, (const uint8_t *)h->d_in.p, h->n, h->block_size, (uint8_t *)h->d_out.p, h->dcap,
+        VcallPin pin(ctx, c.vcall);
+        h->rc = w3_encode_submit(ctx, &c.spec, c.d_in, c.n, c.block_size, (uint8_t *)h->d_out.p, h->dcap,
                                  (uint32_t *)h->d_lens.p, (uint64_t *)h->d_total.p, ctx->s_h2d, &h->djob);
         h->state = h->rc ? 3 : 2;   // (a refused submit is reported by the wait)
     }
+}
+
+// A call whose output went beyond the realistic bound its device buffer was sized for (adversarial input: up to 16 n) is encoded once
+// more, alone, with the room it asked for: into `out`, grown to `need` bytes.  djob: the slot w3_encode_submit gave it.
+static int redo_with_room(w3_ctx *ctx, const KeptCall &c, int djob, uint64_t vcall, DevBuf &out, size_t &cap, uint64_t need, DevBuf &lens, DevBuf &total) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipDeviceSynchronize());   // (the other jobs' kernels: their outputs are complete afterwards, their status words in pinned memory)
+    ENSURE(ctx, out, (size_t)need);
+    cap = (size_t)need;
+    const uint32_t nb = (uint32_t)((c.n + c.block_size - 1) / c.block_size);
+    Job &J = ctx->jobs[submit_pipelines(ctx, c.ps, nb, c.block_size, c.n) ? djob : 0];   // (what w3_encode_submit ran synchronously ran on job 0)
+    VcallPin pin(ctx, vcall);
+    return encode_core(ctx, J, &c.spec, c.d_in, c.n, c.block_size, (uint8_t *)out.p, cap, (uint32_t *)lens.p, (uint64_t *)total.p, ctx->stream);
 }
 
 // state 2 -> 3: wait for the job's encode; rc and the compressed size are known afterwards
@@ -1325,28 +1294,13 @@ static void host_finish_device(w3_ctx *ctx, HostJob &h) {
         return W3_OK;
     };
     if (h.rc == W3_OK || h.rc == W3_E_NOSPACE) {
-        const JobState &ds = ctx->js[h.djob];
+        const Job &ds = ctx->jobs[h.djob];
         if (ds.total_valid) h.total = ds.total_out;   // (the usual case: no device access, no wait for a copy that is in flight on the copy stream)
         else { const int r = read_total(); if (r) h.rc = r; }
     }
-    if (h.rc == W3_E_NOSPACE && h.total > h.dcap) {
-        // The device buffer is sized for the realistic bound (2 n + 64 per block: the stripes' own); a call beyond it (adversarial
-        // input: up to 16 n) is encoded again, alone, with the room it asked for.
-        auto redo = [&]() -> int {
-            HIPCHK(ctx, hipDeviceSynchronize());   // (the other jobs' kernels: their outputs are complete afterwards, their status words in pinned memory)
-            ENSURE(ctx, h.d_out, (size_t)h.total);
-            h.dcap = (size_t)h.total;
-            ParsedSpec ps;
-            int rc = parse_spec(&h.spec, ps);
-            if (rc) return rc;
-            const int slot = submit_pipelines(ctx, ps, (uint32_t)h.nb, h.block_size, h.n) ? h.djob : 0;
-            VcallPin pin(ctx, h.vcall);
-            rc = encode_core(ctx, jobref(ctx, slot), &h.spec, (const uint8_t *)h.d_in.p, h.n, h.block_size, (uint8_t *)h.d_out.p, h.dcap,
-                             (uint32_t *)h.d_lens.p, (uint64_t *)h.d_total.p, ctx->stream);
-            if (rc) return rc;
-            return read_total();
-        };
-        h.rc = redo();
+    if (h.rc == W3_E_NOSPACE && h.total > h.dcap) {   // (the device buffer is sized for 2 n + 64 per block, the stripes' own bound)
+        h.rc = redo_with_room(ctx, h.call, h.djob, h.call.vcall, h.d_out, h.dcap, h.total, h.d_lens, h.d_total);
+        if (!h.rc) h.rc = read_total();
     }
 }
 
@@ -1356,22 +1310,18 @@ static int host_submit_core(w3_ctx *ctx, const w3_model_spec *spec, const Parsed
     int rc = host_streams(ctx);
     if (rc) return rc;
     const size_t nb = (n + block_size - 1) / block_size;
-    int busy = 0, slot = -1;
-    for (int k = 0; k < W3_MAX_HOST_JOBS; k++) {
-        if (ctx->hj[k].state != 0) busy++;
-        else if (slot < 0) slot = k;
-    }
+    int busy[W3_MAX_HOST_JOBS];
+    for (int k = 0; k < W3_MAX_HOST_JOBS; k++) busy[k] = ctx->hj[k].state;
     const int depth = host_depth(spec, n, block_size);
-    if (busy >= depth || slot < 0) {
-        ctx->err = std::to_string(busy) + " host-buffer jobs are in flight already (at most " + std::to_string(depth) + " for an input of this size): w3_encode_host_wait the oldest one first";
+    const SlotPick pick = pick_slot(busy, W3_MAX_HOST_JOBS, 0, depth);   // (the first free slot)
+    const int slot = pick.slot;
+    if (slot < 0) {
+        ctx->err = std::to_string(pick.in_flight) + " host-buffer jobs are in flight already (at most " + std::to_string(depth) + " for an input of this size): w3_encode_host_wait the oldest one first";
         return W3_E_INVALID;
     }
     HostJob &h = ctx->hj[slot];
-    h.spec = *spec;   // (the spec and its HuffHistory tables are the caller's memory)
-    if (ps.n_huff) { memcpy(h.huff_copy, ps.huff, sizeof(w3_huff_table) * ps.n_huff); h.spec.huff = h.huff_copy; }
-    h.n = n; h.block_size = block_size; h.nb = nb; h.out = out; h.out_cap = out_cap; h.block_lens = block_lens;
+    h.nb = nb; h.out = out; h.out_cap = out_cap; h.block_lens = block_lens;
     h.djob = -1; h.rc = W3_OK; h.total = 0;
-    h.vcall = vcall >= 0 ? (uint64_t)vcall : verify_call(ctx, n, block_size);
     memset(&h.tm, 0, sizeof h.tm);
     // the device output buffer: the realistic bound, never more than the hard one (a call beyond it is redone: host_finish_device)
     h.dcap = std::min<size_t>(w3_max_compressed_size(n, block_size), 2 * n + 64 * nb + 64);
@@ -1379,6 +1329,8 @@ static int host_submit_core(w3_ctx *ctx, const w3_model_spec *spec, const Parsed
     ENSURE(ctx, h.d_out, std::max<size_t>(h.dcap, 16));
     ENSURE(ctx, h.d_lens, std::max<size_t>(nb * 4, 16));
     ENSURE(ctx, h.d_total, 8);
+    h.call.keep(spec, ps, (const uint8_t *)h.d_in.p, n, block_size);
+    h.call.vcall = vcall >= 0 ? (uint64_t)vcall : verify_call(ctx, n, block_size);
     HIPCHK(ctx, hipMemcpyAsync(h.d_in.p, in, n, hipMemcpyHostToDevice, ctx->s_h2d));
     h.seq = ++ctx->hseq;
     h.state = 1;
@@ -1434,10 +1386,10 @@ extern "C" int w3_encode_host_submit(w3_ctx *ctx, const w3_model_spec *spec, con
     ParsedSpec ps;
     if ((rc = parse_spec(spec, ps))) { ctx->err = "malformed model spec"; return rc; }
     if (n == 0 || !in || !block_lens) { ctx->err = "w3_encode_host_submit needs input and a length table"; return W3_E_INVALID; }
-    for (const auto &st : ctx->js)   // (the two levels are not mixed: the host jobs count the device job slots as theirs)
-        if (st.state != 0) {
+    for (const auto &J : ctx->jobs)   // (the two levels are not mixed: the host jobs count the device job slots as theirs)
+        if (J.state != 0) {
             bool ours = false;
-            for (const auto &h : ctx->hj) ours |= h.state == 2 && &ctx->js[h.djob] == &st;
+            for (const auto &h : ctx->hj) ours |= h.state == 2 && h.djob == J.index;
             if (!ours) { ctx->err = "w3_encode_submit jobs are in flight on this context: w3_encode_wait them first"; return W3_E_INVALID; }
         }
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -1465,10 +1417,10 @@ extern "C" int w3_encode_stats_device(w3_ctx *ctx, const w3_model_spec *spec, co
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if ((rc = jobs_idle(ctx))) return rc;
     ENSURE(ctx, ctx->lens, nb * 4);
-    rc = encode_core(ctx, jobref(ctx, 0), spec, d_in, n, block_size, nullptr, 0, (uint32_t *)ctx->lens.p, nullptr, stream);
+    rc = encode_core(ctx, ctx->jobs[0], spec, d_in, n, block_size, nullptr, 0, (uint32_t *)ctx->lens.p, nullptr, stream);
     if (rc) return rc;
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(d_block_bits, ctx->bits.p, nb * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(d_block_bits, ctx->jobs[0].bits.p, nb * 4, hipMemcpyDeviceToDevice, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
     return W3_OK;
 }
@@ -1484,9 +1436,9 @@ extern "C" int w3_encode_stats(w3_ctx *ctx, const w3_model_spec *spec, const uin
     ENSURE(ctx, ctx->io_in, n);
     ENSURE(ctx, ctx->lens, nb * 4);
     HIPCHK(ctx, hipMemcpyAsync(ctx->io_in.p, in, n, hipMemcpyHostToDevice, ctx->stream));
-    rc = encode_core(ctx, jobref(ctx, 0), spec, (const uint8_t *)ctx->io_in.p, n, block_size, nullptr, 0, (uint32_t *)ctx->lens.p, nullptr, ctx->stream);
+    rc = encode_core(ctx, ctx->jobs[0], spec, (const uint8_t *)ctx->io_in.p, n, block_size, nullptr, 0, (uint32_t *)ctx->lens.p, nullptr, ctx->stream);
     if (rc) return rc;
-    HIPCHK(ctx, hipMemcpy(block_bits, ctx->bits.p, nb * 4, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(block_bits, ctx->jobs[0].bits.p, nb * 4, hipMemcpyDeviceToHost));
     return W3_OK;
 }
 
@@ -1617,7 +1569,7 @@ extern "C" int w3_crc32_verify_device(w3_ctx *ctx, const uint8_t *d_data, size_t
 //   - calls that w3_encode_submit would run synchronously (lane-per-block specs, slot leaves on hash maps in HBM): one piece — they
 //     take hundreds of milliseconds per GB, PCIe is a few percent of that;
 //   - up to W3_FREE_RUN4_BLOCKS blocks: one piece (four coders of such pieces overlap, but one call has only one);
-//   - beyond: pieces of at most W3_FREE_RUN4_BLOCKS blocks, equal in size — the four-in-flight regime of DESIGN.md 2.8
+//   - beyond: pieces of at most W3_FREE_RUN4_BLOCKS blocks, equal in size — the four-in-flight regime of DESIGN.md 3.3
 //     (measured at 1e9 B from pinned memory, tools/host_api_rate.py: DESIGN.md section 5).
 // W3_OPT_HOST_CHUNK_BLOCKS overrides the piece size (tests: ragged pieces; measurements).
 // blocks per device call of a host-buffer entry point whose input exceeds what one device call handles (check_args): 2 GiB worth
@@ -2282,7 +2234,7 @@ extern "C" int w3_encode_blocks_sharded_device(w3_ctx *const *ctxs, int n_ctx, c
                         ENSURE(c, c->io_out, cap);
                         ENSURE(c, c->lens, nbs[r] * 4);
                         ENSURE(c, c->total, 8);
-                        int rc = encode_core(c, jobref(c, 0), spec, d_in[r], n[r], block_size, (uint8_t *)c->io_out.p, cap, (uint32_t *)c->lens.p, (uint64_t *)c->total.p, nullptr);
+                        int rc = encode_core(c, c->jobs[0], spec, d_in[r], n[r], block_size, (uint8_t *)c->io_out.p, cap, (uint32_t *)c->lens.p, (uint64_t *)c->total.p, nullptr);
                         uint64_t t = 0;
                         if (rc == W3_OK || rc == W3_E_NOSPACE) HIPCHK(c, hipMemcpy(&t, c->total.p, 8, hipMemcpyDeviceToHost));
                         totals[r] = t;
@@ -2363,16 +2315,14 @@ extern "C" int w3_encode_sharded_submit(w3_ctx *const *ctxs, int n_ctx, const w3
     }
     if (nb_total == 0) { ctxs[0]->err = "nothing to encode"; return W3_E_INVALID; }
     // the same slot on every context; as many steps in flight as the smallest w3_encode_max_in_flight among the shards
-    int slot = -1, busy = 0;
-    for (int k = 0; k < W3_MAX_JOBS; k++) {
-        bool free_everywhere = true, used = false;
-        for (int r = 0; r < n_ctx; r++) { free_everywhere &= ctxs[r]->ss[k].state == 0; used |= ctxs[r]->ss[k].state != 0; }
-        busy += used;
-        if (free_everywhere && slot < 0) slot = k;
-    }
+    int busy[W3_MAX_JOBS] = {};   // (a slot is taken while any context holds a shard in it)
+    for (int k = 0; k < W3_MAX_JOBS; k++)
+        for (int r = 0; r < n_ctx; r++) busy[k] |= ctxs[r]->ss[k].state;
     const int depth = w3_encode_sharded_max_in_flight(spec, n, n_ctx, block_size);
-    if (slot < 0 || busy >= depth) {
-        ctxs[0]->err = std::to_string(busy) + " sharded steps are in flight already (at most " + std::to_string(depth) + " for shards of this size): w3_encode_sharded_wait the oldest one first";
+    const SlotPick pick = pick_slot(busy, W3_MAX_JOBS, 0, depth);   // (the first free slot)
+    const int slot = pick.slot;
+    if (slot < 0) {
+        ctxs[0]->err = std::to_string(pick.in_flight) + " sharded steps are in flight already (at most " + std::to_string(depth) + " for shards of this size): w3_encode_sharded_wait the oldest one first";
         return W3_E_INVALID;
     }
     for (int r = 0; r < n_ctx; r++) {
@@ -2380,15 +2330,14 @@ extern "C" int w3_encode_sharded_submit(w3_ctx *const *ctxs, int n_ctx, const w3
         w3_ctx::ShardSlot &x = c->ss[slot];
         auto body = [&]() -> int {
             HIPCHK(c, hipSetDevice(c->device));
-            x.nb = (n[r] + block_size - 1) / block_size; x.n = n[r]; x.d_in = d_in[r]; x.block_size = block_size; x.djob = -1;
-            x.spec = *spec;
-            if (ps.n_huff) { memcpy(x.huff_copy, ps.huff, sizeof(w3_huff_table) * ps.n_huff); x.spec.huff = x.huff_copy; }
+            x.nb = (n[r] + block_size - 1) / block_size; x.djob = -1;
+            x.call.keep(spec, ps, d_in[r], n[r], block_size);
             ENSURE(c, x.total, 8);
             if (!x.nb) { HIPCHK(c, hipMemsetAsync(x.total.p, 0, 8, c->stream)); return W3_OK; }
             x.cap = n[r] + n[r] / 4 + 64 * x.nb + 1024;   // realistic bound; a shard beyond it is redone with the room it asks for (the wait)
             ENSURE(c, x.out, x.cap);
             ENSURE(c, x.lens, x.nb * 4);
-            return w3_encode_submit(c, &x.spec, d_in[r], n[r], block_size, (uint8_t *)x.out.p, x.cap, (uint32_t *)x.lens.p, (uint64_t *)x.total.p, nullptr, &x.djob);
+            return w3_encode_submit(c, &x.call.spec, d_in[r], n[r], block_size, (uint8_t *)x.out.p, x.cap, (uint32_t *)x.lens.p, (uint64_t *)x.total.p, nullptr, &x.djob);
         };
         rc = body();
         if (rc) {   // leave nothing in flight behind an error: the shards submitted so far are completed and dropped
@@ -2431,18 +2380,13 @@ extern "C" int w3_encode_sharded_wait(w3_ctx *const *ctxs, int n_ctx, int sjob, 
             if (x.djob < 0) return W3_OK;
             int rc1 = w3_encode_wait(c, x.djob);
             uint64_t t = 0;
-            const JobState &ds = c->js[x.djob];
+            const Job &ds = c->jobs[x.djob];
             if (rc1 == W3_OK || rc1 == W3_E_NOSPACE) {
                 if (ds.total_valid) t = ds.total_out;
                 else { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, hipMemcpy(&t, x.total.p, 8, hipMemcpyDeviceToHost)); }
             }
-            if (rc1 == W3_E_NOSPACE && t > x.cap) {   // beyond the realistic bound: once more, alone, with the room it asked for
-                HIPCHK(c, hipSetDevice(c->device));
-                HIPCHK(c, hipDeviceSynchronize());
-                ENSURE(c, x.out, (size_t)t);
-                x.cap = (size_t)t;
-                VcallPin pin(c, ds.vcall);
-                rc1 = encode_core(c, jobref(c, x.djob), &x.spec, x.d_in, x.n, x.block_size, (uint8_t *)x.out.p, x.cap, (uint32_t *)x.lens.p, (uint64_t *)x.total.p, c->stream);
+            if (rc1 == W3_E_NOSPACE && t > x.cap) {
+                rc1 = redo_with_room(c, x.call, x.djob, ds.call.vcall, x.out, x.cap, t, x.lens, x.total);
                 if (rc1 == W3_OK) HIPCHK(c, hipMemcpy(&t, x.total.p, 8, hipMemcpyDeviceToHost));
             }
             totals[r] = t;
@@ -2791,7 +2735,7 @@ static int aoh_twophase_run(w3_ctx *ctx, hipStream_t s, AohTwoArgs a, AohPrep &P
     a.tables = base + meta; a.table_stride = tk.stride;
     a.ctx_mask = (uint32_t)((1ull << ctx_bits) - 1ull); a.use_hash = tk.use_hash; a.hash_slots = tk.use_hash ? (uint32_t)tk.slots : 0u;
     a.P = (uint16_t *)(base + o_P); a.str = base + o_str;
-    hipEvent_t *evp = ctx->opt_timing ? ctx->ev : nullptr;
+    hipEvent_t *evp = ctx->opt_timing ? ctx->jobs[0].ev : nullptr;
     for (const AohBatch &bt : plan.batches) {   // (the batches share the string area and P: stream order keeps them apart)
         a.first_block = bt.first; a.count = bt.count;
         if (evp) HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_PREDICT], s));
@@ -2815,7 +2759,7 @@ static int aoh_twophase_run(w3_ctx *ctx, hipStream_t s, AohTwoArgs a, AohPrep &P
     return W3_OK;
 }
 
-// Code blocks [0, nb) of d_in into ctx->stripes (stride cap_out), lengths to d_lens; d_bits (or null) gets the ACStats bit counts.
+// Code blocks [0, nb) of d_in into ctx->jobs[0].stripes (stride cap_out), lengths to d_lens; d_bits (or null) gets the ACStats bit counts.
 // two: the form the call took (aoh_takes_twophase).
 static int aoh_encode_stripes(w3_ctx *ctx, hipStream_t s, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *d_in, size_t n, size_t block_size,
                               uint32_t nb, uint32_t *d_lens, uint32_t *d_bits, uint32_t &cap_out, bool &two) {
@@ -2830,18 +2774,18 @@ static int aoh_encode_stripes(w3_ctx *ctx, hipStream_t s, const w3_huff_code *co
     const uint64_t worst = (16 * l_bytes + 16 + 15) / 16 * 16;
     if (worst > 0xFFFFFFF0ull) { ctx->err = "block too large for the worst-case stripe"; return W3_E_UNSUPPORTED; }
     uint64_t cap = std::min<uint64_t>((2 * l_bytes + 64 + 15) / 16 * 16, worst);
-    ENSURE(ctx, ctx->flag, 16);
+    ENSURE(ctx, ctx->jobs[0].flag, 16);
     std::vector<AohCfg> cfg(1);
     std::vector<uint64_t> steps(1, P.max_l[0]);
     for (int attempt = 0; attempt < 2; attempt++) {
-        ENSURE(ctx, ctx->stripes, (size_t)nb * cap);
-        HIPCHK(ctx, hipMemsetAsync(ctx->flag.p, 0, 16, s));
+        ENSURE(ctx, ctx->jobs[0].stripes, (size_t)nb * cap);
+        HIPCHK(ctx, hipMemsetAsync(ctx->jobs[0].flag.p, 0, 16, s));
         if (two) {
             ctx->timing = tm0;
             AohTwoArgs t;
             memset(&t, 0, sizeof t);
             t.in = d_in; t.n = n; t.block_size = (uint32_t)block_size;
-            t.stripes = (uint8_t *)ctx->stripes.p; t.stripe_cap = (uint32_t)cap; t.out_len = d_lens; t.overflow = (uint32_t *)ctx->flag.p; t.out_bits = d_bits;
+            t.stripes = (uint8_t *)ctx->jobs[0].stripes.p; t.stripe_cap = (uint32_t)cap; t.out_len = d_lens; t.overflow = (uint32_t *)ctx->jobs[0].flag.p; t.out_bits = d_bits;
             if ((rc = aoh_twophase_run<false>(ctx, s, t, P, ctx_bits, nb))) return rc;
         } else {
             memset(&cfg[0], 0, sizeof cfg[0]);
@@ -2849,11 +2793,11 @@ static int aoh_encode_stripes(w3_ctx *ctx, hipStream_t s, const w3_huff_code *co
             AohArgs a;
             memset(&a, 0, sizeof a);
             a.in = d_in; a.n = n; a.block_size = (uint32_t)block_size;
-            a.stripes = (uint8_t *)ctx->stripes.p; a.stripe_cap = (uint32_t)cap; a.out_len = d_lens; a.overflow = (uint32_t *)ctx->flag.p; a.out_bits = d_bits;
+            a.stripes = (uint8_t *)ctx->jobs[0].stripes.p; a.stripe_cap = (uint32_t)cap; a.out_len = d_lens; a.overflow = (uint32_t *)ctx->jobs[0].flag.p; a.out_bits = d_bits;
             if ((rc = aoh_launch<AOH_ENCODE>(ctx, s, a, P, cfg, steps, nb))) return rc;
         }
         uint32_t fl = 0;
-        HIPCHK(ctx, hipMemcpyAsync(&fl, ctx->flag.p, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(&fl, ctx->jobs[0].flag.p, 4, hipMemcpyDeviceToHost, s));
         HIPCHK(ctx, hipStreamSynchronize(s));
         if (!fl) { cap_out = (uint32_t)cap; return W3_OK; }
         if (cap == worst) break;
@@ -2867,9 +2811,9 @@ static int aoh_encode_stripes(w3_ctx *ctx, hipStream_t s, const w3_huff_code *co
 static void aoh_timing(w3_ctx *ctx, bool packed, bool two) {
     ctx->timing.path = two ? W3_PATH_TWOPHASE : W3_PATH_GENERIC; ctx->timing.n_parts = 1;
     if (!ctx->opt_timing) return;
-    ctx->timing.generic_ms = two ? 0.f : elapsed_ev(ctx->ev, W3_EV_PREDICT);
-    ctx->timing.pack_ms = packed ? elapsed_ev(ctx->ev, W3_EV_PACK) : 0.f;
-    ctx->timing.total_ms = elapsed_ev(ctx->ev, W3_EV_TOTAL);
+    ctx->timing.generic_ms = two ? 0.f : elapsed_ev(ctx->jobs[0].ev, W3_EV_PREDICT);
+    ctx->timing.pack_ms = packed ? elapsed_ev(ctx->jobs[0].ev, W3_EV_PACK) : 0.f;
+    ctx->timing.total_ms = elapsed_ev(ctx->jobs[0].ev, W3_EV_TOTAL);
 }
 
 extern "C" int w3_aoh_encode_blocks_device(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *d_in, size_t n, size_t block_size,
@@ -2888,14 +2832,14 @@ extern "C" int w3_aoh_encode_blocks_device(w3_ctx *ctx, const w3_huff_code *code
         return W3_OK;
     }
     if (!d_in || !d_block_lens || !d_out) return W3_E_INVALID;
-    hipEvent_t *evp = ctx->opt_timing ? ctx->ev : nullptr;
+    hipEvent_t *evp = ctx->opt_timing ? ctx->jobs[0].ev : nullptr;
     if (evp) { HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_TOTAL], s)); HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_PREDICT], s)); }
     uint32_t cap = 0;
     bool two = false;
     if ((rc = aoh_encode_stripes(ctx, s, code, ctx_bits, d_in, n, block_size, nb, d_block_lens, nullptr, cap, two))) return rc;
     if (evp) { HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_PREDICT + 1], s)); HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_PACK], s)); }
-    JobRef J = jobref(ctx, 0);
-    if ((rc = run_pack(ctx, J, s, (const uint8_t *)ctx->stripes.p, cap, d_block_lens, nb, d_out, out_cap, total_p))) return rc;
+    Job &J = ctx->jobs[0];
+    if ((rc = run_pack(ctx, J, s, (const uint8_t *)ctx->jobs[0].stripes.p, cap, d_block_lens, nb, d_out, out_cap, total_p))) return rc;
     if (evp) { HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_PACK + 1], s)); HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_TOTAL + 1], s)); }
     uint64_t total = 0;
     HIPCHK(ctx, hipMemcpyAsync(&total, total_p, 8, hipMemcpyDeviceToHost, s));
@@ -2917,7 +2861,7 @@ extern "C" int w3_aoh_encode_blocks(w3_ctx *ctx, const w3_huff_code *code, uint8
     hipStream_t s = ctx->stream;
     memset(&ctx->timing, 0, sizeof ctx->timing);
     const size_t run = host_run_blocks(ctx, block_size);   // any length: device calls of at most 2 GiB of input, one after the other
-    JobRef J = jobref(ctx, 0);
+    Job &J = ctx->jobs[0];
     size_t off = 0;
     uint32_t parts = 0;
     bool two = false;
@@ -2939,7 +2883,7 @@ extern "C" int w3_aoh_encode_blocks(w3_ctx *ctx, const w3_huff_code *code, uint8
         HIPCHK(ctx, hipStreamSynchronize(s));
         if (out && off + total <= out_cap) {   // (once the caller's buffer is full the later pieces are still coded: *out_len must hold the need)
             ENSURE(ctx, ctx->io_out, (size_t)total);
-            if ((rc = run_pack(ctx, J, s, (const uint8_t *)ctx->stripes.p, cap, (const uint32_t *)ctx->lens.p, pnb, (uint8_t *)ctx->io_out.p, (size_t)total, (uint64_t *)ctx->total.p))) return rc;
+            if ((rc = run_pack(ctx, J, s, (const uint8_t *)ctx->jobs[0].stripes.p, cap, (const uint32_t *)ctx->lens.p, pnb, (uint8_t *)ctx->io_out.p, (size_t)total, (uint64_t *)ctx->total.p))) return rc;
             HIPCHK(ctx, hipMemcpyAsync(out + off, ctx->io_out.p, (size_t)total, hipMemcpyDeviceToHost, s));
             HIPCHK(ctx, hipStreamSynchronize(s));
         }
@@ -2975,12 +2919,12 @@ static int aoh_spec_launch(w3_ctx *ctx, hipStream_t s, AohSpecArgs a, uint8_t ct
 
 // which decoder a ranges call takes: the sixteen-lane kernel where it covers, unless W3_OPT_VARIANT bit 1024 asks for the lane kernel
 static bool aoh_ranges_take_spec(const w3_ctx *ctx, uint8_t ctx_bits) {
-    return aoh_spec_covers(ctx_bits) && !(ctx->tp.variant & W3_VAR_DECODE_LANE);
+    return aoh_spec_covers(ctx_bits) && !(ctx->opt.variant & W3_VAR_DECODE_LANE);
 }
 // ... and the full decode: the lane kernel, as before the sixteen-lane kernel existed, unless bit 2048 asks for that one (an untimed
 // form does not become a default: DESIGN.md 7)
 static bool aoh_full_take_spec(const w3_ctx *ctx, uint8_t ctx_bits) {
-    return (ctx->tp.variant & W3_VAR_AOH_DECODE_SPEC) && aoh_ranges_take_spec(ctx, ctx_bits);
+    return (ctx->opt.variant & W3_VAR_AOH_DECODE_SPEC) && aoh_ranges_take_spec(ctx, ctx_bits);
 }
 
 // The decoders of the family on device-resident streams (d_lens[nb], validated by the caller): every block whole into d_out
@@ -3158,7 +3102,7 @@ extern "C" int w3_aoh_encode_stats_device(w3_ctx *ctx, const w3_huff_code *code,
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     memset(&ctx->timing, 0, sizeof ctx->timing);
-    hipEvent_t *evp = ctx->opt_timing ? ctx->ev : nullptr;
+    hipEvent_t *evp = ctx->opt_timing ? ctx->jobs[0].ev : nullptr;
     if (evp) { HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_TOTAL], s)); HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_PREDICT], s)); }
     bool two = false;
     if ((rc = aoh_stats_run(ctx, s, d_in, n, block_size, (uint32_t)nb, code, 1, nullptr, &ctx_bits, 1, d_block_bits, &two))) return rc;
@@ -3180,10 +3124,10 @@ extern "C" int w3_aoh_encode_stats(w3_ctx *ctx, const w3_huff_code *code, uint8_
     for (size_t b0 = 0; b0 < nb; b0 += run) {
         const size_t b1 = std::min(nb, b0 + run), lo = b0 * block_size, hi = std::min(n, b1 * block_size);
         ENSURE(ctx, ctx->io_in, hi - lo);
-        ENSURE(ctx, ctx->bits, (b1 - b0) * 4);
+        ENSURE(ctx, ctx->jobs[0].bits, (b1 - b0) * 4);
         HIPCHK(ctx, hipMemcpy(ctx->io_in.p, in + lo, hi - lo, hipMemcpyHostToDevice));
-        if ((rc = w3_aoh_encode_stats_device(ctx, code, ctx_bits, (const uint8_t *)ctx->io_in.p, hi - lo, block_size, (uint32_t *)ctx->bits.p, ctx->stream))) return rc;
-        HIPCHK(ctx, hipMemcpy(block_bits + b0, ctx->bits.p, (b1 - b0) * 4, hipMemcpyDeviceToHost));
+        if ((rc = w3_aoh_encode_stats_device(ctx, code, ctx_bits, (const uint8_t *)ctx->io_in.p, hi - lo, block_size, (uint32_t *)ctx->jobs[0].bits.p, ctx->stream))) return rc;
+        HIPCHK(ctx, hipMemcpy(block_bits + b0, ctx->jobs[0].bits.p, (b1 - b0) * 4, hipMemcpyDeviceToHost));
     }
     return W3_OK;
 }
@@ -3251,16 +3195,16 @@ extern "C" int w3_export_counters(w3_ctx *ctx, const w3_model_spec *spec, const 
     const uint32_t cap = default_stripe_cap(n);
     ENSURE(ctx, ctx->tables, entries * 4);
     ENSURE(ctx, ctx->io_in, n);
-    ENSURE(ctx, ctx->stripes, cap);
+    ENSURE(ctx, ctx->jobs[0].stripes, cap);
     ENSURE(ctx, ctx->lens, 4);
-    ENSURE(ctx, ctx->flag, 16);
+    ENSURE(ctx, ctx->jobs[0].flag, 16);
     HIPCHK(ctx, hipMemcpyAsync(ctx->io_in.p, in, n, hipMemcpyHostToDevice, s));
     HIPCHK(ctx, hipMemsetAsync(ctx->tables.p, 0, entries * 4, s));
     ga.n = n; ga.block_size = (uint32_t)n; ga.first_block = 0; ga.n_lanes = 1;
-    ga.huff = ctx->tp.huff; ga.n_huff = (int)ps.n_huff;
+    ga.huff = lane_huff(ctx, ps); ga.n_huff = (int)ps.n_huff;
     ga.tables = (uint8_t *)ctx->tables.p; ga.lane_stride = entries * 4;
-    ga.in = (const uint8_t *)ctx->io_in.p; ga.stripes = (uint8_t *)ctx->stripes.p; ga.stripe_cap = cap;
-    ga.out_len = (uint32_t *)ctx->lens.p; ga.overflow = (uint32_t *)ctx->flag.p; ga.out_bits = nullptr;
+    ga.in = (const uint8_t *)ctx->io_in.p; ga.stripes = (uint8_t *)ctx->jobs[0].stripes.p; ga.stripe_cap = cap;
+    ga.out_len = (uint32_t *)ctx->lens.p; ga.overflow = (uint32_t *)ctx->jobs[0].flag.p; ga.out_bits = nullptr;
     launch_generic<false>(ga, 1, s);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(counters, ctx->tables.p, entries * 4, hipMemcpyDeviceToHost, s));
@@ -3291,21 +3235,18 @@ extern "C" int w3_predict_blocks(w3_ctx *ctx, const w3_model_spec *spec, const u
     if (!twophase_supported(ps, block_size, n)) { ctx->err = "spec not covered by the two-phase predict kernels"; return W3_E_UNSUPPORTED; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    if (ps.is_cm()) {
-        CmArgs lut;
-        if ((rc = cm_luts(ctx, s, lut))) return rc;
-        ctx->tp.stretch = lut.stretch; ctx->tp.squash = lut.squash; ctx->tp.st = lut.st;
-    }
+    if (ps.is_cm() && (rc = stage_cm_luts(ctx, s))) return rc;
     const uint32_t nb = (uint32_t)((n + block_size - 1) / block_size);
     if ((rc = stage_huff(ctx, s, ps))) return rc;
+    hand_options(ctx, ctx->jobs[0], true);
     ENSURE(ctx, ctx->io_in, n);
     HIPCHK(ctx, hipMemcpyAsync(ctx->io_in.p, in, n, hipMemcpyHostToDevice, s));
     const uint16_t *d_p = nullptr;
-    { JobRef J0 = jobref(ctx, 0); if ((rc = attach_aux_streams(ctx, J0, 0))) return rc; }
-    rc = twophase_predict(ctx->tp, s, ps, (const uint8_t *)ctx->io_in.p, n, block_size, nb, ps.n_apm == 0, &d_p, nullptr, &ctx->timing, ctx->err);
+    if ((rc = attach_aux_streams(ctx, ctx->jobs[0]))) return rc;
+    rc = twophase_predict(ctx->jobs[0].tp, s, ps, (const uint8_t *)ctx->io_in.p, n, block_size, nb, ps.n_apm == 0, &d_p, nullptr, &ctx->timing, ctx->err);
     if (rc) return rc;
-    if ((rc = twophase_apm(ctx->tp, s, ps, (const uint8_t *)ctx->io_in.p, n, block_size, nb, nullptr, &ctx->timing, ctx->err))) return rc;
-    d_p = (const uint16_t *)ctx->tp.P;
+    if ((rc = twophase_apm(ctx->jobs[0].tp, s, ps, (const uint8_t *)ctx->io_in.p, n, block_size, nb, nullptr, &ctx->timing, ctx->err))) return rc;
+    d_p = (const uint16_t *)ctx->jobs[0].tp.P;
     HIPCHK(ctx, hipStreamSynchronize(s));
     HIPCHK(ctx, hipMemcpy(p_out, d_p, n * 16, hipMemcpyDeviceToHost));
     return W3_OK;
@@ -3348,9 +3289,9 @@ extern "C" int w3_selftest_counter_p(w3_ctx *ctx, uint64_t *mismatches) {
 extern "C" int w3_debug_get_stamps(w3_ctx *ctx, uint64_t out[8]) {
     if (!ctx || !out) return W3_E_INVALID;
     memset(out, 0, 64);
-    if (!ctx->tp.dbg) return W3_OK;
+    if (!ctx->jobs[0].tp.dbg) return W3_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipDeviceSynchronize());
-    HIPCHK(ctx, hipMemcpy(out, ctx->tp.dbg, 64, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(out, ctx->jobs[0].tp.dbg, 64, hipMemcpyDeviceToHost));
     return W3_OK;
 }
