@@ -466,7 +466,7 @@ int w3_sweep_ordern_device(w3_ctx *ctx, const uint8_t *d_in, size_t n, size_t bl
  * w3_aoh_max_compressed_size: upper bound on the concatenated streams (16 output bits per coded bit); 0 = block_size 0 or an INVALID
  * table (needs no device: the way to validate a table).                                                                          */
 typedef struct w3_huff_code { uint16_t code[256]; uint8_t len[256]; } w3_huff_code;
-int    w3_huff_code_table(const uint8_t *buf, size_t n, uint8_t huffman_size, w3_huff_code *out);   /* host only */
+int    w3_huff_code_table(const uint8_t *buf, size_t n, uint8_t huffman_size, w3_huff_code *out);   /* host only; from a device histogram: w3_huff_code_from_counts */
 size_t w3_aoh_max_compressed_size(size_t n, size_t block_size, const w3_huff_code *code);
 int w3_aoh_encode_blocks(w3_ctx *ctx, const w3_huff_code *code, uint8_t ctx_bits, const uint8_t *in, size_t n, size_t block_size,
                          uint8_t *out, size_t out_cap, size_t *out_len, uint32_t *block_lens);
@@ -545,7 +545,7 @@ int w3_predict_blocks(w3_ctx *ctx, const w3_model_spec *spec,
 
 /* ---- StationaryModel::new(buf) (models/ac_hash/stationary.rs:14-34) ---------
  * Host-side table preparation for ACHistory: 8 Counters by bit position walked
- * over `buf`, table[i] = p().  Model construction, not the hot path.          */
+ * over `buf`, table[i] = p().  One host thread; the device forms are below.  */
 int w3_stationary_table(const uint8_t *buf, size_t n, uint16_t table[8]);
 
 /* ---- HuffHistory::new(buf, huff_size, rem_huff_size) (history/huff_history.rs:17-55) --------
@@ -558,6 +558,43 @@ int w3_stationary_table(const uint8_t *buf, size_t n, uint16_t table[8]);
  * INTEGRATION.md); Rust's unstable sort is not re-derived here.  Model construction, not the hot path.
  * Returns W3_E_INVALID for the reference's panics (no symbols, max length > 32 or too small for the alphabet).      */
 int w3_huff_tables(const uint8_t *buf, size_t n, uint8_t huff_size, uint8_t rem_huff_size, w3_huff_table *out);
+
+/* ---- table preparation on the device: the byte histogram and StationaryModel::new (csrc/w3_prep.h) ----------------------------
+ * The three preparations above walk the WHOLE input on one host thread.  These calls do the walking on the device, so that input which
+ * lives there needs no trip to the host, and build the same tables: the results equal w3_stationary_table, w3_huff_code_table and
+ * w3_huff_tables bit for bit.
+ *   w3_histogram_device         counts[v] (HOST memory, 256 entries) = how many of the n bytes at d_in equal v.
+ *   w3_histogram                the same for a host buffer of ANY length: it goes up through the context's staging buffer in pieces of
+ *                               2 GiB (W3_OPT_HOST_CHUNK_BLOCKS: nominal 64 KiB blocks per piece), the pieces' counts are added in 64 bits.
+ *   w3_stationary_table_device  table[8] (HOST memory) = w3_stationary_table of the n bytes at d_in: k_stat_count counts the one-bits
+ *                               per 4 KiB tile and bit position, k_stat_walk follows the eight Counters from tile to tile with a
+ *                               wavefront each and reloads only the tiles in which a Counter halves.
+ *   w3_stationary_table_staged  the same for a host buffer of any length, staged as w3_histogram stages; the Counters' state stays on the
+ *                               device from piece to piece.
+ *   w3_huff_code_from_counts, w3_huff_tables_from_counts   host only: what w3_huff_code_table / w3_huff_tables do behind their own
+ *                               histogram loop (those two call these), error codes included; W3_E_UNSUPPORTED for a count above 2^32 - 1
+ *                               (the reference counts in u32).
+ * The four context calls follow the family's rules: the per-call limit n < 2^32 - 4096 for the _device forms, W3_E_INVALID while a job
+ * is in flight, n == 0 is valid (all-zero counts; eight fresh Counters, 32768 each), stream NULL = the context's, and the call
+ * synchronises its stream before it returns.  The staged copy is not kept for an encode that follows: DESIGN.md 7.
+ * w3_table_prep_profile is the measurement hook of tools/table_prep_rate.py: both preparations once, every kernel between HIP events;
+ * hist_rep = copies per counter in k_hist256 (1, 2, 4, 8, 16; the calls above use W3_HIST_REP).                                        */
+#define W3_STAT_TILE 4096u    /* bytes per tile of the stationary walk */
+#define W3_STAT_BATCH 64u     /* tiles per step of the walk */
+#define W3_HIST_REP 16u       /* copies of a wavefront's LDS counters */
+typedef struct w3_prep_profile {
+    float hist_ms, hist_sum_ms, stat_count_ms, stat_walk_ms;   /* k_hist256, k_hist256_sum, k_stat_count, k_stat_walk */
+    uint32_t halvings[8];                                      /* per bit position (0 = the MSB) */
+    uint16_t table[8];
+    uint64_t counts[256];
+} w3_prep_profile;
+int w3_histogram(w3_ctx *ctx, const uint8_t *in, size_t n, uint64_t counts[256]);
+int w3_histogram_device(w3_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t counts[256] /* host */, void *stream);
+int w3_stationary_table_staged(w3_ctx *ctx, const uint8_t *in, size_t n, uint16_t table[8]);
+int w3_stationary_table_device(w3_ctx *ctx, const uint8_t *d_in, size_t n, uint16_t table[8] /* host */, void *stream);
+int w3_huff_code_from_counts(const uint64_t counts[256], uint8_t huffman_size, w3_huff_code *out);                          /* host only */
+int w3_huff_tables_from_counts(const uint64_t counts[256], uint8_t huff_size, uint8_t rem_huff_size, w3_huff_table *out);   /* host only */
+int w3_table_prep_profile(w3_ctx *ctx, const uint8_t *d_in, size_t n, uint32_t hist_rep, w3_prep_profile *out);
 
 /* ---- read-only tables of the CM kernels (host-side; for known-answer tests) -----------
  * w3_state_table: NaiveStateTable (state_table/naive.rs:7-115) as 3963 rows of

@@ -18,6 +18,7 @@
 #   pmcpy <counters> <script> [args]   one rocprofv3 --pmc pass of python3 <script> args (e.g. tools/decode_rate.py); per-kernel sums
 #   statspy <script> [args]     rocprofv3 --kernel-trace --stats of python3 <script> args
 #   decode [model] [bytes]      tools/decode_rate.py
+#   prep [args]                 tools/table_prep_rate.py (sizes 1e6, 1e8, 1e9 -> profiles/table_prep/table_prep_rate.json)
 #   py <script> [args]          python3 <script> args
 #   ubench <file.hip> [args]    hipcc a tools/*.hip microbenchmark and run it
 # Steps are joined with && semantics: the first failing step ends the call (no GPU step after a failed one).
@@ -86,6 +87,9 @@ EOF
     decode)
         timeout -k 10 900 python3 tools/decode_rate.py "$@" > "$DST/decode_$n.txt" 2>&1; local rc=$?
         tail -12 "$DST/decode_$n.txt"; return $rc ;;
+    prep)
+        timeout -k 10 1100 python3 tools/table_prep_rate.py "$@" > "$DST/prep_$n.txt" 2>&1; local rc=$?
+        tail -5 "$DST/prep_$n.txt" | cut -c1-600; return $rc ;;
     py)
         timeout -k 10 1100 python3 "$@" > "$DST/py_$n.txt" 2>&1; local rc=$?
         tail -40 "$DST/py_$n.txt"; return $rc ;;

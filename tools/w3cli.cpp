@@ -158,7 +158,10 @@ static int compress(w3_ctx *ctx, const std::string &in, const std::string &out) 
         w3_huff_code code;
         memset(&code, 0, sizeof code);
         if (!data.empty()) {
-            rc = w3_huff_code_table(data.data(), data.size(), (uint8_t)am.hsize, &code);
+            uint64_t counts[256];   // the histogram on the device (w3_histogram), the table from the counts
+            rc = w3_histogram(ctx, data.data(), data.size(), counts);
+            if (rc) return die(ctx, rc, "w3_histogram");
+            rc = w3_huff_code_from_counts(counts, (uint8_t)am.hsize, &code);
             if (rc) { fprintf(stderr, "w3_huff_code_table: hsize %d does not fit this file's alphabet\n", am.hsize); return 1; }
             bool any = false;
             for (int s = 0; s < 256; s++) any |= code.len[s] != 0;

@@ -59,6 +59,13 @@ class Timing(C.Structure):
                 ("small_ms", C.c_float)]
 
 
+class PrepProfile(C.Structure):   # w3_prep_profile
+    _fields_ = [("hist_ms", C.c_float), ("hist_sum_ms", C.c_float), ("stat_count_ms", C.c_float), ("stat_walk_ms", C.c_float),
+                ("halvings", C.c_uint32 * 8), ("table", C.c_uint16 * 8), ("counts", C.c_uint64 * 256)]
+
+
+W3_STAT_TILE, W3_STAT_BATCH, W3_HIST_REP = 4096, 64, 16  # include/w3hip.h "table preparation on the device"
+
 EXPORTS = [
     "w3_abi_version", "w3_strerror", "w3_last_error", "w3_ctx_create", "w3_ctx_destroy", "w3_spec_validate",
     "w3_ctx_set_option", "w3_max_compressed_size", "w3_encode_blocks", "w3_decode_blocks", "w3_encode_blocks_device",
@@ -73,6 +80,8 @@ EXPORTS = [
     "w3_sweep_ac_over_huffman_device", "w3_aoh_decode_ranges", "w3_aoh_decode_ranges_device", "w3_aoh_decode_spec_covers",
     "w3_crc32_blocks", "w3_crc32_blocks_device", "w3_crc32_verify_device", "w3_decode_blocks_checked", "w3_decode_ranges_checked",
     "w3_decode_ranges_device_checked", "w3_aoh_decode_blocks_checked", "w3_aoh_decode_ranges_checked", "w3_aoh_decode_ranges_device_checked",
+    "w3_histogram", "w3_histogram_device", "w3_stationary_table_staged", "w3_stationary_table_device", "w3_huff_code_from_counts",
+    "w3_huff_tables_from_counts", "w3_table_prep_profile",
 ]
 
 _lib = None
@@ -170,6 +179,13 @@ def load():
     lib.w3_aoh_decode_blocks_checked.argtypes = lib.w3_aoh_decode_blocks.argtypes + [ck]
     lib.w3_aoh_decode_ranges_checked.argtypes = lib.w3_aoh_decode_ranges.argtypes + [ck]
     lib.w3_aoh_decode_ranges_device_checked.argtypes = lib.w3_aoh_decode_ranges_device.argtypes + [ck]
+    lib.w3_histogram.argtypes = [vp, vp, sz, vp]
+    lib.w3_histogram_device.argtypes = [vp, vp, sz, vp, vp]
+    lib.w3_stationary_table_staged.argtypes = [vp, vp, sz, vp]
+    lib.w3_stationary_table_device.argtypes = [vp, vp, sz, vp, vp]
+    lib.w3_huff_code_from_counts.argtypes = [vp, u8, hc]
+    lib.w3_huff_tables_from_counts.argtypes = [vp, u8, u8, C.POINTER(HuffTable)]
+    lib.w3_table_prep_profile.argtypes = [vp, vp, sz, C.c_uint32, C.POINTER(PrepProfile)]
     lib.w3_rccl_library.argtypes = [C.c_char_p]
     lib.w3_rccl_status.argtypes = [C.c_char_p, sz]
     _lib = lib

@@ -212,6 +212,44 @@ class Context:
         st = C.c_void_p(stream) if stream else None
         self._chk(self.lib.w3_crc32_blocks_device(self.h, C.c_void_p(d_in.data_ptr()), d_in.numel(), block_size, C.c_void_p(d_crc.data_ptr()), st))
 
+    # ---- table preparation on the device (include/w3hip.h; csrc/w3_prep.h) ----
+    def histogram(self, data):
+        """w3_histogram: the byte histogram of host `data` of any length, counted on the device.  -> np.uint64[256]"""
+        a = _u8(data)
+        counts = np.zeros(256, dtype=np.uint64)
+        self._chk(self.lib.w3_histogram(self.h, a.ctypes.data_as(C.c_void_p), len(a), counts.ctypes.data_as(C.c_void_p)))
+        return counts
+
+    def histogram_device(self, d_in, stream=None):
+        """w3_histogram_device: d_in a torch.uint8 CUDA tensor (contiguous).  -> np.uint64[256] on the host"""
+        st = C.c_void_p(stream) if stream else None
+        counts = np.zeros(256, dtype=np.uint64)
+        self._chk(self.lib.w3_histogram_device(self.h, C.c_void_p(d_in.data_ptr()), d_in.numel(), counts.ctypes.data_as(C.c_void_p), st))
+        return counts
+
+    def histogram_of(self, data):
+        """histogram_device for a tensor (anything with data_ptr()), histogram for host data"""
+        return self.histogram_device(data) if hasattr(data, "data_ptr") else self.histogram(data)
+
+    def stationary_table(self, data, stream=None):
+        """StationaryModel::new's table on the device: w3_stationary_table_device for a torch.uint8 CUDA tensor, w3_stationary_table_staged
+        for host data of any length.  -> list of 8 ints"""
+        t = (C.c_uint16 * 8)()
+        if hasattr(data, "data_ptr"):
+            st = C.c_void_p(stream) if stream else None
+            self._chk(self.lib.w3_stationary_table_device(self.h, C.c_void_p(data.data_ptr()), data.numel(), t, st))
+        else:
+            a = _u8(data)
+            self._chk(self.lib.w3_stationary_table_staged(self.h, a.ctypes.data_as(C.c_void_p), len(a), t))
+        return list(t)
+
+    def table_prep_profile(self, d_in, hist_rep=L.W3_HIST_REP):
+        """w3_table_prep_profile (tools/table_prep_rate.py): both preparations of the tensor d_in once, each kernel's time from HIP events"""
+        p = L.PrepProfile()
+        self._chk(self.lib.w3_table_prep_profile(self.h, C.c_void_p(d_in.data_ptr()), d_in.numel(), int(hist_rep), C.byref(p)))
+        return {"hist_ms": p.hist_ms, "hist_sum_ms": p.hist_sum_ms, "stat_count_ms": p.stat_count_ms, "stat_walk_ms": p.stat_walk_ms,
+                "halvings": list(p.halvings), "table": list(p.table), "counts": np.array(p.counts, dtype=np.uint64)}
+
     def crc32_verify_device(self, d_data, block_size, d_crc, stream=None):
         """w3_crc32_verify_device: the blocks of d_data against the table d_crc (both CUDA tensors).  -> (bad_block, n_bad) = (2**64 - 1, 0)
         when every block matches; W3Error(W3_E_CORRUPT) with .bad_block (the lowest block that differs) and .n_bad otherwise."""
@@ -368,11 +406,11 @@ class Context:
         return out[:, :nb]
 
     def aoh_compress(self, data, huffman_size=13, ctx_bits=24, block_size=65536):
-        """Container writer's form: the table of `data` (HuffCode.new), encode.  A one-symbol input gives the all-zero table, as in the
+        """Container writer's form: the table of `data` (HuffCode.new_on: the histogram is taken on the device), encode.  A one-symbol input gives the all-zero table, as in the
         reference, where such a file codes zero bits; it is turned into len 1, code 0 for that symbol HERE, before encoding, so that
         the streams can be decoded.  -> (HuffCode used, streams, block_lens)"""
         a = _u8(data)
-        code = HuffCode.new(a, huffman_size)
+        code = HuffCode.new_on(self, a, huffman_size)
         if len(a) and not any(code.lens):
             code = code.with_single_symbol(int(a[0]))
         out, lens = self.aoh_encode_blocks(code, ctx_bits, a, block_size)

@@ -81,10 +81,9 @@ static inline void reversed_canonical(const uint8_t *lens, size_t n, uint16_t *c
     }
 }
 
-static inline bool build(const uint8_t *buf, size_t n, unsigned huff_size, unsigned rem_size, w3_huff_table *out) {
-    uint32_t counts[256] = {0}, rem[256] = {0};
+static inline bool build(const uint32_t counts[256], unsigned huff_size, unsigned rem_size, w3_huff_table *out) {
+    uint32_t rem[256] = {0};
     uint8_t lens[256];
-    for (size_t i = 0; i < n; i++) counts[buf[i]]++;
     if (!code_lengths(counts, 256, huff_size, lens)) return false;
     reversed_canonical(lens, 256, out->code, out->len);
     for (int byte = 0; byte < 256; byte++)                    // huff_history.rs:27-34

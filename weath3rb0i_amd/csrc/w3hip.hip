@@ -29,6 +29,7 @@
 #include "w3_aoh_spec.h"
 #include "w3_rccl.h"
 #include "w3_crc.h"
+#include "w3_prep.h"
 
 using namespace w3;
 
@@ -114,6 +115,7 @@ struct w3_ctx {
     // CRC-32 per block (w3_crc.h): [0, 16) the verify's result {lowest mismatching segment, mismatches}, from byte 256 on the slices' CRCs;
     // crc_tab: a table on its way to or from a host caller; crc_res: where the result lands on the host
     DevBuf crc_ws, crc_tab;
+    DevBuf prep_ws;   // table preparation (w3_prep.h): the counts, the walk's state, the histogram's partials, the tiles' counts (W3_PREP_WS_*)
     uint64_t crc_res[2] = {~0ull, 0};
     // What a job takes from the context when a call is prepared (hand_options): the two-phase options (w3_ctx_set_option), the
     // context-mixing look-up tables in cm_luts, and the lane-order self-test's verdict (-1 not run yet under this variant, 1 = returning
@@ -252,7 +254,7 @@ extern "C" void w3_ctx_destroy(w3_ctx *ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
     DevBuf *bufs[] = {&ctx->tables, &ctx->lens, &ctx->total, &ctx->io_in, &ctx->io_out, &ctx->coffs, &ctx->misc, &ctx->cm_luts, &ctx->achash_luts,
-                      &ctx->sweep, &ctx->aoh, &ctx->rg_stage, &ctx->rg_meta, &ctx->crc_ws, &ctx->crc_tab};
+                      &ctx->sweep, &ctx->aoh, &ctx->rg_stage, &ctx->rg_meta, &ctx->crc_ws, &ctx->crc_tab, &ctx->prep_ws};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (ctx->h_rg) (void)hipHostFree(ctx->h_rg);
@@ -1711,6 +1713,181 @@ extern "C" int w3_crc32_blocks(w3_ctx *ctx, const uint8_t *in, size_t n, size_t 
     return W3_OK;
 }
 
+// ---------------------------------------------------------------------------
+// table preparation on the device (w3_prep.h): the byte histogram and StationaryModel::new
+// ---------------------------------------------------------------------------
+#define W3_PREP_WS_COUNTS 0u                                      // 256 uint64: the histogram
+#define W3_PREP_WS_STATE 2048u                                    // 24 uint32: (c0, c1) of the 8 positions, then their halvings
+#define W3_PREP_WS_PARTIAL 4096u                                  // W3_HIST_MAX_WG x 256 uint32: the workgroups' partials
+#define W3_PREP_WS_TILES (4096u + W3_HIST_MAX_WG * 1024u)         // 8 uint16 per tile of the stationary walk
+#define W3_PREP_NOMINAL_BLOCK 65536u                              // the "block" of these calls' argument checks and of the staged forms' pieces
+
+static int prep_ensure(w3_ctx *ctx, uint64_t n) {
+    ENSURE(ctx, ctx->prep_ws, (size_t)(W3_PREP_WS_TILES + ((n + 15u) / W3_STAT_TILE + 1u) * 16u));
+    return W3_OK;
+}
+
+// the histogram of d_in[0, n) into the workspace's counts (n > 0; does not synchronise).  rep: the copies per counter (W3_HIST_REP
+// everywhere but in the measurement of w3_table_prep_profile)
+static int hist_enqueue(w3_ctx *ctx, hipStream_t s, const uint8_t *d_in, uint64_t n, uint32_t rep = W3_HIST_REP, hipEvent_t ev_mid = nullptr) {
+    uint8_t *ws = (uint8_t *)ctx->prep_ws.p;
+    uint32_t *partial = (uint32_t *)(ws + W3_PREP_WS_PARTIAL);
+    const uint32_t wg = hist_workgroups(n);
+    switch (rep) {
+    case 1: hipLaunchKernelGGL((k_hist256<1u>), dim3(wg), dim3(256), 0, s, d_in, n, partial); break;
+    case 2: hipLaunchKernelGGL((k_hist256<2u>), dim3(wg), dim3(256), 0, s, d_in, n, partial); break;
+    case 4: hipLaunchKernelGGL((k_hist256<4u>), dim3(wg), dim3(256), 0, s, d_in, n, partial); break;
+    case 8: hipLaunchKernelGGL((k_hist256<8u>), dim3(wg), dim3(256), 0, s, d_in, n, partial); break;
+    case 16: hipLaunchKernelGGL((k_hist256<16u>), dim3(wg), dim3(256), 0, s, d_in, n, partial); break;
+    default: ctx->err = "copies per counter: 1, 2, 4, 8 or 16"; return W3_E_INVALID;
+    }
+    HIPCHK(ctx, hipGetLastError());
+    if (ev_mid) HIPCHK(ctx, hipEventRecord(ev_mid, s));
+    hipLaunchKernelGGL(k_hist256_sum, dim3(256), dim3(64), 0, s, (const uint32_t *)partial, wg, (uint64_t *)(ws + W3_PREP_WS_COUNTS));
+    HIPCHK(ctx, hipGetLastError());
+    return W3_OK;
+}
+
+// the stationary walk over d_in[0, n) from the state in the workspace to the state in the workspace (n > 0; does not synchronise)
+static int stat_enqueue(w3_ctx *ctx, hipStream_t s, const uint8_t *d_in, uint64_t n, hipEvent_t ev_mid = nullptr) {
+    uint8_t *ws = (uint8_t *)ctx->prep_ws.p;
+    uint16_t *ones8 = (uint16_t *)(ws + W3_PREP_WS_TILES);
+    const uint64_t ntiles = stat_tiles(prep_window(d_in, n));
+    hipLaunchKernelGGL(k_stat_count, dim3((uint32_t)std::min<uint64_t>((ntiles + 3) / 4, 4096)), dim3(256), 0, s, d_in, n, ones8);
+    HIPCHK(ctx, hipGetLastError());
+    if (ev_mid) HIPCHK(ctx, hipEventRecord(ev_mid, s));
+    hipLaunchKernelGGL(k_stat_walk, dim3(8), dim3(64), 0, s, d_in, n, (const uint16_t *)ones8, (uint32_t *)(ws + W3_PREP_WS_STATE));
+    HIPCHK(ctx, hipGetLastError());
+    return W3_OK;
+}
+static void stat_table_of(const uint32_t state[24], uint16_t table[8]) {
+    for (int i = 0; i < 8; i++) table[i] = stat_table_entry(state[2 * i], state[2 * i + 1]);
+}
+
+// the checks the calls share (block_size: the nominal block, so that check_args' limits are the family's)
+static int prep_args(w3_ctx *ctx, const void *in, size_t n, const void *out, bool one_device) {
+    int rc = check_args(ctx, n, W3_PREP_NOMINAL_BLOCK, one_device);
+    if (rc) return rc;
+    if ((rc = jobs_idle(ctx))) return rc;   // (the workspace is the context's)
+    if (!out || (!in && n)) return W3_E_INVALID;
+    return W3_OK;
+}
+
+extern "C" int w3_histogram_device(w3_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t counts[256], void *stream) {
+    int rc = prep_args(ctx, d_in, n, counts, true);
+    if (rc) return rc;
+    memset(counts, 0, 256 * sizeof(uint64_t));
+    if (n == 0) return W3_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    if ((rc = prep_ensure(ctx, 0))) return rc;
+    if ((rc = hist_enqueue(ctx, s, d_in, n))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(counts, (uint8_t *)ctx->prep_ws.p + W3_PREP_WS_COUNTS, 256 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return W3_OK;
+}
+
+// A host buffer of any length: up through ctx->io_in in pieces of host_run_blocks nominal 64 KiB blocks (W3_OPT_HOST_CHUNK_BLOCKS: ragged
+// pieces for the tests), the pieces' counts added up in 64 bits.
+extern "C" int w3_histogram(w3_ctx *ctx, const uint8_t *in, size_t n, uint64_t counts[256]) {
+    int rc = prep_args(ctx, in, n, counts, false);
+    if (rc) return rc;
+    memset(counts, 0, 256 * sizeof(uint64_t));
+    if (n == 0) return W3_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t piece = host_run_blocks(ctx, W3_PREP_NOMINAL_BLOCK) * (size_t)W3_PREP_NOMINAL_BLOCK;
+    if ((rc = prep_ensure(ctx, 0))) return rc;
+    ENSURE(ctx, ctx->io_in, std::min(n, piece));
+    uint64_t part[256];
+    for (size_t o0 = 0; o0 < n; o0 += piece) {
+        const size_t len = std::min(piece, n - o0);
+        HIPCHK(ctx, hipMemcpyAsync(ctx->io_in.p, in + o0, len, hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = hist_enqueue(ctx, ctx->stream, (const uint8_t *)ctx->io_in.p, len))) return rc;
+        HIPCHK(ctx, hipMemcpyAsync(part, (uint8_t *)ctx->prep_ws.p + W3_PREP_WS_COUNTS, sizeof part, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        for (int v = 0; v < 256; v++) counts[v] += part[v];
+    }
+    return W3_OK;
+}
+
+extern "C" int w3_stationary_table_device(w3_ctx *ctx, const uint8_t *d_in, size_t n, uint16_t table[8], void *stream) {
+    int rc = prep_args(ctx, d_in, n, table, true);
+    if (rc) return rc;
+    uint32_t state[24] = {0};
+    if (n) {
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+        if ((rc = prep_ensure(ctx, n))) return rc;
+        uint8_t *d_state = (uint8_t *)ctx->prep_ws.p + W3_PREP_WS_STATE;
+        HIPCHK(ctx, hipMemsetAsync(d_state, 0, sizeof state, s));
+        if ((rc = stat_enqueue(ctx, s, d_in, n))) return rc;
+        HIPCHK(ctx, hipMemcpyAsync(state, d_state, sizeof state, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+    }
+    stat_table_of(state, table);
+    return W3_OK;
+}
+
+// The same from a host buffer of any length, staged as w3_histogram stages: the walk's state stays on the device from piece to piece.
+extern "C" int w3_stationary_table_staged(w3_ctx *ctx, const uint8_t *in, size_t n, uint16_t table[8]) {
+    int rc = prep_args(ctx, in, n, table, false);
+    if (rc) return rc;
+    uint32_t state[24] = {0};
+    if (n) {
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        const size_t piece = host_run_blocks(ctx, W3_PREP_NOMINAL_BLOCK) * (size_t)W3_PREP_NOMINAL_BLOCK;
+        if ((rc = prep_ensure(ctx, std::min(n, piece)))) return rc;
+        ENSURE(ctx, ctx->io_in, std::min(n, piece));
+        uint8_t *d_state = (uint8_t *)ctx->prep_ws.p + W3_PREP_WS_STATE;
+        HIPCHK(ctx, hipMemsetAsync(d_state, 0, sizeof state, ctx->stream));
+        for (size_t o0 = 0; o0 < n; o0 += piece) {
+            const size_t len = std::min(piece, n - o0);
+            HIPCHK(ctx, hipMemcpyAsync(ctx->io_in.p, in + o0, len, hipMemcpyHostToDevice, ctx->stream));
+            if ((rc = stat_enqueue(ctx, ctx->stream, (const uint8_t *)ctx->io_in.p, len))) return rc;
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (the next piece overwrites io_in)
+        }
+        HIPCHK(ctx, hipMemcpy(state, d_state, sizeof state, hipMemcpyDeviceToHost));
+    }
+    stat_table_of(state, table);
+    return W3_OK;
+}
+
+// Both preparations of d_in[0, n) once, every kernel between HIP events (tools/table_prep_rate.py).
+extern "C" int w3_table_prep_profile(w3_ctx *ctx, const uint8_t *d_in, size_t n, uint32_t hist_rep, w3_prep_profile *out) {
+    int rc = prep_args(ctx, d_in, n, out, true);
+    if (rc) return rc;
+    memset(out, 0, sizeof *out);
+    uint32_t state[24] = {0};
+    if (n) {
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        hipStream_t s = ctx->stream;
+        if ((rc = prep_ensure(ctx, n))) return rc;
+        uint8_t *ws = (uint8_t *)ctx->prep_ws.p;
+        hipEvent_t ev[5] = {};
+        for (auto &e : ev) HIPCHK(ctx, hipEventCreate(&e));
+        HIPCHK(ctx, hipMemsetAsync(ws + W3_PREP_WS_STATE, 0, sizeof state, s));
+        HIPCHK(ctx, hipEventRecord(ev[0], s));
+        rc = hist_enqueue(ctx, s, d_in, n, hist_rep, ev[1]);
+        if (!rc) HIPCHK(ctx, hipEventRecord(ev[2], s));
+        if (!rc) rc = stat_enqueue(ctx, s, d_in, n, ev[3]);
+        if (!rc) HIPCHK(ctx, hipEventRecord(ev[4], s));
+        if (!rc) {
+            HIPCHK(ctx, hipMemcpyAsync(out->counts, ws + W3_PREP_WS_COUNTS, sizeof out->counts, hipMemcpyDeviceToHost, s));
+            HIPCHK(ctx, hipMemcpyAsync(state, ws + W3_PREP_WS_STATE, sizeof state, hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        if (!rc) {
+            float *ms[4] = {&out->hist_ms, &out->hist_sum_ms, &out->stat_count_ms, &out->stat_walk_ms};
+            for (int k = 0; k < 4; k++) HIPCHK(ctx, hipEventElapsedTime(ms[k], ev[k], ev[k + 1]));
+        }
+        for (auto &e : ev) (void)hipEventDestroy(e);
+        if (rc) return rc;
+    }
+    stat_table_of(state, out->table);
+    for (int i = 0; i < 8; i++) out->halvings[i] = state[16 + i];
+    return W3_OK;
+}
+
 static int decode_blocks_host(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t in_len, const uint32_t *block_lens, size_t nblocks,
                              size_t block_size, uint64_t orig_len, uint8_t *out, w3_check *chk) {
     int rc = check_args(ctx, (size_t)orig_len, block_size, false);
@@ -2559,11 +2736,23 @@ extern "C" int w3_huff_code_table(const uint8_t *buf, size_t n, uint8_t huffman_
     if ((!buf && n) || !out) return W3_E_INVALID;
     uint64_t c64[256] = {0};
     for (size_t i = 0; i < n; i++) c64[buf[i]]++;                      // histogram (helpers.rs:30-36) of the WHOLE buffer (:74)
-    uint32_t counts[256];
+    return w3_huff_code_from_counts(c64, huffman_size, out);
+}
+
+// the reference counts in u32 (helpers.rs:30-36): W3_E_UNSUPPORTED for a count it could not hold
+static int counts_to_u32(const uint64_t c64[256], uint32_t counts[256]) {
     for (int s = 0; s < 256; s++) {
-        if (c64[s] > 0xFFFFFFFFull) return W3_E_UNSUPPORTED;           // (the reference counts in u32 too)
+        if (c64[s] > 0xFFFFFFFFull) return W3_E_UNSUPPORTED;
         counts[s] = (uint32_t)c64[s];
     }
+    return W3_OK;
+}
+
+// ... from the histogram alone (w3_histogram / w3_histogram_device): the one builder of the code
+extern "C" int w3_huff_code_from_counts(const uint64_t c64[256], uint8_t huffman_size, w3_huff_code *out) {
+    if (!c64 || !out) return W3_E_INVALID;
+    uint32_t counts[256];
+    if (const int rc = counts_to_u32(c64, counts)) return rc;
     uint8_t lens[256];
     if (!w3huff::code_lengths(counts, 256, huffman_size, lens)) return W3_E_INVALID;   // package_merge's three asserts (:75)
     for (int s = 0; s < 256; s++)
@@ -3218,7 +3407,18 @@ extern "C" int w3_export_counters(w3_ctx *ctx, const w3_model_spec *spec, const 
 extern "C" int w3_huff_tables(const uint8_t *buf, size_t n, uint8_t huff_size, uint8_t rem_huff_size, w3_huff_table *out) {
     if ((!buf && n) || !out) return W3_E_INVALID;
     if (huff_size > 16 || rem_huff_size > 16) return W3_E_INVALID;   // codes are u16 (package_merge.rs:87: Vec<(u16, u8)>)
-    return w3huff::build(buf, n, huff_size, rem_huff_size, out) ? W3_OK : W3_E_INVALID;
+    uint64_t c64[256] = {0};
+    for (size_t i = 0; i < n; i++) c64[buf[i]]++;
+    return w3_huff_tables_from_counts(c64, huff_size, rem_huff_size, out);
+}
+
+// ... from the histogram alone: the one builder of the two tables
+extern "C" int w3_huff_tables_from_counts(const uint64_t c64[256], uint8_t huff_size, uint8_t rem_huff_size, w3_huff_table *out) {
+    if (!c64 || !out) return W3_E_INVALID;
+    if (huff_size > 16 || rem_huff_size > 16) return W3_E_INVALID;
+    uint32_t counts[256];
+    if (const int rc = counts_to_u32(c64, counts)) return rc;
+    return w3huff::build(counts, huff_size, rem_huff_size, out) ? W3_OK : W3_E_INVALID;
 }
 
 // ---------------------------------------------------------------------------

@@ -17,6 +17,13 @@ class W3Error(RuntimeError):
         super().__init__("w3hip error %d (%s) %s" % (code, L.load().w3_strerror(code).decode(), msg))
 
 
+def _counts(counts):
+    c = np.ascontiguousarray(counts, dtype=np.uint64)
+    if c.shape != (256,):
+        raise W3Error(L.W3_E_INVALID, "a byte histogram has 256 counts")
+    return c
+
+
 class StationaryModel:
     """models/ac_hash/stationary.rs:8-58 — per-bit-position static probabilities."""
 
@@ -31,6 +38,12 @@ class StationaryModel:
     @classmethod
     def new(cls, buf):
         return cls(buf)
+
+    @classmethod
+    def new_on(cls, ctx, data):
+        """StationaryModel::new computed on the device (Context.stationary_table: k_stat_count + k_stat_walk): `data` is host data
+        (bytes, numpy: staged in pieces of any total length) or a uint8 tensor on ctx's device.  The same table as new()."""
+        return cls.from_table(ctx.stationary_table(data))
 
     @classmethod
     def from_table(cls, table):
@@ -112,6 +125,23 @@ class HuffHistory:
         return cls(buf, huff_size, rem_huff_size)
 
     @classmethod
+    def from_counts(cls, counts, huff_size, rem_huff_size):
+        """the tables of a byte histogram (256 counts: Context.histogram / histogram_device): w3_huff_tables_from_counts, the builder
+        new() runs behind its own histogram loop"""
+        c = _counts(counts)
+        o = cls.__new__(cls)
+        o.tables = L.HuffTable()
+        rc = L.load().w3_huff_tables_from_counts(c.ctypes.data_as(C.c_void_p), huff_size, rem_huff_size, C.byref(o.tables))
+        if rc:
+            raise W3Error(rc, "HuffHistory::new: no symbols, or max length too big / too small for the alphabet")
+        return o
+
+    @classmethod
+    def new_on(cls, ctx, data, huff_size, rem_huff_size):
+        """new() with the histogram taken on the device: `data` is host data or a uint8 tensor on ctx's device"""
+        return cls.from_counts(ctx.histogram_of(data), huff_size, rem_huff_size)
+
+    @classmethod
     def from_tables(cls, code, length, rem_code, rem_length):
         o = cls.__new__(cls)
         o.tables = L.HuffTable()
@@ -136,6 +166,22 @@ class HuffCode:
     @classmethod
     def new(cls, data, huffman_size):
         return cls(data, huffman_size)
+
+    @classmethod
+    def from_counts(cls, counts, huffman_size):
+        """the code of a byte histogram (256 counts): w3_huff_code_from_counts, the builder new() runs behind its own histogram loop"""
+        c = _counts(counts)
+        o = cls.__new__(cls)
+        o.table = L.HuffCode()
+        rc = L.load().w3_huff_code_from_counts(c.ctypes.data_as(C.c_void_p), huffman_size, C.byref(o.table))
+        if rc:
+            raise W3Error(rc, "package_merge: no symbols, or max length too big / too small for the alphabet")
+        return o
+
+    @classmethod
+    def new_on(cls, ctx, data, huffman_size):
+        """new() with the histogram taken on the device: `data` is host data or a uint8 tensor on ctx's device"""
+        return cls.from_counts(ctx.histogram_of(data), huffman_size)
 
     @classmethod
     def from_tables(cls, codes, lens):

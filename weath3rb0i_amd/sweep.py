@@ -89,6 +89,15 @@ def _stats_csize(ctx, model, data, block_size, repeats):
     return best
 
 
+def _histogram(ctx, data):
+    """the input's byte histogram, counted on ctx's device (Context.histogram).  A stand-in context that has no device behind it, as
+    the tests of the drivers' lines use, has no such call: for it the bytes are counted here."""
+    if hasattr(ctx, "histogram"):
+        return ctx.histogram(data)
+    import numpy as np
+    return np.bincount(np.frombuffer(bytes(data), dtype=np.uint8), minlength=256).astype(np.uint64)
+
+
 def sweep_entropy_ac(ctx, data, block_size=65536, ctx_bits=range(8, 31), alignment_bits=range(0, 5), repeats=1, out=print):
     """`src/bin/entropy-hashing-ac/main.rs:11-48`: OrderNEntropy(ctx_bits, alignment_bits, ACHistory(ctx_bits - alignment_bits,
     StationaryModel::new(buf))) for ctx_bits 8..=30 x alignment_bits 0..=4, line format of `exec` (:64-73), best per ctx_bits and
@@ -98,7 +107,7 @@ def sweep_entropy_ac(ctx, data, block_size=65536, ctx_bits=range(8, 31), alignme
     best = [len(data)] * levels
     params = [(0, 0)] * levels
     table = {}
-    station = models.StationaryModel.new(data)
+    station = models.StationaryModel.new_on(ctx, data)   # walked on the device
     for b in ctx_bits:
         best[1] = len(data)
         params[1] = (0, 0)
@@ -122,11 +131,12 @@ def sweep_entropy_ac(ctx, data, block_size=65536, ctx_bits=range(8, 31), alignme
 
 def sweep_entropy_huff(ctx, data, block_size=65536, rem_huff_sizes=range(7, 13), huff_sizes=range(8, 16), ctx_bits=range(8, 31), repeats=1, out=print):
     """`src/bin/entropy-hashing-huff/main.rs:11-50`: OrderNEntropy(ctx_bits, 0, HuffHistory::new(buf, huff_size, rem_huff_size)), three levels
-    of best.  The tables come from w3_huff_tables (ties among equal counts in ascending symbol order: INTEGRATION.md)."""
+    of best.  The tables come from one device histogram and w3_huff_tables_from_counts (ties among equal counts in ascending symbol order: INTEGRATION.md)."""
     levels = 3
     best = [len(data)] * levels
     params = [(0, 0, 0)] * levels
     table = {}
+    counts = _histogram(ctx, data)   # ONE histogram for all the (rem_huff_size, huff_size) pairs
     for r in rem_huff_sizes:
         best[1] = len(data)
         params[1] = (0, 0, 0)
@@ -134,7 +144,7 @@ def sweep_entropy_huff(ctx, data, block_size=65536, rem_huff_sizes=range(7, 13),
             best[2] = len(data)
             params[2] = (0, 0, 0)
             try:
-                hist = models.HuffHistory.new(data, h, r)
+                hist = models.HuffHistory.from_counts(counts, h, r)
             except models.W3Error:   # the reference panics when the length limit is too small for the alphabet (package_merge.rs)
                 out("[eh-huff] [rem_hsize: %2d, hsize: %2d] length limit too small for the alphabet" % (r, h))
                 continue
@@ -166,9 +176,10 @@ def sweep_ac_over_huffman(ctx, data, block_size=65536, huffman_sizes=range(7, 16
     params = [(0, 0)] * levels
     table = {}
     codes, sizes = [], []
+    counts = _histogram(ctx, data)   # ONE histogram for all the sizes
     for h in huffman_sizes:
         try:
-            codes.append(models.HuffCode.new(data, h))
+            codes.append(models.HuffCode.from_counts(counts, h))
             sizes.append(h)
         except models.W3Error:
             pass
