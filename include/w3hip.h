@@ -178,9 +178,11 @@ enum {
     W3_OPT_FAULT_KERNELS = 13, /* test hook, with W3_OPT_VARIANT bit 32: bit mask (1 .. 7) of the kernels whose returning LDS adds the injected
                            fault mis-orders — 1 = k_predict_small's rounds (default), 2 = k_rank_sorted's rounds, 4 = k_partition8's
                            cursor adds (two records of one bin swap their slots in the tile: a permutation, never another index) */
-    W3_OPT_AOH_BATCH_BLOCKS = 14 /* test hook in the manner of W3_OPT_HOST_CHUNK_BLOCKS: most blocks per batch of the two-phase form of AC over
+    W3_OPT_AOH_BATCH_BLOCKS = 14, /* test hook in the manner of W3_OPT_HOST_CHUNK_BLOCKS: most blocks per batch of the two-phase form of AC over
                            Huffman, and most jobs per batch of its ranges calls and of the sixteen-lane full decode (0 = default: as many
                            as the device memory budget holds; the output is the same) */
+    W3_OPT_EXPORT_EPOCH = 15 /* test hook in the manner of W3_OPT_AOH_BATCH_BLOCKS: bytes per epoch of w3_export_counters_device / _staged
+                           (0 = default; the result is the same).  A multiple of 1 KiB, at most 2^28: anything else is W3_E_INVALID */
 };
 enum { W3_PATH_AUTO = 0, W3_PATH_GENERIC = 1, W3_PATH_TWOPHASE = 2,
        W3_PATH_SPEC = 3 /* reported only (w3_timing.path of the AC-over-Huffman decode and ranges calls that took the sixteen-lane decoder);
@@ -526,6 +528,29 @@ int w3_sweep_ac_over_huffman_device(w3_ctx *ctx, const uint8_t *d_in, size_t n, 
  * `in` as ONE stream, i.e. the state the reference's model is in when compress() returns: counters[ctx] = n0 | n1 << 16
  * (models/counter.rs:4-6) for ctx in 0 .. 2^bits_in_context.  bits_in_context <= 28, n <= 2^28.                       */
 int w3_export_counters(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t n, uint32_t *counters);
+
+/* ---- the same for whole inputs of any size, on the device (csrc/w3_export.h) ---------------------------------------
+ * For ONE adaptive W3_NODE_ORDERN leaf with history == W3_HIST_NONE, not frozen, bits <= 28, the context of a step is a pure function of
+ * the input and a Counter depends on the order of its updates only where it halves.  The input goes through in epochs: per epoch every
+ * context's visits are counted by bit value (k_ctx_count), added to the table where no count can have reached 65535 (k_ctx_apply), and the
+ * few contexts in which one did are replayed exactly by a wavefront each (k_ctx_replay).  The result equals w3_export_counters bit for
+ * bit.  Every other spec is W3_E_UNSUPPORTED (leaves with an entropy history keep a key chain that is serial over one stream: the
+ * one-lane call above is their route, w3_last_error says so).
+ *   w3_export_counters_device   d_counters = uint32[2^bits] in DEVICE memory, every entry written.  n < 2^32 - 4096 per call, n == 0 gives
+ *                               zeros, stream NULL = the context's, the call synchronises its stream before it returns.
+ *   w3_export_counters_staged   a host buffer of ANY length and a host result, staged as w3_histogram stages (pieces of 2 GiB;
+ *                               W3_OPT_HOST_CHUNK_BLOCKS: nominal 64 KiB blocks per piece); the table stays on the device from piece to
+ *                               piece, the history bits and the offset in the stream are carried across the cuts.
+ * Both are W3_E_INVALID while a job is in flight.  w3_export_get_profile: what the last of these calls did — the integer fields always,
+ * the times under W3_OPT_TIMING (per kernel only up to 4,096 epochs per piece; total_ms: the pieces' kernels from the first to the last,
+ * the staged form's copies to and from the device not included). */
+typedef struct w3_export_profile {
+    uint64_t epochs, replays, halvings;   /* epochs run; (context, epoch) pairs replayed; halvings the replays applied */
+    float count_ms, apply_ms, replay_ms, total_ms;
+} w3_export_profile;
+int w3_export_counters_device(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *d_in, size_t n, uint32_t *d_counters, void *stream);
+int w3_export_counters_staged(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t n, uint32_t *counters);
+int w3_export_get_profile(const w3_ctx *ctx, w3_export_profile *out);
 
 /* ---- the reference's whole-file container ----------------------------------
  * compress()/decompress() of main.rs:89-144: b"w30i" + u64 BE length + ONE

@@ -16,6 +16,7 @@ W3_MAX_HUFF = 4
 W3_OK, W3_E_INVALID, W3_E_NOSPACE, W3_E_HIP, W3_E_UNSUPPORTED, W3_E_NOMEM, W3_E_FORMAT = 0, -1, -2, -3, -4, -5, -6
 W3_E_CORRUPT = -7
 W3_OPT_PATH, W3_OPT_TIMING, W3_OPT_CODER, W3_OPT_ACC_LIMIT, W3_OPT_DEBUG_STAMPS, W3_OPT_VARIANT, W3_OPT_SLOT_BUDGET_MB, W3_OPT_VERIFY, W3_OPT_FAULT_BLOCK, W3_OPT_TUNE, W3_OPT_HOST_CHUNK_BLOCKS, W3_OPT_FAULT_KERNELS, W3_OPT_AOH_BATCH_BLOCKS = 1, 2, 3, 4, 5, 7, 8, 9, 10, 11, 12, 13, 14
+W3_OPT_EXPORT_EPOCH = 15
 W3_VAR_NO_LDS_ATOMICS, W3_VAR_PARTITION4, W3_VAR_NO_CHAINED_PARTITION, W3_VAR_CM_UNSTAGED, W3_VAR_NO_SIDE_STREAM, W3_VAR_INJECT_LDS_FAULT = 1, 2, 4, 8, 16, 32
 W3_VAR_HALF_CU, W3_VAR_FULL_CU = 64, 128
 W3_VAR_SLOT_TABLE, W3_VAR_SLOT_SORTED, W3_VAR_DECODE_LANE, W3_VAR_AOH_DECODE_SPEC = 256, 512, 1024, 2048
@@ -64,6 +65,11 @@ class PrepProfile(C.Structure):   # w3_prep_profile
                 ("halvings", C.c_uint32 * 8), ("table", C.c_uint16 * 8), ("counts", C.c_uint64 * 256)]
 
 
+class ExportProfile(C.Structure):   # w3_export_profile
+    _fields_ = [("epochs", C.c_uint64), ("replays", C.c_uint64), ("halvings", C.c_uint64),
+                ("count_ms", C.c_float), ("apply_ms", C.c_float), ("replay_ms", C.c_float), ("total_ms", C.c_float)]
+
+
 W3_STAT_TILE, W3_STAT_BATCH, W3_HIST_REP = 4096, 64, 16  # include/w3hip.h "table preparation on the device"
 
 EXPORTS = [
@@ -82,6 +88,7 @@ EXPORTS = [
     "w3_decode_ranges_device_checked", "w3_aoh_decode_blocks_checked", "w3_aoh_decode_ranges_checked", "w3_aoh_decode_ranges_device_checked",
     "w3_histogram", "w3_histogram_device", "w3_stationary_table_staged", "w3_stationary_table_device", "w3_huff_code_from_counts",
     "w3_huff_tables_from_counts", "w3_table_prep_profile",
+    "w3_export_counters_device", "w3_export_counters_staged", "w3_export_get_profile",
 ]
 
 _lib = None
@@ -186,6 +193,9 @@ def load():
     lib.w3_huff_code_from_counts.argtypes = [vp, u8, hc]
     lib.w3_huff_tables_from_counts.argtypes = [vp, u8, u8, C.POINTER(HuffTable)]
     lib.w3_table_prep_profile.argtypes = [vp, vp, sz, C.c_uint32, C.POINTER(PrepProfile)]
+    lib.w3_export_counters_device.argtypes = [vp, C.POINTER(ModelSpec), vp, sz, vp, vp]
+    lib.w3_export_counters_staged.argtypes = [vp, C.POINTER(ModelSpec), vp, sz, vp]
+    lib.w3_export_get_profile.argtypes = [vp, C.POINTER(ExportProfile)]
     lib.w3_rccl_library.argtypes = [C.c_char_p]
     lib.w3_rccl_status.argtypes = [C.c_char_p, sz]
     _lib = lib

@@ -131,6 +131,11 @@ class Context:
         ranges calls and of the sixteen-lane full decode (0 = from the memory budget)."""
         self._chk(self.lib.w3_ctx_set_option(self.h, L.W3_OPT_AOH_BATCH_BLOCKS, int(blocks)))
 
+    def set_export_epoch(self, nbytes=0):
+        """W3_OPT_EXPORT_EPOCH: bytes per epoch of export_counters_device / export_counters_staged (0 = default; a multiple of 1 KiB, at
+        most 2^28; the result is the same)."""
+        self._chk(self.lib.w3_ctx_set_option(self.h, L.W3_OPT_EXPORT_EPOCH, int(nbytes)))
+
     def set_timing(self, on=True):
         self._chk(self.lib.w3_ctx_set_option(self.h, L.W3_OPT_TIMING, int(on)))
 
@@ -311,6 +316,43 @@ class Context:
         t = np.zeros(1 << bits, dtype=np.uint32)
         self._chk(self.lib.w3_export_counters(self.h, C.byref(spec), a.ctypes.data_as(C.c_void_p), len(a), t.ctypes.data_as(C.c_void_p)))
         return (t & 0xFFFF).astype(np.uint16), (t >> 16).astype(np.uint16)
+
+    def export_counters_device(self, model, d_in, d_counters=None, stream=None):
+        """w3_export_counters_device: the same table for ONE adaptive OrderN leaf without entropy history, computed in parallel over the
+        whole input (csrc/w3_export.h).  d_in: a torch.uint8 CUDA tensor (contiguous).  -> a torch.int32 CUDA tensor of 2^bits packed
+        counters n0 | n1 << 16 (d_counters when given: every entry is overwritten)"""
+        import torch
+        if d_in.dtype != torch.uint8 or not d_in.is_cuda or not d_in.is_contiguous():
+            raise W3Error(L.W3_E_INVALID, "d_in: a contiguous torch.uint8 CUDA tensor")
+        spec = model.spec()
+        entries = 1 << spec.nodes[0].bits
+        if d_counters is None:
+            if spec.n_nodes != 1 or spec.nodes[0].bits > 28:   # (refused below, before the tensor is touched: do not allocate 2^bits for it)
+                entries = 1
+            d_counters = torch.empty(entries, dtype=torch.int32, device=d_in.device)
+        elif (d_counters.dtype != torch.int32 or d_counters.numel() != entries or not d_counters.is_contiguous()
+              or d_counters.device != d_in.device):
+            raise W3Error(L.W3_E_INVALID, "d_counters: a contiguous torch.int32 tensor of 2^bits entries on d_in's device")
+        st = C.c_void_p(stream) if stream else None
+        self._chk(self.lib.w3_export_counters_device(self.h, C.byref(spec), C.c_void_p(d_in.data_ptr()), d_in.numel(),
+                                                     C.c_void_p(d_counters.data_ptr()), st))
+        return d_counters
+
+    def export_counters_staged(self, model, data):
+        """w3_export_counters_staged: the same from host `data` of any length, staged through the device in pieces.
+        -> (n0: np.uint16[2^bits], n1: np.uint16[2^bits]), the shape export_counters returns"""
+        spec = model.spec()
+        a = _u8(data)
+        refused = spec.n_nodes != 1 or spec.nodes[0].bits > 28
+        t = np.zeros(1 if refused else 1 << spec.nodes[0].bits, dtype=np.uint32)
+        self._chk(self.lib.w3_export_counters_staged(self.h, C.byref(spec), a.ctypes.data_as(C.c_void_p), len(a), t.ctypes.data_as(C.c_void_p)))
+        return (t & 0xFFFF).astype(np.uint16), (t >> 16).astype(np.uint16)
+
+    def export_profile(self):
+        """w3_export_get_profile: what the last export_counters_device / _staged call did (the times under set_timing())"""
+        p = L.ExportProfile()
+        self._chk(self.lib.w3_export_get_profile(self.h, C.byref(p)))
+        return {k: getattr(p, k) for k, _ in L.ExportProfile._fields_}
 
     def predict_blocks(self, model, data, block_size):
         spec = model.spec()

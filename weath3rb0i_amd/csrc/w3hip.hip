@@ -30,6 +30,7 @@
 #include "w3_rccl.h"
 #include "w3_crc.h"
 #include "w3_prep.h"
+#include "w3_export.h"
 
 using namespace w3;
 
@@ -116,6 +117,12 @@ struct w3_ctx {
     // crc_tab: a table on its way to or from a host caller; crc_res: where the result lands on the host
     DevBuf crc_ws, crc_tab;
     DevBuf prep_ws;   // table preparation (w3_prep.h): the counts, the walk's state, the histogram's partials, the tiles' counts (W3_PREP_WS_*)
+    // the parallel statistics export (w3_export.h): the delta table D (all zero between calls: exp_d_zero = the bytes known to be), the
+    // staged form's table, the replay list, the kernels' stats words
+    DevBuf exp_d, exp_s, exp_list, exp_stats;
+    size_t exp_d_zero = 0;
+    uint32_t export_epoch = 0;                      // W3_OPT_EXPORT_EPOCH (0 = W3_EXP_EPOCH_DEFAULT)
+    w3_export_profile exp_prof{};
     uint64_t crc_res[2] = {~0ull, 0};
     // What a job takes from the context when a call is prepared (hand_options): the two-phase options (w3_ctx_set_option), the
     // context-mixing look-up tables in cm_luts, and the lane-order self-test's verdict (-1 not run yet under this variant, 1 = returning
@@ -254,7 +261,8 @@ extern "C" void w3_ctx_destroy(w3_ctx *ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
     DevBuf *bufs[] = {&ctx->tables, &ctx->lens, &ctx->total, &ctx->io_in, &ctx->io_out, &ctx->coffs, &ctx->misc, &ctx->cm_luts, &ctx->achash_luts,
-                      &ctx->sweep, &ctx->aoh, &ctx->rg_stage, &ctx->rg_meta, &ctx->crc_ws, &ctx->crc_tab, &ctx->prep_ws};
+                      &ctx->sweep, &ctx->aoh, &ctx->rg_stage, &ctx->rg_meta, &ctx->crc_ws, &ctx->crc_tab, &ctx->prep_ws,
+                      &ctx->exp_d, &ctx->exp_s, &ctx->exp_list, &ctx->exp_stats};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (ctx->h_rg) (void)hipHostFree(ctx->h_rg);
@@ -348,6 +356,10 @@ extern "C" int w3_ctx_set_option(w3_ctx *ctx, int opt, int64_t value) {
     case W3_OPT_AOH_BATCH_BLOCKS:
         if (value < 0 || value > 0x7FFFFFFF) return W3_E_INVALID;
         ctx->aoh_batch_blocks = (uint32_t)value;
+        return W3_OK;
+    case W3_OPT_EXPORT_EPOCH:
+        if (value < 0 || value > (int64_t)W3_EXP_EPOCH_MAX || value % 1024) { ctx->err = "an export epoch is a multiple of 1 KiB, at most 2^28 bytes"; return W3_E_INVALID; }
+        ctx->export_epoch = (uint32_t)value;
         return W3_OK;
     default: return W3_E_INVALID;
     }
@@ -3398,6 +3410,149 @@ extern "C" int w3_export_counters(w3_ctx *ctx, const w3_model_spec *spec, const 
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(counters, ctx->tables.p, entries * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
+    return W3_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The same on the device for whole inputs of any size (w3_export.h): count, apply and replay per epoch.
+// ---------------------------------------------------------------------------
+static int export_args(w3_ctx *ctx, const w3_model_spec *spec, const void *in, size_t n, const void *out, bool one_device, ExpModel &m) {
+    int rc = check_args(ctx, n, W3_PREP_NOMINAL_BLOCK, one_device);
+    if (rc) return rc;
+    if ((rc = jobs_idle(ctx))) return rc;   // (the workspace is the context's)
+    ParsedSpec ps;
+    if ((rc = parse_spec(spec, ps))) return rc;
+    if (ps.n_leaves != 1 || ps.n_apm || ps.has_slot || ps.leaf[0].kind != W3_NODE_ORDERN || ps.leaf[0].frozen || ps.leaf[0].history != W3_HIST_NONE) {
+        ctx->err = "the parallel export takes ONE adaptive OrderN leaf without entropy history: w3_export_counters (one lane) is the route for leaves with an entropy history";
+        return W3_E_UNSUPPORTED;
+    }
+    if (ps.leaf[0].bits > W3_EXP_MAX_BITS) { ctx->err = "tables above 2^28 counters are not exported"; return W3_E_UNSUPPORTED; }
+    if (!out || (!in && n)) return W3_E_INVALID;
+    m.bits = ps.leaf[0].bits; m.align = ps.leaf[0].align;
+    return W3_OK;
+}
+
+// the workspace for a stream of `upto` bytes: D (zero), the replay list, the stats words
+static int export_ensure(w3_ctx *ctx, hipStream_t s, const ExpModel &m, uint64_t upto) {
+    const size_t need = (size_t)8 << m.bits;
+    const void *had = ctx->exp_d.p;
+    ENSURE(ctx, ctx->exp_d, need);
+    if (ctx->exp_d.p != had) ctx->exp_d_zero = 0;
+    if (ctx->exp_d_zero < need) {
+        HIPCHK(ctx, hipMemsetAsync(ctx->exp_d.p, 0, need, s));
+        ctx->exp_d_zero = need;
+    }
+    ENSURE(ctx, ctx->exp_list, (size_t)exp_list_cap(m.bits, upto) * 4);
+    ENSURE(ctx, ctx->exp_stats, W3_EXP_ST_WORDS * 4);
+    return W3_OK;
+}
+
+// One piece that lies on the device through its epochs, S = the table before it and behind it; synchronises s.  `upto`: the stream's
+// bytes through this piece's end (the list's bound).  Adds to ctx->exp_prof.
+static int export_piece(w3_ctx *ctx, hipStream_t s, const ExpPiece &pc, const ExpModel &m, uint32_t *S) {
+    const uint64_t E = ctx->export_epoch ? ctx->export_epoch : W3_EXP_EPOCH_DEFAULT, nctx = 1ull << m.bits;
+    const uint64_t epochs = (pc.n + E - 1) / E;
+    const uint32_t cap = (uint32_t)exp_list_cap(m.bits, pc.abs0 + pc.n);
+    exp_u64 *D = (exp_u64 *)ctx->exp_d.p;
+    uint32_t *list = (uint32_t *)ctx->exp_list.p, *stats = (uint32_t *)ctx->exp_stats.p;
+    const size_t zero_had = ctx->exp_d_zero;
+    ctx->exp_d_zero = 0;   // (until the piece is through: a failed call leaves D in an unknown state)
+    std::vector<hipEvent_t> ev;
+    struct Events {   // destroyed on every way out
+        std::vector<hipEvent_t> &v;
+        ~Events() { for (hipEvent_t e : v) (void)hipEventDestroy(e); }
+    } events{ev};
+    const bool per_kernel = ctx->opt_timing && epochs <= 4096;
+    if (ctx->opt_timing) {
+        ev.resize(per_kernel ? 3 * (size_t)epochs + 1 : 2, nullptr);
+        for (auto &e : ev) HIPCHK(ctx, hipEventCreate(&e));
+        HIPCHK(ctx, hipEventRecord(ev[0], s));
+    }
+    HIPCHK(ctx, hipMemsetAsync(stats, 0, W3_EXP_ST_WORDS * 4, s));
+    const uint32_t apply_wg = (uint32_t)std::min<uint64_t>((nctx + 255) / 256, 8192);
+    const uint32_t replay_wg = std::min<uint32_t>(cap, W3_EXP_REPLAY_MAX_WG);
+    for (uint64_t k = 0; k < epochs; k++) {
+        const uint64_t e0 = k * E, len = std::min<uint64_t>(E, pc.n - e0), rows = exp_rows(pc, e0, len);
+        if (m.bits <= W3_EXP_LDS_BITS) {
+            const uint32_t wg = (uint32_t)std::min<uint64_t>((rows + 3) / 4, W3_EXP_LDS_MAX_WG);
+            hipLaunchKernelGGL((k_ctx_count_lds<W3_EXP_LDS_REP>), dim3(wg), dim3(256), (size_t)(8u << m.bits) * W3_EXP_LDS_REP, s, pc, e0, len, m, D, stats);
+        } else {
+            const uint32_t wg = (uint32_t)std::min<uint64_t>((rows + 3) / 4, W3_EXP_GLOBAL_MAX_WG);
+            hipLaunchKernelGGL(k_ctx_count, dim3(wg), dim3(256), 0, s, pc, e0, len, m, D, stats);
+        }
+        HIPCHK(ctx, hipGetLastError());
+        if (per_kernel) HIPCHK(ctx, hipEventRecord(ev[3 * k + 1], s));
+        hipLaunchKernelGGL(k_ctx_apply, dim3(apply_wg), dim3(256), 0, s, D, S, nctx, list, cap, stats);
+        HIPCHK(ctx, hipGetLastError());
+        if (per_kernel) HIPCHK(ctx, hipEventRecord(ev[3 * k + 2], s));
+        hipLaunchKernelGGL(k_ctx_replay, dim3(replay_wg), dim3(64), 0, s, pc, e0, len, m, S, (const uint32_t *)list, cap, stats);
+        HIPCHK(ctx, hipGetLastError());
+        if (per_kernel) HIPCHK(ctx, hipEventRecord(ev[3 * k + 3], s));
+    }
+    if (ctx->opt_timing && !per_kernel) HIPCHK(ctx, hipEventRecord(ev[1], s));
+    uint32_t st[W3_EXP_ST_WORDS] = {0};
+    HIPCHK(ctx, hipMemcpyAsync(st, stats, sizeof st, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    if (st[W3_EXP_ST_OVERFLOW]) { ctx->err = "the export's replay list exceeded its bound"; return W3_E_HIP; }
+    ctx->exp_d_zero = zero_had;   // (k_ctx_apply zeroed what k_ctx_count added)
+    w3_export_profile &pr = ctx->exp_prof;
+    pr.epochs += epochs; pr.replays += st[W3_EXP_ST_REPLAYS]; pr.halvings += st[W3_EXP_ST_HALVINGS];
+    if (ctx->opt_timing) {
+        float ms = 0.f;
+        if (per_kernel)
+            for (uint64_t k = 0; k < epochs; k++) {
+                float *into[3] = {&pr.count_ms, &pr.apply_ms, &pr.replay_ms};
+                for (int j = 0; j < 3; j++) { HIPCHK(ctx, hipEventElapsedTime(&ms, ev[3 * k + j], ev[3 * k + j + 1])); *into[j] += ms; }
+            }
+        HIPCHK(ctx, hipEventElapsedTime(&ms, ev.front(), ev.back()));
+        pr.total_ms += ms;
+    }
+    return W3_OK;
+}
+
+extern "C" int w3_export_counters_device(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *d_in, size_t n, uint32_t *d_counters, void *stream) {
+    ExpModel m;
+    int rc = export_args(ctx, spec, d_in, n, d_counters, true, m);
+    if (rc) return rc;
+    ctx->exp_prof = w3_export_profile();
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    HIPCHK(ctx, hipMemsetAsync(d_counters, 0, (size_t)4 << m.bits, s));
+    if (n == 0) { HIPCHK(ctx, hipStreamSynchronize(s)); return W3_OK; }
+    if ((rc = export_ensure(ctx, s, m, n))) return rc;
+    const ExpPiece pc = {d_in, n, 0, 0};
+    return export_piece(ctx, s, pc, m, d_counters);
+}
+
+extern "C" int w3_export_counters_staged(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t n, uint32_t *counters) {
+    ExpModel m;
+    int rc = export_args(ctx, spec, in, n, counters, false, m);
+    if (rc) return rc;
+    ctx->exp_prof = w3_export_profile();
+    const size_t bytes = (size_t)4 << m.bits;
+    if (n == 0) { memset(counters, 0, bytes); return W3_OK; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t piece = host_run_blocks(ctx, W3_PREP_NOMINAL_BLOCK) * (size_t)W3_PREP_NOMINAL_BLOCK;
+    if ((rc = export_ensure(ctx, s, m, n))) return rc;
+    ENSURE(ctx, ctx->exp_s, bytes);
+    ENSURE(ctx, ctx->io_in, std::min(n, piece));
+    HIPCHK(ctx, hipMemsetAsync(ctx->exp_s.p, 0, bytes, s));
+    for (size_t o0 = 0; o0 < n; o0 += piece) {
+        const size_t len = std::min(piece, n - o0);
+        uint32_t carry = 0;   // the four stream bytes before the piece
+        for (size_t k = o0 < 4 ? 0 : o0 - 4; k < o0; k++) carry = (carry << 8) | in[k];
+        HIPCHK(ctx, hipMemcpyAsync(ctx->io_in.p, in + o0, len, hipMemcpyHostToDevice, s));
+        const ExpPiece pc = {(const uint8_t *)ctx->io_in.p, len, o0, carry};
+        if ((rc = export_piece(ctx, s, pc, m, (uint32_t *)ctx->exp_s.p))) return rc;   // (synchronises: the next piece overwrites io_in)
+    }
+    HIPCHK(ctx, hipMemcpy(counters, ctx->exp_s.p, bytes, hipMemcpyDeviceToHost));
+    return W3_OK;
+}
+
+extern "C" int w3_export_get_profile(const w3_ctx *ctx, w3_export_profile *out) {
+    if (!ctx || !out) return W3_E_INVALID;
+    *out = ctx->exp_prof;
     return W3_OK;
 }
 
