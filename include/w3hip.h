@@ -534,8 +534,8 @@ int w3_export_counters(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in
  * the input and a Counter depends on the order of its updates only where it halves.  The input goes through in epochs: per epoch every
  * context's visits are counted by bit value (k_ctx_count), added to the table where no count can have reached 65535 (k_ctx_apply), and the
  * few contexts in which one did are replayed exactly by a wavefront each (k_ctx_replay).  The result equals w3_export_counters bit for
- * bit.  Every other spec is W3_E_UNSUPPORTED (leaves with an entropy history keep a key chain that is serial over one stream: the
- * one-lane call above is their route, w3_last_error says so).
+ * bit.  Every other spec is W3_E_UNSUPPORTED (leaves with an entropy history go through w3_export_entropy_device / _staged below or the
+ * one-lane call above, w3_last_error says so).
  *   w3_export_counters_device   d_counters = uint32[2^bits] in DEVICE memory, every entry written.  n < 2^32 - 4096 per call, n == 0 gives
  *                               zeros, stream NULL = the context's, the call synchronises its stream before it returns.
  *   w3_export_counters_staged   a host buffer of ANY length and a host result, staged as w3_histogram stages (pieces of 2 GiB;
@@ -551,6 +551,24 @@ typedef struct w3_export_profile {
 int w3_export_counters_device(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *d_in, size_t n, uint32_t *d_counters, void *stream);
 int w3_export_counters_staged(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t n, uint32_t *counters);
 int w3_export_get_profile(const w3_ctx *ctx, w3_export_profile *out);
+
+/* ---- ... and for leaves with an entropy history (csrc/w3_export_entropy.h) -------------------------------------------
+ * The general single-leaf entry point: ONE adaptive W3_NODE_ORDERN leaf, not frozen, bits <= 28, history any of W3_HIST_NONE, RAW, AC,
+ * HUFF.  ACHistory::hash and HuffHistory::hash are pure functions of the input too (the 64 stream bits before a step; the trailing bytes
+ * whose code lengths sum to 32), so per epoch a key stage writes the finished context of every step (one uint32 per step: keyed epochs
+ * are at most 2^24 bytes whatever W3_OPT_EXPORT_EPOCH says) and count and replay run over the keys.  NONE and RAW run the kernels of the
+ * calls above.  Exact for any caller-supplied w3_huff_table, zero-length codes included (an epoch whose bounded walks meet a run of them
+ * is redone by the recurrence: huff_fixed_epochs).  Everything else is W3_E_UNSUPPORTED.  The contracts are those of
+ * w3_export_counters_device / _staged: every entry written, n < 2^32 - 4096 for the device form, any length staged, n == 0 gives zeros,
+ * W3_E_INVALID while a job is in flight, nothing written on a refusal.  The result equals w3_export_counters bit for bit. */
+typedef struct w3_export_entropy_profile {
+    w3_export_profile base;      /* epochs, replays, halvings, count/apply/replay/total ms: as for the calls above */
+    float    key_ms;             /* the key stage (under W3_OPT_TIMING) */
+    uint64_t huff_fixed_epochs;  /* epochs whose Huffman keys were redone by the recurrence */
+} w3_export_entropy_profile;
+int w3_export_entropy_device(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *d_in, size_t n, uint32_t *d_counters, void *stream);
+int w3_export_entropy_staged(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t n, uint32_t *counters);
+int w3_export_entropy_get_profile(const w3_ctx *ctx, w3_export_entropy_profile *out);
 
 /* ---- the reference's whole-file container ----------------------------------
  * compress()/decompress() of main.rs:89-144: b"w30i" + u64 BE length + ONE

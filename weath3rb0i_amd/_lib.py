@@ -70,6 +70,10 @@ class ExportProfile(C.Structure):   # w3_export_profile
                 ("count_ms", C.c_float), ("apply_ms", C.c_float), ("replay_ms", C.c_float), ("total_ms", C.c_float)]
 
 
+class ExportEntropyProfile(C.Structure):   # w3_export_entropy_profile
+    _fields_ = [("base", ExportProfile), ("key_ms", C.c_float), ("huff_fixed_epochs", C.c_uint64)]
+
+
 W3_STAT_TILE, W3_STAT_BATCH, W3_HIST_REP = 4096, 64, 16  # include/w3hip.h "table preparation on the device"
 
 EXPORTS = [
@@ -89,6 +93,7 @@ EXPORTS = [
     "w3_histogram", "w3_histogram_device", "w3_stationary_table_staged", "w3_stationary_table_device", "w3_huff_code_from_counts",
     "w3_huff_tables_from_counts", "w3_table_prep_profile",
     "w3_export_counters_device", "w3_export_counters_staged", "w3_export_get_profile",
+    "w3_export_entropy_device", "w3_export_entropy_staged", "w3_export_entropy_get_profile",
 ]
 
 _lib = None
@@ -196,6 +201,9 @@ def load():
     lib.w3_export_counters_device.argtypes = [vp, C.POINTER(ModelSpec), vp, sz, vp, vp]
     lib.w3_export_counters_staged.argtypes = [vp, C.POINTER(ModelSpec), vp, sz, vp]
     lib.w3_export_get_profile.argtypes = [vp, C.POINTER(ExportProfile)]
+    lib.w3_export_entropy_device.argtypes = [vp, C.POINTER(ModelSpec), vp, sz, vp, vp]
+    lib.w3_export_entropy_staged.argtypes = [vp, C.POINTER(ModelSpec), vp, sz, vp]
+    lib.w3_export_entropy_get_profile.argtypes = [vp, C.POINTER(ExportEntropyProfile)]
     lib.w3_rccl_library.argtypes = [C.c_char_p]
     lib.w3_rccl_status.argtypes = [C.c_char_p, sz]
     _lib = lib

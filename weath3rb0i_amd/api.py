@@ -354,6 +354,47 @@ class Context:
         self._chk(self.lib.w3_export_get_profile(self.h, C.byref(p)))
         return {k: getattr(p, k) for k, _ in L.ExportProfile._fields_}
 
+    def export_entropy_device(self, model, d_in, d_counters=None, stream=None):
+        """w3_export_entropy_device: export_counters_device for ONE adaptive leaf with any history — OrderN, or OrderNEntropy over
+        RawHistory, ACHistory or HuffHistory (init_model()'s leaf) — with a key stage per epoch (csrc/w3_export_entropy.h).  d_in: a
+        torch.uint8 CUDA tensor (contiguous).  -> a torch.int32 CUDA tensor of 2^bits packed counters n0 | n1 << 16 (d_counters when
+        given: every entry is overwritten)"""
+        import torch
+        if d_in.dtype != torch.uint8 or not d_in.is_cuda or not d_in.is_contiguous():
+            raise W3Error(L.W3_E_INVALID, "d_in: a contiguous torch.uint8 CUDA tensor")
+        spec = model.spec()
+        entries = 1 << spec.nodes[0].bits
+        if d_counters is None:
+            if spec.n_nodes != 1 or spec.nodes[0].bits > 28:   # (refused below, before the tensor is touched: do not allocate 2^bits for it)
+                entries = 1
+            d_counters = torch.empty(entries, dtype=torch.int32, device=d_in.device)
+        elif (d_counters.dtype != torch.int32 or d_counters.numel() != entries or not d_counters.is_contiguous()
+              or d_counters.device != d_in.device):
+            raise W3Error(L.W3_E_INVALID, "d_counters: a contiguous torch.int32 tensor of 2^bits entries on d_in's device")
+        st = C.c_void_p(stream) if stream else None
+        self._chk(self.lib.w3_export_entropy_device(self.h, C.byref(spec), C.c_void_p(d_in.data_ptr()), d_in.numel(),
+                                                    C.c_void_p(d_counters.data_ptr()), st))
+        return d_counters
+
+    def export_entropy_staged(self, model, data):
+        """w3_export_entropy_staged: the same from host `data` of any length, staged through the device in pieces.
+        -> (n0: np.uint16[2^bits], n1: np.uint16[2^bits]), the shape export_counters returns"""
+        spec = model.spec()
+        a = _u8(data)
+        refused = spec.n_nodes != 1 or spec.nodes[0].bits > 28
+        t = np.zeros(1 if refused else 1 << spec.nodes[0].bits, dtype=np.uint32)
+        self._chk(self.lib.w3_export_entropy_staged(self.h, C.byref(spec), a.ctypes.data_as(C.c_void_p), len(a), t.ctypes.data_as(C.c_void_p)))
+        return (t & 0xFFFF).astype(np.uint16), (t >> 16).astype(np.uint16)
+
+    def export_entropy_profile(self):
+        """w3_export_entropy_get_profile: what the last export_entropy_device / _staged call did (the times under set_timing()):
+        export_profile()'s fields, key_ms and huff_fixed_epochs"""
+        p = L.ExportEntropyProfile()
+        self._chk(self.lib.w3_export_entropy_get_profile(self.h, C.byref(p)))
+        out = {k: getattr(p.base, k) for k, _ in L.ExportProfile._fields_}
+        out.update(key_ms=p.key_ms, huff_fixed_epochs=p.huff_fixed_epochs)
+        return out
+
     def predict_blocks(self, model, data, block_size):
         spec = model.spec()
         a = _u8(data)
