@@ -532,8 +532,8 @@ int w3_export_counters(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in
 /* ---- the same for whole inputs of any size, on the device (csrc/w3_export.h) ---------------------------------------
  * For ONE adaptive W3_NODE_ORDERN leaf with history == W3_HIST_NONE, not frozen, bits <= 28, the context of a step is a pure function of
  * the input and a Counter depends on the order of its updates only where it halves.  The input goes through in epochs: per epoch every
- * context's visits are counted by bit value (k_ctx_count), added to the table where no count can have reached 65535 (k_ctx_apply), and the
- * few contexts in which one did are replayed exactly by a wavefront each (k_ctx_replay).  The result equals w3_export_counters bit for
+ * context's visits are counted by bit value (k_exp_count), added to the table where no count can have reached 65535 (k_ctx_apply), and the
+ * few contexts in which one did are replayed exactly by a wavefront each (k_exp_replay).  The result equals w3_export_counters bit for
  * bit.  Every other spec is W3_E_UNSUPPORTED (leaves with an entropy history go through w3_export_entropy_device / _staged below or the
  * one-lane call above, w3_last_error says so).
  *   w3_export_counters_device   d_counters = uint32[2^bits] in DEVICE memory, every entry written.  n < 2^32 - 4096 per call, n == 0 gives

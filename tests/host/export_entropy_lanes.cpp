@@ -23,19 +23,9 @@
 // The AC key stage here takes ACHistory::hash of a window from the oracle: ac_history_hash_steps (w3_device.h) is written over wavefront
 // ballots and device intrinsics and is covered on the GPU only.  The window (across epochs, pieces and the carry), the key's composition
 // and everything behind the keys are the header's own code.
-#include <algorithm>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <map>
 #include <memory>
-#include <set>
 #include <sstream>
-#include <string>
-#include <sys/mman.h>
-#include <unistd.h>
-#include <vector>
 
 extern "C" {
 #include "w3_oracle.h"
@@ -43,21 +33,10 @@ extern "C" {
 
 #define W3_HD static inline
 #include "../../weath3rb0i_amd/csrc/w3_export_entropy.h"
+#define LANES_EXPORT_FORM   // (Form: the device form of a piece over w3_export.h, included above)
+#include "lanes_common.h"
 
 // ---- the yardstick: OrderNEntropy + Counter, literally ----------------------------------------------------------------------------------
-struct Counter {
-    uint16_t data[2] = {0, 0};
-    bool update(uint8_t bit) {   // counter.rs:20-26; true if it halved
-        data[bit] += 1;
-        if (data[bit] == 0xFFFF) {
-            data[0] = (uint16_t)((data[0] >> 1) + (data[0] & 1));
-            data[1] = (uint16_t)((data[1] >> 1) + (data[1] & 1));
-            return true;
-        }
-        return false;
-    }
-};
-struct Halving { uint64_t byte; uint32_t ctx; };
 struct Literal {
     std::vector<Counter> stats;
     std::vector<uint32_t> keys;   // ctx | bit << 31 of every step: what the key stage has to produce
@@ -93,33 +72,30 @@ struct AlignedKeys {   // a heap block of exactly `steps` keys, 16-byte aligned:
     ~AlignedKeys() { free(p); }
     AlignedKeys(const AlignedKeys &) = delete;
 };
-struct Form {
-    w3::ExpModel m;
+// the key stage of one epoch as the kernels run it, compared with the literal run's keys: what KeyedForm::piece hands to Form::piece
+struct KeyedForm : Form {
     w3o_history hist;   // kind, max_bits, model, huff: the leaf's parameters
-    std::vector<uint64_t> D;
-    std::vector<uint32_t> S;
-    uint64_t replays = 0, halvings = 0, epochs = 0, fixed = 0;
-    std::string bad;
-    Form(uint32_t bits, uint32_t align, const w3o_history &h) : m{bits, align}, hist(h), D((size_t)1 << bits), S((size_t)1 << bits) {}
+    uint64_t fixed = 0;
+    KeyedForm(uint32_t bits, uint32_t align, const w3o_history &h) : Form(bits, align), hist(h) {}
     uint32_t ac_hash(uint64_t window, uint32_t j) {   // ACHistory::hash of the oracle with this history
         w3o_history h = hist;
         h.bits = window; h.pos = j;
         return w3o_history_hash(&h);
     }
-    // one piece, as a device call runs it: per epoch the key stage, k_expk_count (here: 7 waves striding over the rows), k_ctx_apply, k_expk_replay
-    void piece(const w3::ExpKeyPiece &pc, uint64_t E, const std::vector<uint32_t> &want_keys) {
-        std::vector<uint32_t> touched, list;
+    void piece(const w3::ExpPiece &pc, uint64_t E, const std::vector<uint32_t> &want_keys) {
         bool chained = false;   // W3_EXPK_HS_* of the device, zeroed per piece
         uint32_t chain_cb = 0;
-        for (uint64_t e0 = 0; e0 < pc.n; e0 += E) {
-            const uint64_t len = std::min<uint64_t>(E, pc.n - e0), steps = len * 8;
-            AlignedKeys K(steps);
+        std::unique_ptr<AlignedKeys> keys;   // (the epoch's: freed when the next epoch's are made)
+        Form::piece(pc, E, [&](uint64_t e0, uint64_t len) {
+            const uint64_t steps = len * 8;
+            keys.reset(new AlignedKeys(steps));
+            uint32_t *K = keys->p;
             if (hist.kind == W3O_HIST_AC) {   // k_expk_ackeys
                 for (uint64_t g = 0; g < steps; g++) {
                     const uint64_t i = e0 + (g >> 3);
                     const uint32_t j = (uint32_t)g & 7u, c0 = pc.p[i];
-                    const uint64_t h64 = (w3::expk_window(pc, i) << j) | (uint64_t)(c0 >> (8u - j));
-                    K.p[g] = w3::expk_key(m, ac_hash(h64, j), (pc.abs0 + i) * 8u + j, (c0 >> (7u - j)) & 1u);
+                    const uint64_t h64 = (w3::exp_window(pc, i) << j) | (uint64_t)(c0 >> (8u - j));
+                    K[g] = w3::expk_key(m, ac_hash(h64, j), (pc.abs0 + i) * 8u + j, (c0 >> (7u - j)) & 1u);
                 }
             } else {   // k_expk_huffkeys, k_expk_huff_fix
                 const w3o_huff_tables &t = hist.huff;
@@ -127,101 +103,29 @@ struct Form {
                 for (uint64_t g = 0; g < len; g++) {
                     uint32_t k[8];
                     if (!w3::expk_huff_byte(pc, e0, g, m, t.code, t.len, t.rem_code, t.rem_len, k)) flagged = true;
-                    memcpy(K.p + 8 * g, k, 32);
+                    memcpy(K + 8 * g, k, 32);
                 }
                 if (flagged) {
                     const uint32_t seed = w3::expk_huff_epoch_seed(pc, e0, chained, chain_cb, t.code, t.len);
-                    chain_cb = w3::expk_huff_redo(pc, e0, len, m, seed, t.code, t.len, t.rem_code, t.rem_len, K.p);
+                    chain_cb = w3::expk_huff_redo(pc, e0, len, m, seed, t.code, t.len, t.rem_code, t.rem_len, K);
                     fixed++;
                 }
                 chained = flagged;
             }
-            if (bad.empty() && memcmp(K.p, want_keys.data() + (pc.abs0 + e0) * 8, (size_t)steps * 4)) {
+            const uint32_t *want = want_keys.data() + (pc.abs0 + e0) * 8;
+            if (bad.empty() && memcmp(K, want, (size_t)steps * 4)) {
                 uint64_t g = 0;
-                while (K.p[g] == want_keys[(pc.abs0 + e0) * 8 + g]) g++;
+                while (K[g] == want[g]) g++;
                 char buf[160];
-                snprintf(buf, sizeof buf, "key of stream step %llu: %08x, the literal run has %08x", (unsigned long long)((pc.abs0 + e0) * 8 + g), K.p[g],
-                         want_keys[(pc.abs0 + e0) * 8 + g]);
+                snprintf(buf, sizeof buf, "key of stream step %llu: %08x, the literal run has %08x", (unsigned long long)((pc.abs0 + e0) * 8 + g), K[g], want[g]);
                 bad = buf;
             }
-            const uint64_t nw = 7;
-            touched.clear();
-            for (uint64_t gw = 0; gw < nw; gw++)
-                for (uint32_t lane = 0; lane < 64; lane++)
-                    w3::expk_count_wave_lane(K.p, steps, lane, gw, nw, [&](uint32_t ctx, uint32_t bit) {
-                        if (!D[ctx]) touched.push_back(ctx);
-                        D[ctx] += bit ? 1ull << 32 : 1ull;
-                    });
-            list.clear();
-            for (uint32_t c : touched) {   // (k_ctx_apply visits every context and skips D == 0)
-                if (w3::exp_apply(D[c], S[c])) list.push_back(c);
-                D[c] = 0;
-            }
-            if (list.size() > w3::exp_list_cap(m.bits, pc.abs0 + e0 + len)) bad = "the replay list exceeds its bound";
-            w3::WaveHost wv;
-            for (uint32_t c : list) {
-                const uint32_t h = w3::expk_replay(wv, K.p, steps, c, S[c]);
-                if (!h) bad = "a listed context without a halving";
-                halvings += h;
-            }
-            replays += list.size();
-            epochs++;
-        }
+            return w3::ExpKeySrc{K, steps};
+        });
     }
 };
 
-struct Heap {   // a heap block that ENDS with the data, a bytes past a 16-byte boundary, other values before it
-    uint8_t *raw = nullptr, *p = nullptr;
-    Heap(size_t n, unsigned a) {
-        if (posix_memalign((void **)&raw, 16, a + n ? a + n : 1)) abort();
-        memset(raw, 0xA5, a);
-        p = raw + a;
-    }
-    ~Heap() { free(raw); }
-    Heap(const Heap &) = delete;
-};
-struct Guarded {   // [p, p + n) starting at a page start behind an inaccessible page (end = false) or ending at a page end before one
-    uint8_t *m = nullptr, *p = nullptr;
-    size_t total = 0;
-    Guarded(size_t n, bool end) {
-        const size_t page = (size_t)sysconf(_SC_PAGESIZE), pages = (n + page - 1) / page + 1;
-        total = (pages + 2) * page;
-        m = (uint8_t *)mmap(nullptr, total, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-        if (m == MAP_FAILED) { perror("mmap"); exit(2); }
-        memset(m + page, 0xA5, pages * page);
-        if (mprotect(m, page, PROT_NONE) || mprotect(m + (pages + 1) * page, page, PROT_NONE)) { perror("mprotect"); exit(2); }
-        p = end ? m + (pages + 1) * page - n : m + page;
-    }
-    ~Guarded() { munmap(m, total); }
-    Guarded(const Guarded &) = delete;
-};
-
-static std::vector<uint8_t> blob;
-
-static bool make_input(const std::string &spec, std::vector<uint8_t> &out) {
-    unsigned long long a = 0, b = 0, c = 0, d = 0;
-    if (sscanf(spec.c_str(), "blob:%llu:%llu", &a, &b) == 2) {
-        if (a + b > blob.size()) return false;
-        out.assign(blob.begin() + (long)a, blob.begin() + (long)(a + b));
-        return true;
-    }
-    if (sscanf(spec.c_str(), "ffz:%llu:%llu", &a, &b) == 2) {
-        out.assign((size_t)(a + b), 0);
-        std::fill(out.begin(), out.begin() + (long)a, 0xFF);
-        return true;
-    }
-    if (sscanf(spec.c_str(), "zrun:%llu:%llu:%llu:%llu", &a, &b, &c, &d) == 4) {
-        if (a + d > blob.size()) return false;
-        out.assign(blob.begin(), blob.begin() + (long)a);
-        out.insert(out.end(), (size_t)b, 0);
-        out.insert(out.end(), (size_t)c, 0xFF);
-        out.insert(out.end(), blob.begin() + (long)a, blob.begin() + (long)(a + d));
-        return true;
-    }
-    return false;
-}
-
-static bool make_history(const std::string &spec, const std::vector<uint8_t> &data, w3o_history &h) {
+static bool make_history(const std::vector<uint8_t> &blob, const std::string &spec, const std::vector<uint8_t> &data, w3o_history &h) {
     unsigned a = 0, b = 0;
     unsigned long long len = 0;
     char name[16] = {0};
@@ -242,47 +146,10 @@ static bool make_history(const std::string &spec, const std::vector<uint8_t> &da
     return false;
 }
 
-static uint64_t fnv(uint64_t h, uint64_t v) { return (h ^ v) * 1099511628211ull; }
-
-// the pieces [lo, hi) the cut list makes of n bytes
-static std::vector<std::pair<uint64_t, uint64_t>> pieces_of(uint64_t n, const std::vector<uint64_t> &cuts) {
-    std::vector<std::pair<uint64_t, uint64_t>> out;
-    uint64_t lo = 0;
-    for (size_t k = 0; k <= cuts.size(); k++) {
-        const uint64_t hi = k < cuts.size() ? std::min(cuts[k], n) : n;
-        if (hi < lo) continue;
-        if (hi > lo || (n == 0 && k == cuts.size())) out.push_back({lo, hi});
-        lo = hi;
-    }
-    return out;
-}
-
-// (context, epoch) pairs in which the literal run halves, for pieces cut as above with epochs of E bytes from every piece's start
-static uint64_t literal_pairs(const std::vector<Halving> &where, const std::vector<std::pair<uint64_t, uint64_t>> &pieces, uint64_t E) {
-    std::set<std::pair<uint64_t, uint32_t>> pairs;
-    for (const Halving &h : where) {
-        uint64_t id = 0;
-        for (const auto &pc : pieces) {
-            if (h.byte >= pc.first && h.byte < pc.second) { id += (h.byte - pc.first) / E; break; }
-            id += (pc.second - pc.first + E - 1) / E;
-        }
-        pairs.insert({id, h.ctx});
-    }
-    return pairs.size();
-}
-
 int main(int argc, char **argv) {
     if (argc != 3) { fprintf(stderr, "usage: export_entropy_lanes <blob> <cases>\n"); return 2; }
-    {
-        FILE *f = fopen(argv[1], "rb");
-        if (!f) { perror(argv[1]); return 2; }
-        fseek(f, 0, SEEK_END);
-        const long n = ftell(f);
-        fseek(f, 0, SEEK_SET);
-        blob.resize((size_t)n);
-        if (n && fread(blob.data(), 1, (size_t)n, f) != (size_t)n) { perror("read"); return 2; }
-        fclose(f);
-    }
+    std::vector<uint8_t> blob;
+    if (!load_blob(argv[1], blob)) return 2;
     FILE *cf = fopen(argv[2], "r");
     if (!cf) { perror(argv[2]); return 2; }
     std::map<std::string, std::shared_ptr<Literal>> literals;   // by input, history and shape: the cases of one file share them
@@ -295,7 +162,7 @@ int main(int argc, char **argv) {
         in >> kind >> ispec >> hspec >> bits >> align >> E;
         std::vector<uint8_t> data;
         w3o_history hist;
-        if (!in || !make_input(ispec, data) || !make_history(hspec, data, hist) || bits < 1 || bits > 24 || align > 7 || align > bits ||
+        if (!in || !make_input(blob, ispec, data) || !make_history(blob, hspec, data, hist) || bits < 1 || bits > 24 || align > 7 || align > bits ||
             (kind != "exp" && kind != "lit")) { fprintf(stderr, "bad case: %s", line); return 2; }
         const uint64_t n = data.size();
         if (E == 0) E = std::max<uint64_t>((n + 1023) / 1024 * 1024, 1024);
@@ -311,7 +178,7 @@ int main(int argc, char **argv) {
         std::string hb;
         for (uint64_t b : hbytes) hb += (hb.empty() ? "" : ",") + std::to_string(b);
         if (hb.empty()) hb = "-";
-        uint64_t nonzero = 0, fold = 1469598103934665603ull;
+        uint64_t nonzero = 0, fold = FNV0;
         for (uint32_t c = 0; c < lit.stats.size(); c++)
             if (lit.packed(c)) { nonzero++; fold = fnv(fnv(fold, c), lit.packed(c)); }
         const unsigned len0 = hist.kind == W3O_HIST_HUFF ? hist.huff.len[0] : 99, len255 = hist.kind == W3O_HIST_HUFF ? hist.huff.len[255] : 99;
@@ -339,41 +206,19 @@ int main(int argc, char **argv) {
             unsigned long long x;
             while (in >> x) cuts.push_back(x);
             const auto pieces = pieces_of(n, cuts);
-            Form f(bits, align, hist);
-            uint64_t carry8 = 0, prev = 0;
+            KeyedForm f(bits, align, hist);
+            uint64_t carry = 0, prev = 0;
             uint32_t seed = 0;
             for (const auto &pr : pieces) {
-                const uint64_t len = pr.second - pr.first;
-                w3::ExpKeyPiece pc;
                 if (hist.kind == W3O_HIST_HUFF && pr.first) seed = w3::expk_huff_piece_seed(data.data(), pr.first, prev, seed, hist.huff.code, hist.huff.len);
                 prev = pr.first;
-                pc.n = len; pc.abs0 = pr.first; pc.carry8 = carry8; pc.seed = seed;
-                if (a <= 15) {
-                    Heap h((size_t)len, a);
-                    if (len) memcpy(h.p, data.data() + pr.first, (size_t)len);
-                    pc.p = h.p;
+                in_buffer(data.data() + pr.first, (size_t)(pr.second - pr.first), a, [&](const uint8_t *p) {
+                    const w3::ExpPiece pc = {p, pr.second - pr.first, pr.first, carry, seed};
                     f.piece(pc, E, lit.keys);
-                    carry8 = w3::expk_window(pc, len);
-                } else {
-                    Guarded g((size_t)len, a == 17);
-                    if (len) memcpy(g.p, data.data() + pr.first, (size_t)len);
-                    pc.p = g.p;
-                    f.piece(pc, E, lit.keys);
-                    carry8 = w3::expk_window(pc, len);
-                }
+                    carry = w3::exp_window(pc, pc.n);
+                });
             }
-            const uint64_t pairs = literal_pairs(lit.where, pieces, E);
-            uint64_t diff = 0, first = 0;
-            for (uint32_t c = 0; c < f.S.size(); c++) {
-                const uint32_t want = lit.packed(c);
-                if (f.S[c] != want && !diff++) first = c;
-                if (f.D[c]) f.bad = "D is not left zeroed";
-            }
-            if (!f.bad.empty()) r = "BAD " + f.bad;
-            else if (diff) { snprintf(buf, sizeof buf, "BAD %llu contexts differ, first %llu: %08x != %08x", (unsigned long long)diff, (unsigned long long)first, f.S[first], lit.packed((uint32_t)first)); r = buf; }
-            else if (f.replays != pairs) { snprintf(buf, sizeof buf, "BAD replays %llu, the literal run halves in %llu (context, epoch) pairs", (unsigned long long)f.replays, (unsigned long long)pairs); r = buf; }
-            else if (f.halvings != lit.where.size()) { snprintf(buf, sizeof buf, "BAD halvings %llu != %llu", (unsigned long long)f.halvings, (unsigned long long)lit.where.size()); r = buf; }
-            else if (f.replays > 8 * n / 32767) r = "BAD more replays than 8 n / 32767";
+            r = f.verdict([&](uint32_t c) { return lit.packed(c); }, literal_pairs(lit.where, pieces, E), lit.where.size(), n);
             replays = f.replays; epochs = f.epochs; fixed = f.fixed;
         }
         if (r.empty()) {

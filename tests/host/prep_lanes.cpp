@@ -26,6 +26,7 @@
 
 #define W3_HD static inline
 #include "../../weath3rb0i_amd/csrc/w3_prep.h"
+#include "lanes_common.h"   // Heap: a heap block that ENDS with the data, a bytes past a 16-byte boundary
 
 struct State {
     uint32_t c0[8] = {0}, c1[8] = {0}, h[8] = {0};
@@ -148,16 +149,6 @@ static std::vector<std::vector<size_t>> cuts_around(uint64_t h, uint32_t skew) {
     if (e0 >= skew) c.push_back({(size_t)(e0 - skew), (size_t)h + 1});
     return c;
 }
-
-struct Heap {   // a heap block that ENDS with the data, a bytes past a 16-byte boundary
-    uint8_t *raw = nullptr, *p = nullptr;
-    Heap(size_t n, unsigned a) {
-        if (posix_memalign((void **)&raw, 16, a + n ? a + n : 1)) abort();
-        memset(raw, 0xA5, a);
-        p = raw + a;
-    }
-    ~Heap() { free(raw); }
-};
 
 int main(int argc, char **argv) {
     if (argc != 3) { fprintf(stderr, "usage: prep_lanes <blob> <cases>\n"); return 2; }

@@ -12,7 +12,7 @@ import subprocess
 import pytest
 
 from weath3rb0i_amd import _lib as L
-from tests.synth import lcg_text, markov_text
+from tests import export_harness as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "host", "export_lanes.cpp")
@@ -31,24 +31,10 @@ SHORT = (0, 1, 15, 16, 17, 1023, 1024, 1025)
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    d = tmp_path_factory.mktemp("export")
-    (d / "blob").write_bytes(markov_text(300000) + lcg_text(300000) + markov_text(70000))
-    exe = str(d / "export_lanes")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-o", exe, SRC])
-    return exe, str(d / "blob"), d
+    return H.build(tmp_path_factory, "export", SRC)
 
 
-def answers(harness, cases, name, exe=None):
-    exe0, blob_path, d = harness
-    p = d / name
-    p.write_text("\n".join(cases) + "\n")
-    r = subprocess.run([exe or exe0, blob_path, str(p)], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, (r.returncode, r.stdout[-300:], r.stderr[-800:])   # (-11: a read outside the buffer)
-    lines = r.stdout.splitlines()
-    assert len(lines) == len(cases)
-    bad = [(c, ln[:200]) for c, ln in zip(cases, lines) if not ln.startswith("ok")]
-    assert not bad, bad[:5]
-    return [{k: (v if k == "fold" else int(v)) for k, v in re.findall(r"(\w+)=(\S+)", ln)} for ln in lines]
+answers = H.answers
 
 
 def directed_cases():
@@ -126,11 +112,10 @@ def test_every_shape_and_pieces_cut_off_the_alignment_period(harness):
 @needs_gxx
 def test_the_same_under_address_and_ub_sanitizers(harness, tmp_path):
     """A stand-alone sanitizer build of the harness (every piece lives in a heap block that ends with its last byte)."""
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-    (tmp_path / "probe.cpp").write_text("int main() { return 0; }\n")
-    r = subprocess.run(["g++"] + san + ["-o", str(tmp_path / "probe"), str(tmp_path / "probe.cpp")], capture_output=True, text=True)
-    if r.returncode != 0:
-        pytest.skip("g++ cannot link the sanitizer runtime: " + r.stderr[-200:])
+    san = H.SAN
+    why = H.sanitizer_probe(tmp_path)
+    if why:
+        pytest.skip(why)
     exe = str(tmp_path / "export_san")
     subprocess.check_call(["g++", "-O1", "-g", "-std=c++17"] + san + ["-o", exe, SRC])   # (the harness itself must build)
     cases = [c for c, key, e in directed_cases() if e in (4096, 0) or key in ("A", "B1", "B2")]

@@ -14,7 +14,7 @@ import subprocess
 import pytest
 
 from weath3rb0i_amd import _lib as L
-from tests.synth import lcg_text, markov_text
+from tests import export_harness as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "host", "export_entropy_lanes.cpp")
@@ -36,25 +36,11 @@ SHORT = list(range(0, 50)) + list(range(1000, 1060))
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    d = tmp_path_factory.mktemp("export_entropy")
-    (d / "blob").write_bytes(markov_text(300000) + lcg_text(300000) + markov_text(70000))
-    obj, exe = str(d / "w3_oracle.o"), str(d / "export_entropy_lanes")
-    subprocess.check_call(["gcc", "-O2", "-std=c11", "-D_GNU_SOURCE", "-c", "-I", ORACLE, "-o", obj, os.path.join(ORACLE, "w3_oracle.c")])
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-I", ORACLE, "-o", exe, SRC, obj, "-lpthread", "-lm"])
-    return exe, str(d / "blob"), d, obj
+    return H.build(tmp_path_factory, "export_entropy", SRC, oracle=ORACLE)
 
 
 def answers(harness, cases, name, exe=None):
-    exe0, blob_path, d = harness[:3]
-    p = d / name
-    p.write_text("\n".join(cases) + "\n")
-    r = subprocess.run([exe or exe0, blob_path, str(p)], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, (r.returncode, r.stdout[-300:], r.stderr[-800:])   # (-11: a read outside the buffer)
-    lines = r.stdout.splitlines()
-    assert len(lines) == len(cases)
-    bad = [(c, ln[:200]) for c, ln in zip(cases, lines) if not ln.startswith("ok")]
-    assert not bad, bad[:5]
-    return [{k: (v if k in ("fold", "hbytes") else int(v)) for k, v in re.findall(r"(\w+)=(\S+)", ln)} for ln in lines]
+    return H.answers(harness, cases, name, exe=exe, text=("fold", "hbytes"))
 
 
 def directed_cases():
@@ -150,11 +136,10 @@ def test_short_lengths_every_skew_between_inaccessible_pages(harness):
 @needs_cc
 def test_the_same_under_address_and_ub_sanitizers(harness, tmp_path):
     """A stand-alone sanitizer build of the harness (every piece and every epoch's keys live in heap blocks that end with their last byte)."""
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-    (tmp_path / "probe.cpp").write_text("int main() { return 0; }\n")
-    r = subprocess.run(["g++"] + san + ["-o", str(tmp_path / "probe"), str(tmp_path / "probe.cpp")], capture_output=True, text=True)
-    if r.returncode != 0:
-        pytest.skip("g++ cannot link the sanitizer runtime: " + r.stderr[-200:])
+    san = H.SAN
+    why = H.sanitizer_probe(tmp_path)
+    if why:
+        pytest.skip(why)
     exe = str(tmp_path / "export_entropy_san")
     subprocess.check_call(["g++", "-O1", "-g", "-std=c++17"] + san + ["-I", ORACLE, "-o", exe, SRC, harness[3], "-lpthread", "-lm"])
     cases = [c for c, key, e in directed_cases() if key in ("Z0", "Z2", "H62") and e in (4096, 0)]

@@ -132,7 +132,7 @@ def test_the_harness_traps_a_chunk_loaded_behind_the_end(harness, tmp_path):
     h = open(SRC, encoding="utf-8").read().replace('"../../weath3rb0i_amd/csrc/w3_prep.h"', '"%s"' % str(tmp_path / "w3_prep.h"))
     (tmp_path / "prep_bad.cpp").write_text(h, encoding="utf-8")
     exe = str(tmp_path / "prep_bad")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-o", exe, str(tmp_path / "prep_bad.cpp")])
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", os.path.dirname(SRC), "-o", exe, str(tmp_path / "prep_bad.cpp")])   # (-I: lanes_common.h)
     for case in ("histg 0 1000 1", "statg 0 1000 1"):
         p = start(harness, [case], "guard_bad", exe=exe)
         p.communicate(timeout=60)

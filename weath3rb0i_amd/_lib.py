@@ -198,11 +198,10 @@ def load():
     lib.w3_huff_code_from_counts.argtypes = [vp, u8, hc]
     lib.w3_huff_tables_from_counts.argtypes = [vp, u8, u8, C.POINTER(HuffTable)]
     lib.w3_table_prep_profile.argtypes = [vp, vp, sz, C.c_uint32, C.POINTER(PrepProfile)]
-    lib.w3_export_counters_device.argtypes = [vp, C.POINTER(ModelSpec), vp, sz, vp, vp]
-    lib.w3_export_counters_staged.argtypes = [vp, C.POINTER(ModelSpec), vp, sz, vp]
+    for which in ("counters", "entropy"):   # one signature per form
+        getattr(lib, "w3_export_%s_device" % which).argtypes = [vp, C.POINTER(ModelSpec), vp, sz, vp, vp]
+        getattr(lib, "w3_export_%s_staged" % which).argtypes = [vp, C.POINTER(ModelSpec), vp, sz, vp]
     lib.w3_export_get_profile.argtypes = [vp, C.POINTER(ExportProfile)]
-    lib.w3_export_entropy_device.argtypes = [vp, C.POINTER(ModelSpec), vp, sz, vp, vp]
-    lib.w3_export_entropy_staged.argtypes = [vp, C.POINTER(ModelSpec), vp, sz, vp]
     lib.w3_export_entropy_get_profile.argtypes = [vp, C.POINTER(ExportEntropyProfile)]
     lib.w3_rccl_library.argtypes = [C.c_char_p]
     lib.w3_rccl_status.argtypes = [C.c_char_p, sz]

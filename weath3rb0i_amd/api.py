@@ -317,10 +317,8 @@ class Context:
         self._chk(self.lib.w3_export_counters(self.h, C.byref(spec), a.ctypes.data_as(C.c_void_p), len(a), t.ctypes.data_as(C.c_void_p)))
         return (t & 0xFFFF).astype(np.uint16), (t >> 16).astype(np.uint16)
 
-    def export_counters_device(self, model, d_in, d_counters=None, stream=None):
-        """w3_export_counters_device: the same table for ONE adaptive OrderN leaf without entropy history, computed in parallel over the
-        whole input (csrc/w3_export.h).  d_in: a torch.uint8 CUDA tensor (contiguous).  -> a torch.int32 CUDA tensor of 2^bits packed
-        counters n0 | n1 << 16 (d_counters when given: every entry is overwritten)"""
+    def _export_device(self, fn, model, d_in, d_counters, stream):
+        """the device form of both exports: fn = the library's w3_export_counters_device or w3_export_entropy_device"""
         import torch
         if d_in.dtype != torch.uint8 or not d_in.is_cuda or not d_in.is_contiguous():
             raise W3Error(L.W3_E_INVALID, "d_in: a contiguous torch.uint8 CUDA tensor")
@@ -334,19 +332,28 @@ class Context:
               or d_counters.device != d_in.device):
             raise W3Error(L.W3_E_INVALID, "d_counters: a contiguous torch.int32 tensor of 2^bits entries on d_in's device")
         st = C.c_void_p(stream) if stream else None
-        self._chk(self.lib.w3_export_counters_device(self.h, C.byref(spec), C.c_void_p(d_in.data_ptr()), d_in.numel(),
-                                                     C.c_void_p(d_counters.data_ptr()), st))
+        self._chk(fn(self.h, C.byref(spec), C.c_void_p(d_in.data_ptr()), d_in.numel(), C.c_void_p(d_counters.data_ptr()), st))
         return d_counters
 
-    def export_counters_staged(self, model, data):
-        """w3_export_counters_staged: the same from host `data` of any length, staged through the device in pieces.
-        -> (n0: np.uint16[2^bits], n1: np.uint16[2^bits]), the shape export_counters returns"""
+    def _export_staged(self, fn, model, data):
+        """the staged form of both exports: fn = the library's w3_export_counters_staged or w3_export_entropy_staged"""
         spec = model.spec()
         a = _u8(data)
         refused = spec.n_nodes != 1 or spec.nodes[0].bits > 28
         t = np.zeros(1 if refused else 1 << spec.nodes[0].bits, dtype=np.uint32)
-        self._chk(self.lib.w3_export_counters_staged(self.h, C.byref(spec), a.ctypes.data_as(C.c_void_p), len(a), t.ctypes.data_as(C.c_void_p)))
+        self._chk(fn(self.h, C.byref(spec), a.ctypes.data_as(C.c_void_p), len(a), t.ctypes.data_as(C.c_void_p)))
         return (t & 0xFFFF).astype(np.uint16), (t >> 16).astype(np.uint16)
+
+    def export_counters_device(self, model, d_in, d_counters=None, stream=None):
+        """w3_export_counters_device: the same table for ONE adaptive OrderN leaf without entropy history, computed in parallel over the
+        whole input (csrc/w3_export.h).  d_in: a torch.uint8 CUDA tensor (contiguous).  -> a torch.int32 CUDA tensor of 2^bits packed
+        counters n0 | n1 << 16 (d_counters when given: every entry is overwritten)"""
+        return self._export_device(self.lib.w3_export_counters_device, model, d_in, d_counters, stream)
+
+    def export_counters_staged(self, model, data):
+        """w3_export_counters_staged: the same from host `data` of any length, staged through the device in pieces.
+        -> (n0: np.uint16[2^bits], n1: np.uint16[2^bits]), the shape export_counters returns"""
+        return self._export_staged(self.lib.w3_export_counters_staged, model, data)
 
     def export_profile(self):
         """w3_export_get_profile: what the last export_counters_device / _staged call did (the times under set_timing())"""
@@ -359,32 +366,12 @@ class Context:
         RawHistory, ACHistory or HuffHistory (init_model()'s leaf) — with a key stage per epoch (csrc/w3_export_entropy.h).  d_in: a
         torch.uint8 CUDA tensor (contiguous).  -> a torch.int32 CUDA tensor of 2^bits packed counters n0 | n1 << 16 (d_counters when
         given: every entry is overwritten)"""
-        import torch
-        if d_in.dtype != torch.uint8 or not d_in.is_cuda or not d_in.is_contiguous():
-            raise W3Error(L.W3_E_INVALID, "d_in: a contiguous torch.uint8 CUDA tensor")
-        spec = model.spec()
-        entries = 1 << spec.nodes[0].bits
-        if d_counters is None:
-            if spec.n_nodes != 1 or spec.nodes[0].bits > 28:   # (refused below, before the tensor is touched: do not allocate 2^bits for it)
-                entries = 1
-            d_counters = torch.empty(entries, dtype=torch.int32, device=d_in.device)
-        elif (d_counters.dtype != torch.int32 or d_counters.numel() != entries or not d_counters.is_contiguous()
-              or d_counters.device != d_in.device):
-            raise W3Error(L.W3_E_INVALID, "d_counters: a contiguous torch.int32 tensor of 2^bits entries on d_in's device")
-        st = C.c_void_p(stream) if stream else None
-        self._chk(self.lib.w3_export_entropy_device(self.h, C.byref(spec), C.c_void_p(d_in.data_ptr()), d_in.numel(),
-                                                    C.c_void_p(d_counters.data_ptr()), st))
-        return d_counters
+        return self._export_device(self.lib.w3_export_entropy_device, model, d_in, d_counters, stream)
 
     def export_entropy_staged(self, model, data):
         """w3_export_entropy_staged: the same from host `data` of any length, staged through the device in pieces.
         -> (n0: np.uint16[2^bits], n1: np.uint16[2^bits]), the shape export_counters returns"""
-        spec = model.spec()
-        a = _u8(data)
-        refused = spec.n_nodes != 1 or spec.nodes[0].bits > 28
-        t = np.zeros(1 if refused else 1 << spec.nodes[0].bits, dtype=np.uint32)
-        self._chk(self.lib.w3_export_entropy_staged(self.h, C.byref(spec), a.ctypes.data_as(C.c_void_p), len(a), t.ctypes.data_as(C.c_void_p)))
-        return (t & 0xFFFF).astype(np.uint16), (t >> 16).astype(np.uint16)
+        return self._export_staged(self.lib.w3_export_entropy_staged, model, data)
 
     def export_entropy_profile(self):
         """w3_export_entropy_get_profile: what the last export_entropy_device / _staged call did (the times under set_timing()):

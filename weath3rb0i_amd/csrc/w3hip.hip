@@ -123,12 +123,9 @@ struct w3_ctx {
     DevBuf exp_d, exp_s, exp_list, exp_stats;
     size_t exp_d_zero = 0;
     uint32_t export_epoch = 0;                      // W3_OPT_EXPORT_EPOCH (0 = W3_EXP_EPOCH_DEFAULT)
-    w3_export_profile exp_prof{};
-    // ... for OrderNEntropy leaves (w3_export_entropy.h): the keys of one epoch, the Huffman key stage's state words; what the key stage
-    // adds to the profile
+    w3_export_entropy_profile exp_prof{};           // (w3_export_get_profile returns its base)
+    // ... for OrderNEntropy leaves (w3_export_entropy.h): the keys of one epoch, the Huffman key stage's state words
     DevBuf exp_k, exp_hs;
-    float exp_key_ms = 0.f;
-    uint64_t exp_huff_fixed = 0;
     uint64_t crc_res[2] = {~0ull, 0};
     // What a job takes from the context when a call is prepared (hand_options): the two-phase options (w3_ctx_set_option), the
     // context-mixing look-up tables in cm_luts, and the lane-order self-test's verdict (-1 not run yet under this variant, 1 = returning
@@ -3420,21 +3417,28 @@ extern "C" int w3_export_counters(w3_ctx *ctx, const w3_model_spec *spec, const 
 }
 
 // ---------------------------------------------------------------------------
-// The same on the device for whole inputs of any size (w3_export.h): count, apply and replay per epoch.
+// The same on the device for whole inputs of any size (w3_export.h, w3_export_entropy.h): ONE adaptive leaf; count, apply and replay per
+// epoch, for ACHistory and HuffHistory behind a key stage per epoch.  w3_export_counters_device / _staged admit OrderN leaves without
+// entropy history only, w3_export_entropy_device / _staged every history; behind the argument check they are one path.
 // ---------------------------------------------------------------------------
-static int export_args(w3_ctx *ctx, const w3_model_spec *spec, const void *in, size_t n, const void *out, bool one_device, ExpModel &m) {
+static int export_args(w3_ctx *ctx, const w3_model_spec *spec, const void *in, size_t n, const void *out, bool one_device, bool admits_entropy, ParsedSpec &ps,
+                       ExpModel &m) {
     int rc = check_args(ctx, n, W3_PREP_NOMINAL_BLOCK, one_device);
     if (rc) return rc;
     if ((rc = jobs_idle(ctx))) return rc;   // (the workspace is the context's)
-    ParsedSpec ps;
     if ((rc = parse_spec(spec, ps))) return rc;
-    if (ps.n_leaves != 1 || ps.n_apm || ps.has_slot || ps.leaf[0].kind != W3_NODE_ORDERN || ps.leaf[0].frozen || ps.leaf[0].history != W3_HIST_NONE) {
-        ctx->err = "the parallel export takes ONE adaptive OrderN leaf without entropy history: w3_export_counters (one lane) or w3_export_entropy_device / _staged (in parallel) are the routes for leaves with an entropy history";
+    if (ps.n_leaves != 1 || ps.n_apm || ps.has_slot || ps.leaf[0].kind != W3_NODE_ORDERN || ps.leaf[0].frozen ||
+        (admits_entropy ? ps.leaf[0].history > W3_HIST_HUFF : ps.leaf[0].history != W3_HIST_NONE)) {
+        ctx->err = admits_entropy
+                       ? "w3_export_entropy_device / _staged take ONE adaptive OrderN or OrderNEntropy leaf (RawHistory, ACHistory, HuffHistory)"
+                       : "the parallel export takes ONE adaptive OrderN leaf without entropy history: w3_export_counters (one lane) or w3_export_entropy_device / _staged (in parallel) are the routes for leaves with an entropy history";
         return W3_E_UNSUPPORTED;
     }
     if (ps.leaf[0].bits > W3_EXP_MAX_BITS) { ctx->err = "tables above 2^28 counters are not exported"; return W3_E_UNSUPPORTED; }
     if (!out || (!in && n)) return W3_E_INVALID;
     m.bits = ps.leaf[0].bits; m.align = ps.leaf[0].align;
+    if (admits_entropy) ctx->exp_prof = w3_export_entropy_profile();
+    else ctx->exp_prof.base = w3_export_profile();   // (a counters call leaves what only an entropy call reports)
     return W3_OK;
 }
 
@@ -3453,30 +3457,89 @@ static int export_ensure(w3_ctx *ctx, hipStream_t s, const ExpModel &m, uint64_t
     return W3_OK;
 }
 
-// What a leaf with an entropy history adds to a piece (w3_export_entropy.h): the key stage's arguments.  kp is the piece again with the
-// wider carry and the Huffman seed.
+// What a leaf with an entropy history adds (w3_export_entropy.h): the key stage's arguments
 struct ExpKeyed {
     int history;                // W3_HIST_AC or W3_HIST_HUFF
-    ExpKeyPiece kp;
     uint32_t max_bits; uint16_t table[8]; const uint4 *lut;   // ACHistory
     const w3_huff_table *tb;                                  // HuffHistory (on the device)
+    const w3_huff_table *host_tb;                             // ... and the caller's (the staged form's seed chain)
 };
 static uint64_t export_epoch_bytes(const w3_ctx *ctx, bool keyed) {
     if (!keyed) return ctx->export_epoch ? ctx->export_epoch : W3_EXP_EPOCH_DEFAULT;
     return ctx->export_epoch ? std::min<uint64_t>(ctx->export_epoch, W3_EXPK_EPOCH_MAX) : W3_EXPK_EPOCH_DEFAULT;
 }
 
-// One piece that lies on the device through its epochs, S = the table before it and behind it; synchronises s.  `upto`: the stream's
-// bytes through this piece's end (the list's bound).  Adds to ctx->exp_prof.  kd: the keyed form (a key stage per epoch, count and replay
+// the key stage's workspace and tables for pieces of at most `piece` bytes; false in `keyed`: the leaf needs none (OrderN, RawHistory)
+static int export_keyed_prepare(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, size_t piece, ExpKeyed &kd, bool &keyed) {
+    const w3_node &nd = ps.leaf[0];
+    keyed = nd.history == W3_HIST_AC || nd.history == W3_HIST_HUFF;
+    if (!keyed) return W3_OK;
+    memset(&kd, 0, sizeof kd);
+    kd.history = nd.history;
+    int rc;
+    if (nd.history == W3_HIST_HUFF) {
+        if ((rc = stage_huff(ctx, s, ps))) return rc;
+        kd.tb = lane_huff(ctx, ps) + nd.reserved;
+        kd.host_tb = ps.huff + nd.reserved;
+        ENSURE(ctx, ctx->exp_hs, W3_EXPK_HS_WORDS * 4);
+    } else {
+        GenericArgs ga;
+        memset(&ga, 0, sizeof ga);
+        (void)layout_generic(ps, W3_PREP_NOMINAL_BLOCK, ga);
+        if ((rc = prepare_achash_luts(ctx, s, ga))) return rc;
+        kd.lut = ga.leaf[0].lut; kd.max_bits = nd.max_bits;
+        memcpy(kd.table, nd.table, sizeof kd.table);
+    }
+    ENSURE(ctx, ctx->exp_k, (size_t)std::min<uint64_t>(export_epoch_bytes(ctx, true), (piece + 1023) / 1024 * 1024) * 32);
+    return W3_OK;
+}
+
+// the key stage of the epoch [e0, e0 + len): K = ctx | bit << 31 per step
+static void export_launch_keys(w3_ctx *ctx, hipStream_t s, const ExpKeyed &kd, const ExpPiece &pc, uint64_t e0, uint64_t len, const ExpModel &m) {
+    uint32_t *K = (uint32_t *)ctx->exp_k.p;
+    if (kd.history == W3_HIST_AC) {
+        ExpAcArgs a;
+        memset(&a, 0, sizeof a);
+        a.pc = pc; a.e0 = e0; a.len = len; a.m = m; a.max_bits = kd.max_bits; a.lut = kd.lut; a.K = K;
+        memcpy(a.table, kd.table, sizeof a.table);
+        hipLaunchKernelGGL(k_expk_ackeys, dim3((unsigned)std::min<uint64_t>((len * 8 + 255) / 256, 1u << 20)), dim3(256), 0, s, a);
+    } else {
+        ExpHuffArgs a;
+        memset(&a, 0, sizeof a);
+        a.pc = pc; a.e0 = e0; a.len = len; a.m = m; a.tb = kd.tb; a.K = K; a.hs = (uint32_t *)ctx->exp_hs.p;
+        hipLaunchKernelGGL(k_expk_huffkeys, dim3((unsigned)std::min<uint64_t>((len + 255) / 256, 1u << 16)), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_expk_huff_fix, dim3(1), dim3(64), 0, s, a);
+    }
+}
+
+// count and replay over a source; rows_per_wg: the rows a workgroup of the count has in flight
+template <class Src>
+static void export_launch_count(w3_ctx *ctx, hipStream_t s, const Src &src, uint64_t rows_per_wg, const ExpModel &m) {
+    const uint64_t wgs = (exp_rows(src) + rows_per_wg - 1) / rows_per_wg;
+    exp_u64 *D = (exp_u64 *)ctx->exp_d.p;
+    uint32_t *stats = (uint32_t *)ctx->exp_stats.p;
+    if (m.bits <= W3_EXP_LDS_BITS)
+        hipLaunchKernelGGL((k_exp_count_lds<Src, W3_EXP_LDS_REP>), dim3((uint32_t)std::min<uint64_t>(wgs, W3_EXP_LDS_MAX_WG)), dim3(256),
+                           (size_t)(8u << m.bits) * W3_EXP_LDS_REP, s, src, m.bits, D, stats);
+    else
+        hipLaunchKernelGGL(k_exp_count<Src>, dim3((uint32_t)std::min<uint64_t>(wgs, W3_EXP_GLOBAL_MAX_WG)), dim3(256), 0, s, src, D, stats);
+}
+template <class Src>
+static void export_launch_replay(w3_ctx *ctx, hipStream_t s, const Src &src, uint32_t *S, uint32_t cap) {
+    hipLaunchKernelGGL(k_exp_replay<Src>, dim3(std::min<uint32_t>(cap, W3_EXP_REPLAY_MAX_WG)), dim3(64), 0, s, src, S, (const uint32_t *)ctx->exp_list.p, cap,
+                       (uint32_t *)ctx->exp_stats.p);
+}
+
+// One piece that lies on the device through its epochs, S = the table before it and behind it; synchronises s.  The list's bound is that
+// of the stream's bytes through this piece's end.  Adds to ctx->exp_prof.  kd: the keyed form (a key stage per epoch, count and replay
 // over the keys).
-static int export_piece(w3_ctx *ctx, hipStream_t s, const ExpPiece &pc, const ExpModel &m, uint32_t *S, const ExpKeyed *kd = nullptr) {
+static int export_piece(w3_ctx *ctx, hipStream_t s, const ExpPiece &pc, const ExpModel &m, uint32_t *S, const ExpKeyed *kd) {
     const uint64_t E = export_epoch_bytes(ctx, kd != nullptr), nctx = 1ull << m.bits;
     const size_t nst = kd ? 4 : 3;   // kernels (timed stages) per epoch
-    uint32_t *K = (uint32_t *)ctx->exp_k.p, *hs = (uint32_t *)ctx->exp_hs.p;
+    const bool huff = kd && kd->history == W3_HIST_HUFF;
     const uint64_t epochs = (pc.n + E - 1) / E;
     const uint32_t cap = (uint32_t)exp_list_cap(m.bits, pc.abs0 + pc.n);
-    exp_u64 *D = (exp_u64 *)ctx->exp_d.p;
-    uint32_t *list = (uint32_t *)ctx->exp_list.p, *stats = (uint32_t *)ctx->exp_stats.p;
+    uint32_t *stats = (uint32_t *)ctx->exp_stats.p;
     const size_t zero_had = ctx->exp_d_zero;
     ctx->exp_d_zero = 0;   // (until the piece is through: a failed call leaves D in an unknown state)
     std::vector<hipEvent_t> ev;
@@ -3491,70 +3554,49 @@ static int export_piece(w3_ctx *ctx, hipStream_t s, const ExpPiece &pc, const Ex
         HIPCHK(ctx, hipEventRecord(ev[0], s));
     }
     HIPCHK(ctx, hipMemsetAsync(stats, 0, W3_EXP_ST_WORDS * 4, s));
-    if (kd && kd->history == W3_HIST_HUFF) HIPCHK(ctx, hipMemsetAsync(hs, 0, W3_EXPK_HS_WORDS * 4, s));
+    if (huff) HIPCHK(ctx, hipMemsetAsync(ctx->exp_hs.p, 0, W3_EXPK_HS_WORDS * 4, s));
     const uint32_t apply_wg = (uint32_t)std::min<uint64_t>((nctx + 255) / 256, 8192);
-    const uint32_t replay_wg = std::min<uint32_t>(cap, W3_EXP_REPLAY_MAX_WG);
     for (uint64_t k = 0; k < epochs; k++) {
-        const uint64_t e0 = k * E, len = std::min<uint64_t>(E, pc.n - e0), rows = kd ? expk_rows(len * 8) : exp_rows(pc, e0, len);
+        const uint64_t e0 = k * E, len = std::min<uint64_t>(E, pc.n - e0);
+        const ExpRawSrc raw = {pc, e0, len, m};
+        const ExpKeySrc keys = {(const uint32_t *)ctx->exp_k.p, len * 8};
         size_t at = nst * k;   // the epoch's first event
-        if (kd) {   // the key stage, then count over the keys
-            const uint64_t steps = len * 8;
-            if (kd->history == W3_HIST_AC) {
-                ExpAcArgs a;
-                memset(&a, 0, sizeof a);
-                a.pc = kd->kp; a.e0 = e0; a.len = len; a.m = m; a.max_bits = kd->max_bits; a.lut = kd->lut; a.K = K;
-                memcpy(a.table, kd->table, sizeof a.table);
-                hipLaunchKernelGGL(k_expk_ackeys, dim3((unsigned)std::min<uint64_t>((steps + 255) / 256, 1u << 20)), dim3(256), 0, s, a);
-            } else {
-                ExpHuffArgs a;
-                memset(&a, 0, sizeof a);
-                a.pc = kd->kp; a.e0 = e0; a.len = len; a.m = m; a.tb = kd->tb; a.K = K; a.hs = hs;
-                hipLaunchKernelGGL(k_expk_huffkeys, dim3((unsigned)std::min<uint64_t>((len + 255) / 256, 1u << 16)), dim3(256), 0, s, a);
-                hipLaunchKernelGGL(k_expk_huff_fix, dim3(1), dim3(64), 0, s, a);
-            }
+        auto stage_done = [&]() -> int {
             HIPCHK(ctx, hipGetLastError());
             if (per_kernel) HIPCHK(ctx, hipEventRecord(ev[++at], s));
-            const uint64_t per_wg = 4u * W3_EXPK_COUNT_ROWS;   // rows a workgroup has in flight
-            if (m.bits <= W3_EXP_LDS_BITS) {
-                const uint32_t wg = (uint32_t)std::min<uint64_t>((rows + per_wg - 1) / per_wg, W3_EXP_LDS_MAX_WG);
-                hipLaunchKernelGGL((k_expk_count_lds<W3_EXP_LDS_REP>), dim3(wg), dim3(256), (size_t)(8u << m.bits) * W3_EXP_LDS_REP, s, (const uint32_t *)K, steps, m, D, stats);
-            } else {
-                const uint32_t wg = (uint32_t)std::min<uint64_t>((rows + per_wg - 1) / per_wg, W3_EXP_GLOBAL_MAX_WG);
-                hipLaunchKernelGGL(k_expk_count, dim3(wg), dim3(256), 0, s, (const uint32_t *)K, steps, D, stats);
-            }
-        } else if (m.bits <= W3_EXP_LDS_BITS) {
-            const uint32_t wg = (uint32_t)std::min<uint64_t>((rows + 3) / 4, W3_EXP_LDS_MAX_WG);
-            hipLaunchKernelGGL((k_ctx_count_lds<W3_EXP_LDS_REP>), dim3(wg), dim3(256), (size_t)(8u << m.bits) * W3_EXP_LDS_REP, s, pc, e0, len, m, D, stats);
+            return W3_OK;
+        };
+        int rc;
+        if (kd) {
+            export_launch_keys(ctx, s, *kd, pc, e0, len, m);
+            if ((rc = stage_done())) return rc;
+            export_launch_count(ctx, s, keys, 4u * W3_EXPK_COUNT_ROWS, m);
         } else {
-            const uint32_t wg = (uint32_t)std::min<uint64_t>((rows + 3) / 4, W3_EXP_GLOBAL_MAX_WG);
-            hipLaunchKernelGGL(k_ctx_count, dim3(wg), dim3(256), 0, s, pc, e0, len, m, D, stats);
+            export_launch_count(ctx, s, raw, 4u, m);
         }
-        HIPCHK(ctx, hipGetLastError());
-        if (per_kernel) HIPCHK(ctx, hipEventRecord(ev[++at], s));
-        hipLaunchKernelGGL(k_ctx_apply, dim3(apply_wg), dim3(256), 0, s, D, S, nctx, list, cap, stats);
-        HIPCHK(ctx, hipGetLastError());
-        if (per_kernel) HIPCHK(ctx, hipEventRecord(ev[++at], s));
-        if (kd) hipLaunchKernelGGL(k_expk_replay, dim3(replay_wg), dim3(64), 0, s, (const uint32_t *)K, len * 8, S, (const uint32_t *)list, cap, stats);
-        else hipLaunchKernelGGL(k_ctx_replay, dim3(replay_wg), dim3(64), 0, s, pc, e0, len, m, S, (const uint32_t *)list, cap, stats);
-        HIPCHK(ctx, hipGetLastError());
-        if (per_kernel) HIPCHK(ctx, hipEventRecord(ev[++at], s));
+        if ((rc = stage_done())) return rc;
+        hipLaunchKernelGGL(k_ctx_apply, dim3(apply_wg), dim3(256), 0, s, (exp_u64 *)ctx->exp_d.p, S, nctx, (uint32_t *)ctx->exp_list.p, cap, stats);
+        if ((rc = stage_done())) return rc;
+        if (kd) export_launch_replay(ctx, s, keys, S, cap);
+        else export_launch_replay(ctx, s, raw, S, cap);
+        if ((rc = stage_done())) return rc;
     }
     if (ctx->opt_timing && !per_kernel) HIPCHK(ctx, hipEventRecord(ev[1], s));
     uint32_t st[W3_EXP_ST_WORDS] = {0};
     uint32_t hst[W3_EXPK_HS_WORDS] = {0};
     HIPCHK(ctx, hipMemcpyAsync(st, stats, sizeof st, hipMemcpyDeviceToHost, s));
-    if (kd && kd->history == W3_HIST_HUFF) HIPCHK(ctx, hipMemcpyAsync(hst, hs, sizeof hst, hipMemcpyDeviceToHost, s));
+    if (huff) HIPCHK(ctx, hipMemcpyAsync(hst, ctx->exp_hs.p, sizeof hst, hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
-    ctx->exp_huff_fixed += hst[W3_EXPK_HS_FIXED];
+    ctx->exp_prof.huff_fixed_epochs += hst[W3_EXPK_HS_FIXED];
     if (st[W3_EXP_ST_OVERFLOW]) { ctx->err = "the export's replay list exceeded its bound"; return W3_E_HIP; }
-    ctx->exp_d_zero = zero_had;   // (k_ctx_apply zeroed what k_ctx_count added)
-    w3_export_profile &pr = ctx->exp_prof;
+    ctx->exp_d_zero = zero_had;   // (k_ctx_apply zeroed what the count added)
+    w3_export_profile &pr = ctx->exp_prof.base;
     pr.epochs += epochs; pr.replays += st[W3_EXP_ST_REPLAYS]; pr.halvings += st[W3_EXP_ST_HALVINGS];
     if (ctx->opt_timing) {
         float ms = 0.f;
         if (per_kernel)
             for (uint64_t k = 0; k < epochs; k++) {
-                float *into[4] = {&ctx->exp_key_ms, &pr.count_ms, &pr.apply_ms, &pr.replay_ms};
+                float *into[4] = {&ctx->exp_prof.key_ms, &pr.count_ms, &pr.apply_ms, &pr.replay_ms};
                 for (size_t j = 0; j < nst; j++) { HIPCHK(ctx, hipEventElapsedTime(&ms, ev[nst * k + j], ev[nst * k + j + 1])); *into[4 - nst + j] += ms; }
             }
         HIPCHK(ctx, hipEventElapsedTime(&ms, ev.front(), ev.back()));
@@ -3563,107 +3605,11 @@ static int export_piece(w3_ctx *ctx, hipStream_t s, const ExpPiece &pc, const Ex
     return W3_OK;
 }
 
-extern "C" int w3_export_counters_device(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *d_in, size_t n, uint32_t *d_counters, void *stream) {
-    ExpModel m;
-    int rc = export_args(ctx, spec, d_in, n, d_counters, true, m);
-    if (rc) return rc;
-    ctx->exp_prof = w3_export_profile();
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    HIPCHK(ctx, hipMemsetAsync(d_counters, 0, (size_t)4 << m.bits, s));
-    if (n == 0) { HIPCHK(ctx, hipStreamSynchronize(s)); return W3_OK; }
-    if ((rc = export_ensure(ctx, s, m, n))) return rc;
-    const ExpPiece pc = {d_in, n, 0, 0};
-    return export_piece(ctx, s, pc, m, d_counters);
-}
-
-extern "C" int w3_export_counters_staged(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t n, uint32_t *counters) {
-    ExpModel m;
-    int rc = export_args(ctx, spec, in, n, counters, false, m);
-    if (rc) return rc;
-    ctx->exp_prof = w3_export_profile();
-    const size_t bytes = (size_t)4 << m.bits;
-    if (n == 0) { memset(counters, 0, bytes); return W3_OK; }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    const size_t piece = host_run_blocks(ctx, W3_PREP_NOMINAL_BLOCK) * (size_t)W3_PREP_NOMINAL_BLOCK;
-    if ((rc = export_ensure(ctx, s, m, n))) return rc;
-    ENSURE(ctx, ctx->exp_s, bytes);
-    ENSURE(ctx, ctx->io_in, std::min(n, piece));
-    HIPCHK(ctx, hipMemsetAsync(ctx->exp_s.p, 0, bytes, s));
-    for (size_t o0 = 0; o0 < n; o0 += piece) {
-        const size_t len = std::min(piece, n - o0);
-        uint32_t carry = 0;   // the four stream bytes before the piece
-        for (size_t k = o0 < 4 ? 0 : o0 - 4; k < o0; k++) carry = (carry << 8) | in[k];
-        HIPCHK(ctx, hipMemcpyAsync(ctx->io_in.p, in + o0, len, hipMemcpyHostToDevice, s));
-        const ExpPiece pc = {(const uint8_t *)ctx->io_in.p, len, o0, carry};
-        if ((rc = export_piece(ctx, s, pc, m, (uint32_t *)ctx->exp_s.p))) return rc;   // (synchronises: the next piece overwrites io_in)
-    }
-    HIPCHK(ctx, hipMemcpy(counters, ctx->exp_s.p, bytes, hipMemcpyDeviceToHost));
-    return W3_OK;
-}
-
-extern "C" int w3_export_get_profile(const w3_ctx *ctx, w3_export_profile *out) {
-    if (!ctx || !out) return W3_E_INVALID;
-    *out = ctx->exp_prof;
-    return W3_OK;
-}
-
-// ---------------------------------------------------------------------------
-// ... and for ONE adaptive leaf with any history (w3_export_entropy.h): OrderN and RawHistory through the kernels above, ACHistory and
-// HuffHistory with a key stage per epoch and count and replay over the keys.
-// ---------------------------------------------------------------------------
-static int export_entropy_args(w3_ctx *ctx, const w3_model_spec *spec, const void *in, size_t n, const void *out, bool one_device, ExpModel &m, ParsedSpec &ps) {
-    int rc = check_args(ctx, n, W3_PREP_NOMINAL_BLOCK, one_device);
-    if (rc) return rc;
-    if ((rc = jobs_idle(ctx))) return rc;   // (the workspace is the context's)
-    if ((rc = parse_spec(spec, ps))) return rc;
-    if (ps.n_leaves != 1 || ps.n_apm || ps.has_slot || ps.leaf[0].kind != W3_NODE_ORDERN || ps.leaf[0].frozen || ps.leaf[0].history > W3_HIST_HUFF) {
-        ctx->err = "w3_export_entropy_device / _staged take ONE adaptive OrderN or OrderNEntropy leaf (RawHistory, ACHistory, HuffHistory)";
-        return W3_E_UNSUPPORTED;
-    }
-    if (ps.leaf[0].bits > W3_EXP_MAX_BITS) { ctx->err = "tables above 2^28 counters are not exported"; return W3_E_UNSUPPORTED; }
-    if (!out || (!in && n)) return W3_E_INVALID;
-    m.bits = ps.leaf[0].bits; m.align = ps.leaf[0].align;
-    return W3_OK;
-}
-
-// the key stage's workspace and tables for pieces of at most `piece` bytes; false in `keyed`: the leaf needs none (OrderN, RawHistory)
-static int export_keyed_prepare(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, size_t piece, ExpKeyed &kd, bool &keyed) {
-    const w3_node &nd = ps.leaf[0];
-    keyed = nd.history == W3_HIST_AC || nd.history == W3_HIST_HUFF;
-    if (!keyed) return W3_OK;
-    memset(&kd, 0, sizeof kd);
-    kd.history = nd.history;
-    int rc;
-    if (nd.history == W3_HIST_HUFF) {
-        if ((rc = stage_huff(ctx, s, ps))) return rc;
-        kd.tb = lane_huff(ctx, ps) + nd.reserved;
-        ENSURE(ctx, ctx->exp_hs, W3_EXPK_HS_WORDS * 4);
-    } else {
-        GenericArgs ga;
-        memset(&ga, 0, sizeof ga);
-        (void)layout_generic(ps, W3_PREP_NOMINAL_BLOCK, ga);
-        if ((rc = prepare_achash_luts(ctx, s, ga))) return rc;
-        kd.lut = ga.leaf[0].lut; kd.max_bits = nd.max_bits;
-        memcpy(kd.table, nd.table, sizeof kd.table);
-    }
-    ENSURE(ctx, ctx->exp_k, (size_t)std::min<uint64_t>(export_epoch_bytes(ctx, true), (piece + 1023) / 1024 * 1024) * 32);
-    return W3_OK;
-}
-
-static void export_entropy_reset(w3_ctx *ctx) {
-    ctx->exp_prof = w3_export_profile();
-    ctx->exp_key_ms = 0.f;
-    ctx->exp_huff_fixed = 0;
-}
-
-extern "C" int w3_export_entropy_device(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *d_in, size_t n, uint32_t *d_counters, void *stream) {
+static int export_device(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *d_in, size_t n, uint32_t *d_counters, void *stream, bool admits_entropy) {
     ExpModel m;
     ParsedSpec ps;
-    int rc = export_entropy_args(ctx, spec, d_in, n, d_counters, true, m, ps);
+    int rc = export_args(ctx, spec, d_in, n, d_counters, true, admits_entropy, ps, m);
     if (rc) return rc;
-    export_entropy_reset(ctx);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     HIPCHK(ctx, hipMemsetAsync(d_counters, 0, (size_t)4 << m.bits, s));
@@ -3672,17 +3618,15 @@ extern "C" int w3_export_entropy_device(w3_ctx *ctx, const w3_model_spec *spec, 
     ExpKeyed kd;
     bool keyed = false;
     if ((rc = export_keyed_prepare(ctx, s, ps, n, kd, keyed))) return rc;
-    const ExpPiece pc = {d_in, n, 0, 0};
-    if (keyed) kd.kp = ExpKeyPiece{d_in, n, 0, 0, 0};
+    const ExpPiece pc = {d_in, n, 0, 0, 0};
     return export_piece(ctx, s, pc, m, d_counters, keyed ? &kd : nullptr);
 }
 
-extern "C" int w3_export_entropy_staged(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t n, uint32_t *counters) {
+static int export_staged(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t n, uint32_t *counters, bool admits_entropy) {
     ExpModel m;
     ParsedSpec ps;
-    int rc = export_entropy_args(ctx, spec, in, n, counters, false, m, ps);
+    int rc = export_args(ctx, spec, in, n, counters, false, admits_entropy, ps, m);
     if (rc) return rc;
-    export_entropy_reset(ctx);
     const size_t bytes = (size_t)4 << m.bits;
     if (n == 0) { memset(counters, 0, bytes); return W3_OK; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -3692,7 +3636,7 @@ extern "C" int w3_export_entropy_staged(w3_ctx *ctx, const w3_model_spec *spec, 
     ExpKeyed kd;
     bool keyed = false;
     if ((rc = export_keyed_prepare(ctx, s, ps, std::min(n, piece), kd, keyed))) return rc;
-    const w3_huff_table *tb = keyed && kd.history == W3_HIST_HUFF ? ps.huff + ps.leaf[0].reserved : nullptr;
+    const w3_huff_table *tb = keyed ? kd.host_tb : nullptr;   // (HuffHistory only)
     ENSURE(ctx, ctx->exp_s, bytes);
     ENSURE(ctx, ctx->io_in, std::min(n, piece));
     HIPCHK(ctx, hipMemsetAsync(ctx->exp_s.p, 0, bytes, s));
@@ -3703,19 +3647,34 @@ extern "C" int w3_export_entropy_staged(w3_ctx *ctx, const w3_model_spec *spec, 
         for (size_t k = o0 < 8 ? 0 : o0 - 8; k < o0; k++) carry = (carry << 8) | in[k];
         if (tb && o0) seed = expk_huff_piece_seed(in, o0, o0 - piece, seed, tb->code, tb->len);
         HIPCHK(ctx, hipMemcpyAsync(ctx->io_in.p, in + o0, len, hipMemcpyHostToDevice, s));
-        const ExpPiece pc = {(const uint8_t *)ctx->io_in.p, len, o0, (uint32_t)carry};
-        if (keyed) kd.kp = ExpKeyPiece{(const uint8_t *)ctx->io_in.p, len, o0, carry, seed};
+        const ExpPiece pc = {(const uint8_t *)ctx->io_in.p, len, o0, carry, seed};
         if ((rc = export_piece(ctx, s, pc, m, (uint32_t *)ctx->exp_s.p, keyed ? &kd : nullptr))) return rc;   // (synchronises: the next piece overwrites io_in)
     }
     HIPCHK(ctx, hipMemcpy(counters, ctx->exp_s.p, bytes, hipMemcpyDeviceToHost));
     return W3_OK;
 }
 
+extern "C" int w3_export_counters_device(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *d_in, size_t n, uint32_t *d_counters, void *stream) {
+    return export_device(ctx, spec, d_in, n, d_counters, stream, false);
+}
+extern "C" int w3_export_counters_staged(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t n, uint32_t *counters) {
+    return export_staged(ctx, spec, in, n, counters, false);
+}
+extern "C" int w3_export_entropy_device(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *d_in, size_t n, uint32_t *d_counters, void *stream) {
+    return export_device(ctx, spec, d_in, n, d_counters, stream, true);
+}
+extern "C" int w3_export_entropy_staged(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t n, uint32_t *counters) {
+    return export_staged(ctx, spec, in, n, counters, true);
+}
+
+extern "C" int w3_export_get_profile(const w3_ctx *ctx, w3_export_profile *out) {
+    if (!ctx || !out) return W3_E_INVALID;
+    *out = ctx->exp_prof.base;
+    return W3_OK;
+}
 extern "C" int w3_export_entropy_get_profile(const w3_ctx *ctx, w3_export_entropy_profile *out) {
     if (!ctx || !out) return W3_E_INVALID;
-    out->base = ctx->exp_prof;
-    out->key_ms = ctx->exp_key_ms;
-    out->huff_fixed_epochs = ctx->exp_huff_fixed;
+    *out = ctx->exp_prof;
     return W3_OK;
 }
 
