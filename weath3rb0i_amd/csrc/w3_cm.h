@@ -1,10 +1,12 @@
-// w3_cm.h — lane-per-block CONTEXT-MIXING kernel: the literal north-star design.  One wavefront lane
-// owns one block's arithmetic coder and model state; the 12-bit state table (NaiveStateTable,
+// w3_cm.h — the LANE-PER-BLOCK path: the literal north-star design.  One wavefront lane owns one
+// block's arithmetic coder and model state.  Here: the kernels for specs with a slot-state leaf or
+// an APM stage (k_cm_nl, k_cm_staged, k_cm).  The 12-bit state table (NaiveStateTable,
 // state_table/naive.rs) and the APM stretch LUT are staged in LDS; slot-model contexts are resolved
 // against a per-lane Cell/Slot hash map in HBM (hashmap.rs); Counter tables as in w3_generic.h.
 //
-// Runs every spec that contains a SLOT_STATE leaf or an APM stage, and every decode of such a spec
-// (decode is serial by nature: the next context depends on the decoded bit, main.rs:131-140).
+// The path encodes what the two-phase path does not cover (and everything under W3_PATH_GENERIC)
+// and decodes wherever k_decode_spec (w3_decode_spec.h) does not apply, every range job under
+// W3_VAR_DECODE_LANE included: it is the device's own cross-check of both.
 // The slot model, its replacement policy and the APM are BUILD-DEFINED (SURVEY §8 A19 ii-v): the
 // reference has the primitives but no model that uses them.  Definitions: DESIGN.md §2.4.
 #pragma once

@@ -14,7 +14,7 @@
 //   the four nodes on the decoded path update their Counters (Counter::update) and APM entries; an exact-map slot is claimed by
 //   compare-and-swap (two path nodes may meet one empty slot).
 // A wavefront holds four blocks: 3,815 wavefronts at enwik9 size instead of 239, and the chip hides the round trips it still has.
-// Model tables: the lane-per-block decoder's layout (layout_generic / layout_cm), one region per block.
+// Model tables: the lane-per-block decoder's layout (layout_generic / layout_lane), one region per block.
 // Covered: up to 8 leaves — Counter-table leaves of any history kind with alignment_bits >= 2 (FrozenModel leaves too), slot-state leaves (HS
 // below) — and 0..2 APM stages.  Everything else (alignment 0 / 1: the nibble's own updates feed its later contexts; longer chains) stays on
 // the lane-per-block kernels, which also remain the cross-check (W3_OPT_VARIANT bit 1024).
@@ -497,7 +497,7 @@ static inline void launch_decode_spec_na(const CmArgs &ca, uint32_t cnt, hipStre
     default: hipLaunchKernelGGL((k_decode_spec<NL, 2, D, false, NM, RAW>), grid, blk, 0, s, ca); break;
     }
 }
-// table formats of this batch (the APM tables' initialisation must agree: cm_run asks the same question)
+// table formats of this batch (the APM tables' initialisation must agree: lane_run asks the same question)
 static inline bool decode_spec_nibble_major(const CmArgs &ca, uint32_t cnt, int bits_per_group) {
     if (bits_per_group != 4) return false;                      // (the two-bit-group variant keeps the round-3 formats)
     if (ca.dflags & 1u) return false;                           // W3_OPT_TUNE bit 17: round-3 formats whatever the size

@@ -1,8 +1,10 @@
-// w3_generic.h — GENERIC device path: one wavefront lane runs the reference's
-// bit loop (main.rs:103-109 encode, :131-140 decode) for one block, with its
-// model state (Counter tables) in HBM.  Handles every model spec, including
-// the ones the two-phase fast path does not cover, and is the only decoder
-// (decoding is serial by nature: the next context depends on the decoded bit).
+// w3_generic.h — the LANE-PER-BLOCK path, Counter-leaf half: one wavefront lane runs the reference's
+// bit loop (main.rs:103-109 encode, :131-140 decode) for one block, with its model state (Counter
+// tables) in HBM.  Here: the argument block, a leaf's context and table slot, and the kernels for specs
+// of Counter leaves alone (k_generic, k_generic_nl); slot-state leaves and APM chains: w3_cm.h.
+// The path handles every model spec: it is the encoder of the specs the two-phase path does not
+// cover (and of W3_PATH_GENERIC), the decoder wherever k_decode_spec (w3_decode_spec.h) does not
+// apply and under W3_VAR_DECODE_LANE, and the device's own cross-check of both.
 #pragma once
 #include "w3_device.h"
 #include "../../include/w3hip.h"

@@ -513,7 +513,7 @@ static int run_pack(w3_ctx *ctx, Job &J, hipStream_t s, const uint8_t *stripes, 
 }
 
 // ---------------------------------------------------------------------------
-// generic path
+// lane-per-block path (w3_generic.h, w3_cm.h): every spec, encode and decode, through one runner (lane_run)
 // ---------------------------------------------------------------------------
 static int table_budget(w3_ctx *ctx, uint64_t lane_stride, uint32_t want_lanes, uint32_t &lanes_out) {
     size_t free_b = 0, total_b = 0;
@@ -568,94 +568,8 @@ static int prepare_achash_luts(w3_ctx *ctx, hipStream_t s, GenericArgs &ga) {
 // nibble and leaf) was measured for the large batches, which are bound by those look-ups' HBM traffic — order012apm 736 -> 758 MiB/s at 1e9 B,
 // but order012 856 -> 778, Order0 3,906 -> 3,366, main.rs default 1,585 -> 1,417, and 189 -> 104 MiB/s at 1e8 B: four round trips per nibble
 // instead of two, and a quarter of the wavefronts to hide them (profiles/r3_decode_spec/).  Kept as a tested variant.
-static int decode_group_bits(const w3_ctx *ctx, uint32_t blocks_in_batch) {
-    (void)blocks_in_batch;
-    return (ctx->opt.tune & 16384u) ? 2 : 4;
-}
+static int decode_group_bits(const w3_ctx *ctx) { return (ctx->opt.tune & 16384u) ? 2 : 4; }
 
-// k_generic over cnt lanes; 1-4 leaves: all Counter loads of a step in flight together
-template <bool DECODE>
-static void launch_generic(const GenericArgs &ga, uint32_t cnt, hipStream_t s) {
-    const dim3 grid((cnt + 63) / 64), blk(64);
-    switch (ga.n_leaves) {
-    case 1: hipLaunchKernelGGL((k_generic_nl<DECODE, 1>), grid, blk, 0, s, ga); break;
-    case 2: hipLaunchKernelGGL((k_generic_nl<DECODE, 2>), grid, blk, 0, s, ga); break;
-    case 3: hipLaunchKernelGGL((k_generic_nl<DECODE, 3>), grid, blk, 0, s, ga); break;
-    case 4: hipLaunchKernelGGL((k_generic_nl<DECODE, 4>), grid, blk, 0, s, ga); break;
-    default: hipLaunchKernelGGL(k_generic<DECODE>, grid, blk, 0, s, ga); break;
-    }
-}
-
-static int generic_encode(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, const uint8_t *d_in, size_t n, size_t block_size,
-                          uint32_t nb, uint32_t stripe_cap, uint32_t *d_lens) {
-    GenericArgs ga;
-    memset(&ga, 0, sizeof ga);
-    const uint64_t lane_stride = layout_generic(ps, block_size, ga);
-    uint32_t lanes = 0;
-    int rc = table_budget(ctx, lane_stride, nb, lanes);
-    if (rc) return rc;
-    if ((rc = prepare_achash_luts(ctx, s, ga))) return rc;
-    ENSURE(ctx, ctx->tables, (size_t)lanes * lane_stride);
-    ga.n = n; ga.block_size = (uint32_t)block_size;
-    ga.huff = lane_huff(ctx, ps); ga.n_huff = (int)ps.n_huff;
-    ga.tables = (uint8_t *)ctx->tables.p; ga.lane_stride = lane_stride;
-    ga.in = d_in; ga.stripe_cap = stripe_cap; ga.out_len = d_lens; ga.overflow = (uint32_t *)ctx->jobs[0].flag.p;
-    ga.out_bits = (uint32_t *)ctx->jobs[0].bits.p;
-    for (uint32_t first = 0; first < nb; first += lanes) {
-        uint32_t cnt = std::min(lanes, nb - first);
-        ga.first_block = first; ga.n_lanes = cnt;
-        ga.stripes = (uint8_t *)ctx->jobs[0].stripes.p + (uint64_t)first * stripe_cap;
-        HIPCHK(ctx, hipMemsetAsync(ctx->tables.p, 0, (size_t)cnt * lane_stride, s));
-        launch_generic<false>(ga, cnt, s);
-        HIPCHK(ctx, hipGetLastError());
-    }
-    return W3_OK;
-}
-
-// The decoders: every block of the length table d_lens[nb] whole (d_jobs == nullptr), or the n_jobs decode jobs of d_jobs (the
-// random-access decode: w3_ranges.h) — the lanes, and with them the table budget's batches, the table zero-fill, the APM tables'
-// initialisation and k_decode_spec's choices, then count jobs instead of blocks.
-// Precondition: ctx->coffs holds the exclusive scan of d_lens[nb], enqueued on s (scan_lens / check_len_table).
-static int generic_decode(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, const uint8_t *d_cin, const uint32_t *d_lens, uint32_t nb,
-                          size_t block_size, uint64_t orig_len, uint8_t *d_out, const DecodeJob *d_jobs = nullptr, uint32_t n_jobs = 0) {
-    GenericArgs ga;
-    memset(&ga, 0, sizeof ga);
-    const uint64_t lane_stride = layout_generic(ps, block_size, ga);
-    const uint32_t nl = d_jobs ? n_jobs : nb;
-    uint32_t lanes = 0;
-    int rc = table_budget(ctx, lane_stride, nl, lanes);
-    if (rc) return rc;
-    if ((rc = prepare_achash_luts(ctx, s, ga))) return rc;
-    ENSURE(ctx, ctx->tables, (size_t)lanes * lane_stride);
-    ga.n = orig_len; ga.block_size = (uint32_t)block_size;
-    ga.huff = lane_huff(ctx, ps); ga.n_huff = (int)ps.n_huff;
-    ga.tables = (uint8_t *)ctx->tables.p; ga.lane_stride = lane_stride;
-    ga.cin = d_cin; ga.coffs = (const uint64_t *)ctx->coffs.p; ga.clens = d_lens; ga.dout = d_out;
-    ga.jobs = d_jobs;
-    for (uint32_t first = 0; first < nl; first += lanes) {
-        uint32_t cnt = std::min(lanes, nl - first);
-        ga.first_block = first; ga.n_lanes = cnt;
-        HIPCHK(ctx, hipMemsetAsync(ctx->tables.p, 0, (size_t)cnt * lane_stride, s));
-        {   // the nibble's context tree at once, sixteen lanes per block (w3_decode_spec.h), where it applies
-            CmArgs ca;
-            memset(&ca, 0, sizeof ca);
-            ca.g = ga;
-            ca.dflags = (ctx->opt.tune >> 17) & 7u;
-            if (decode_spec_covers(ca) && !(ctx->opt.variant & W3_VAR_DECODE_LANE)) {
-                launch_decode_spec(ca, cnt, s, decode_group_bits(ctx, cnt));
-                HIPCHK(ctx, hipGetLastError());
-                continue;
-            }
-        }
-        launch_generic<true>(ga, cnt, s);
-        HIPCHK(ctx, hipGetLastError());
-    }
-    return W3_OK;
-}
-
-// ---------------------------------------------------------------------------
-// CM path (slot-state leaves and/or APM chain): k_cm, lane per block
-// ---------------------------------------------------------------------------
 static int cm_luts(w3_ctx *ctx, hipStream_t s, CmArgs &ca) {
     const size_t st_bytes = (size_t)kStSize * 8, str_bytes = 4096 * 2, sq_bytes = 4096 * 2;
     if (!ctx->cm_luts.p) {
@@ -683,8 +597,12 @@ static int cm_luts(w3_ctx *ctx, hipStream_t s, CmArgs &ca) {
     return W3_OK;
 }
 
-static uint64_t layout_cm(const ParsedSpec &ps, size_t block_size, CmArgs &ca) {
-    uint64_t off = (layout_generic(ps, block_size, ca.g) + 15) / 16 * 16;
+// The per-lane table region: the Counter tables and slot-leaf hash maps (layout_generic), then, for specs with APM stages or slot
+// leaves, rounded up to 16 bytes, the APM tables.  Returns the lane stride.
+static uint64_t layout_lane(const ParsedSpec &ps, size_t block_size, CmArgs &ca) {
+    uint64_t off = layout_generic(ps, block_size, ca.g);
+    if (!ps.is_cm()) return off;
+    off = (off + 15) / 16 * 16;
     ca.n_apm = ps.n_apm;
     for (int k = 0; k < ps.n_apm; k++) {
         ca.apm[k].ctx_kind = ps.apm[k].align;
@@ -696,72 +614,71 @@ static uint64_t layout_cm(const ParsedSpec &ps, size_t block_size, CmArgs &ca) {
     return off;
 }
 
+// Which lane-per-block kernel runs a spec, over cnt lanes.  Up to 4 Counter leaves and no slot leaves: the kernels with all Counter
+// loads of a step in flight together, k_generic_nl without and k_cm_nl with an APM chain.  Otherwise the run-time leaf loop: without
+// APM stages and slot leaves k_generic, else the slot cells staged in LDS (k_cm_staged: up to W3_CM_STAGED_MAX slot leaves, none
+// included) or in global memory (k_cm).  Specs of Counter leaves alone take the kernels over GenericArgs, the rest those over CmArgs.
 template <bool DECODE>
-static int cm_run(w3_ctx *ctx, hipStream_t s, CmArgs &ca, uint64_t lane_stride, uint32_t nb, uint32_t stripe_cap) {
+static void lane_launch(const CmArgs &ca, uint32_t cnt, hipStream_t s, bool unstaged) {
+    static void (*const plain_nl[4])(GenericArgs) = {k_generic_nl<DECODE, 1>, k_generic_nl<DECODE, 2>, k_generic_nl<DECODE, 3>, k_generic_nl<DECODE, 4>};
+    static void (*const cm_nl[4])(CmArgs) = {k_cm_nl<DECODE, 1>, k_cm_nl<DECODE, 2>, k_cm_nl<DECODE, 3>, k_cm_nl<DECODE, 4>};
+    const dim3 grid((cnt + 63) / 64), blk(64);
+    const int nl = ca.g.n_leaves;
+    int n_slot = 0;
+    for (int l = 0; l < nl; l++) n_slot += ca.g.leaf[l].kind == 1;
+    const bool batch = !n_slot && nl >= 1 && nl <= 4;
+    if (!n_slot && !ca.n_apm) hipLaunchKernelGGL(batch ? plain_nl[nl - 1] : k_generic<DECODE>, grid, blk, 0, s, ca.g);
+    else hipLaunchKernelGGL(batch ? cm_nl[nl - 1] : n_slot <= W3_CM_STAGED_MAX && !unstaged ? k_cm_staged<DECODE> : k_cm<DECODE>, grid, blk, 0, s, ca);
+}
+
+// What one call of the lane-per-block path codes.  Encode: in -> job 0's stripes of stripe_cap bytes each, the blocks' lengths to out_len.
+// Decode: the streams cin, by the length table clens[nb], -> dout: every block whole (jobs == nullptr), or the n_jobs decode jobs (the
+// random-access decode: w3_ranges.h) — the lanes, and with them the table budget's batches, the table zero-fill, the APM tables'
+// initialisation and k_decode_spec's choices, then count jobs instead of blocks.
+// Decode precondition: ctx->coffs holds the exclusive scan of clens[nb], enqueued on s (scan_lens / check_len_table).
+struct LaneIo {
+    const uint8_t *in = nullptr; uint32_t stripe_cap = 0; uint32_t *out_len = nullptr;
+    const uint8_t *cin = nullptr; const uint32_t *clens = nullptr; uint8_t *dout = nullptr; const DecodeJob *jobs = nullptr; uint32_t n_jobs = 0;
+};
+
+template <bool DECODE>
+static int lane_run(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, size_t block_size, uint64_t n, uint32_t nb, const LaneIo &io) {
+    CmArgs ca;
+    memset(&ca, 0, sizeof ca);
+    GenericArgs &g = ca.g;
+    const uint64_t lane_stride = layout_lane(ps, block_size, ca);
+    const uint32_t nl = io.jobs ? io.n_jobs : nb;   // (the lanes: blocks, or jobs)
     uint32_t lanes = 0;
-    int rc = table_budget(ctx, lane_stride, nb, lanes);
+    int rc = table_budget(ctx, lane_stride, nl, lanes);
     if (rc) return rc;
-    ENSURE(ctx, ctx->tables, (size_t)lanes * lane_stride);
-    if ((rc = cm_luts(ctx, s, ca))) return rc;
-    ca.g.tables = (uint8_t *)ctx->tables.p; ca.g.lane_stride = lane_stride;
-    for (uint32_t first = 0; first < nb; first += lanes) {
-        uint32_t cnt = std::min(lanes, nb - first);
-        ca.g.first_block = first; ca.g.n_lanes = cnt;
-        if (!DECODE) ca.g.stripes = (uint8_t *)ctx->jobs[0].stripes.p + (uint64_t)first * stripe_cap;
+    if ((rc = prepare_achash_luts(ctx, s, g))) return rc;
+    if (ps.is_cm() && (rc = cm_luts(ctx, s, ca))) return rc;
+    ca.dflags = (ctx->opt.tune >> 17) & 7u;
+    g.n = n; g.block_size = (uint32_t)block_size;
+    g.huff = lane_huff(ctx, ps); g.n_huff = (int)ps.n_huff;
+    g.tables = (uint8_t *)ctx->tables.p; g.lane_stride = lane_stride;
+    if (DECODE) {
+        g.cin = io.cin; g.coffs = (const uint64_t *)ctx->coffs.p; g.clens = io.clens; g.dout = io.dout; g.jobs = io.jobs;
+    } else {
+        g.in = io.in; g.stripe_cap = io.stripe_cap; g.out_len = io.out_len;
+        g.overflow = (uint32_t *)ctx->jobs[0].flag.p; g.out_bits = (uint32_t *)ctx->jobs[0].bits.p;
+    }
+    // the nibble's context tree at once, sixteen lanes per block (w3_decode_spec.h), where it applies
+    const bool spec_dec = DECODE && decode_spec_covers(ca) && !(ctx->opt.variant & W3_VAR_DECODE_LANE);
+    for (uint32_t first = 0; first < nl; first += lanes) {
+        const uint32_t cnt = std::min(lanes, nl - first);
+        g.first_block = first; g.n_lanes = cnt;
+        if (!DECODE) g.stripes = (uint8_t *)ctx->jobs[0].stripes.p + (uint64_t)first * io.stripe_cap;
         HIPCHK(ctx, hipMemsetAsync(ctx->tables.p, 0, (size_t)cnt * lane_stride, s));
-        const bool spec_dec = DECODE && decode_spec_covers(ca) && !(ctx->opt.variant & W3_VAR_DECODE_LANE);
-        ca.dflags = (ctx->opt.tune >> 17) & 7u;
-        const bool nm_tables = spec_dec && decode_spec_nibble_major(ca, cnt, decode_group_bits(ctx, cnt));   // (the APM tables' layout follows the kernel's)
+        const bool nm_tables = spec_dec && decode_spec_nibble_major(ca, cnt, decode_group_bits(ctx));   // (the APM tables' layout follows the kernel's)
         for (int k = 0; k < ca.n_apm; k++)
-            hipLaunchKernelGGL(k_cm_init_apm, dim3(2048), dim3(256), 0, s, ca.g.tables, lane_stride, ca.apm[k].off,
+            hipLaunchKernelGGL(k_cm_init_apm, dim3(2048), dim3(256), 0, s, g.tables, lane_stride, ca.apm[k].off,
                                nm_tables ? (ca.apm[k].ctx_kind ? 256u * 272u : 272u) : (ca.apm[k].ctx_kind ? 65536u : 256u), cnt, ca.squash, nm_tables ? 1u : 0u);
-        bool has_slot = false;
-        for (int l = 0; l < ca.g.n_leaves; l++) has_slot |= ca.g.leaf[l].kind == 1;
-        const dim3 grid((cnt + 63) / 64), blk(64);
-        if (spec_dec) launch_decode_spec(ca, cnt, s, decode_group_bits(ctx, cnt));   // (w3_decode_spec.h)
-        else if (!has_slot && ca.g.n_leaves <= 4) {   // Counter leaves + APM chain: all Counter loads of a step in flight together
-            switch (ca.g.n_leaves) {
-            case 1: hipLaunchKernelGGL((k_cm_nl<DECODE, 1>), grid, blk, 0, s, ca); break;
-            case 2: hipLaunchKernelGGL((k_cm_nl<DECODE, 2>), grid, blk, 0, s, ca); break;
-            case 3: hipLaunchKernelGGL((k_cm_nl<DECODE, 3>), grid, blk, 0, s, ca); break;
-            default: hipLaunchKernelGGL((k_cm_nl<DECODE, 4>), grid, blk, 0, s, ca); break;
-            }
-        } else {
-            int n_slot = 0;
-            for (int l = 0; l < ca.g.n_leaves; l++) n_slot += ca.g.leaf[l].kind == 1;
-            if (n_slot <= W3_CM_STAGED_MAX && !(ctx->opt.variant & W3_VAR_CM_UNSTAGED)) hipLaunchKernelGGL(k_cm_staged<DECODE>, grid, blk, 0, s, ca);   // slot cells staged in LDS
-            else hipLaunchKernelGGL(k_cm<DECODE>, grid, blk, 0, s, ca);
-        }
+        if (spec_dec) launch_decode_spec(ca, cnt, s, decode_group_bits(ctx));
+        else lane_launch<DECODE>(ca, cnt, s, (ctx->opt.variant & W3_VAR_CM_UNSTAGED) != 0);
         HIPCHK(ctx, hipGetLastError());
     }
     return W3_OK;
-}
-
-static int cm_encode(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, const uint8_t *d_in, size_t n, size_t block_size,
-                     uint32_t nb, uint32_t stripe_cap, uint32_t *d_lens) {
-    CmArgs ca;
-    memset(&ca, 0, sizeof ca);
-    const uint64_t lane_stride = layout_cm(ps, block_size, ca);
-    { int rc_ = prepare_achash_luts(ctx, s, ca.g); if (rc_) return rc_; }
-    ca.g.n = n; ca.g.block_size = (uint32_t)block_size;
-    ca.g.huff = lane_huff(ctx, ps); ca.g.n_huff = (int)ps.n_huff;
-    ca.g.in = d_in; ca.g.stripe_cap = stripe_cap; ca.g.out_len = d_lens; ca.g.overflow = (uint32_t *)ctx->jobs[0].flag.p;
-    ca.g.out_bits = (uint32_t *)ctx->jobs[0].bits.p;
-    return cm_run<false>(ctx, s, ca, lane_stride, nb, stripe_cap);
-}
-
-// (precondition as generic_decode: ctx->coffs holds the exclusive scan of d_lens[nb], enqueued on s)
-static int cm_decode(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, const uint8_t *d_cin, const uint32_t *d_lens, uint32_t nb,
-                     size_t block_size, uint64_t orig_len, uint8_t *d_out, const DecodeJob *d_jobs = nullptr, uint32_t n_jobs = 0) {
-    CmArgs ca;
-    memset(&ca, 0, sizeof ca);
-    const uint64_t lane_stride = layout_cm(ps, block_size, ca);
-    { int rc_ = prepare_achash_luts(ctx, s, ca.g); if (rc_) return rc_; }
-    ca.g.n = orig_len; ca.g.block_size = (uint32_t)block_size;
-    ca.g.huff = lane_huff(ctx, ps); ca.g.n_huff = (int)ps.n_huff;
-    ca.g.cin = d_cin; ca.g.coffs = (const uint64_t *)ctx->coffs.p; ca.g.clens = d_lens; ca.g.dout = d_out;
-    ca.g.jobs = d_jobs;
-    return cm_run<true>(ctx, s, ca, lane_stride, d_jobs ? n_jobs : nb, 0);   // (the lanes: blocks, or jobs)
 }
 
 // ---------------------------------------------------------------------------
@@ -940,8 +857,9 @@ static int encode_core(w3_ctx *ctx, Job &J, const w3_model_spec *spec, const uin
             ctx->timing.path = W3_PATH_TWOPHASE;
         } else {
             if (evp) HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_PREDICT], s));
-            rc = ps.is_cm() ? cm_encode(ctx, s, ps, d_in, n, block_size, nb, cap, d_block_lens)
-                            : generic_encode(ctx, s, ps, d_in, n, block_size, nb, cap, d_block_lens);
+            LaneIo io;
+            io.in = d_in; io.stripe_cap = cap; io.out_len = d_block_lens;
+            rc = lane_run<false>(ctx, s, ps, block_size, n, nb, io);
             if (evp) HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_PREDICT + 1], s));
             ctx->timing.path = W3_PATH_GENERIC;
             if (rc) return rc;
@@ -1474,8 +1392,9 @@ extern "C" int w3_decode_blocks_device(w3_ctx *ctx, const w3_model_spec *spec, c
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     if ((rc = stage_huff(ctx, s, ps))) return rc;
     if ((rc = check_len_table(ctx, s, d_block_lens, (uint32_t)nb, in_len))) return rc;
-    rc = ps.is_cm() ? cm_decode(ctx, s, ps, d_in, d_block_lens, (uint32_t)nb, block_size, orig_len, d_out)
-                    : generic_decode(ctx, s, ps, d_in, d_block_lens, (uint32_t)nb, block_size, orig_len, d_out);
+    LaneIo io;
+    io.cin = d_in; io.clens = d_block_lens; io.dout = d_out;
+    rc = lane_run<true>(ctx, s, ps, block_size, orig_len, (uint32_t)nb, io);
     if (rc) return rc;
     HIPCHK(ctx, hipStreamSynchronize(s));
     return W3_OK;
@@ -1977,10 +1896,11 @@ static int ranges_run(w3_ctx *ctx, hipStream_t s, const RangeDec &rd, const uint
                       uint64_t staging, uint8_t *d_out, const CrcSeg *d_segs = nullptr) {
     ENSURE(ctx, ctx->rg_stage, (size_t)staging + 16);   // (k_gather_pieces reads up to 3 bytes past a piece)
     uint8_t *d_stage = (uint8_t *)ctx->rg_stage.p;
+    LaneIo io;
+    io.cin = d_cin; io.clens = d_lens; io.dout = d_stage; io.jobs = d_jobs; io.n_jobs = n_jobs;
     const int rc = !rd.ps ? aoh_decode_run(ctx, s, rd.aoh_code, rd.aoh_ctx_bits, d_cin, d_lens, nb, block_size, orig_len, d_stage, d_jobs, n_jobs, max_job_len,
                                            aoh_ranges_take_spec(ctx, rd.aoh_ctx_bits))
-                 : rd.ps->is_cm() ? cm_decode(ctx, s, *rd.ps, d_cin, d_lens, nb, block_size, orig_len, d_stage, d_jobs, n_jobs)
-                                  : generic_decode(ctx, s, *rd.ps, d_cin, d_lens, nb, block_size, orig_len, d_stage, d_jobs, n_jobs);
+                          : lane_run<true>(ctx, s, *rd.ps, block_size, orig_len, nb, io);
     if (rc) return rc;
     if (d_segs) {
         if (const int r = crc_enqueue(ctx, s, d_stage, staging, (uint32_t)block_size, d_segs, n_jobs, max_job_len, nullptr, nullptr, true)) return r;
@@ -3391,8 +3311,9 @@ extern "C" int w3_export_counters(w3_ctx *ctx, const w3_model_spec *spec, const 
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     if ((rc = stage_huff(ctx, s, ps))) return rc;
-    GenericArgs ga;
-    memset(&ga, 0, sizeof ga);
+    CmArgs ca;
+    memset(&ca, 0, sizeof ca);
+    GenericArgs &ga = ca.g;
     (void)layout_generic(ps, n, ga);
     ga.leaf[0].use_hash = 0; ga.leaf[0].tbl_off = 0;            // direct-indexed, like the reference's Vec<Counter>
     if ((rc = prepare_achash_luts(ctx, s, ga))) return rc;
@@ -3409,7 +3330,7 @@ extern "C" int w3_export_counters(w3_ctx *ctx, const w3_model_spec *spec, const 
     ga.tables = (uint8_t *)ctx->tables.p; ga.lane_stride = entries * 4;
     ga.in = (const uint8_t *)ctx->io_in.p; ga.stripes = (uint8_t *)ctx->jobs[0].stripes.p; ga.stripe_cap = cap;
     ga.out_len = (uint32_t *)ctx->lens.p; ga.overflow = (uint32_t *)ctx->jobs[0].flag.p; ga.out_bits = nullptr;
-    launch_generic<false>(ga, 1, s);
+    lane_launch<false>(ca, 1, s, false);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(counters, ctx->tables.p, entries * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
