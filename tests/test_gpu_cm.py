@@ -279,7 +279,7 @@ def test_cm_unstaged_kernel_still_agrees(ctx, oracle):
     ctx.set_variant("cm_unstaged")
     try:
         for name in ("slot_mix", "full_cm_small_tables"):
-            check(ctx, oracle, name, data, 4096)
+            check(ctx, oracle, name, data, 4096, variant=("cm_unstaged",))   # (or check()'s k_slot leg would take the variant off before its generic leg)
     finally:
         ctx.set_variant()
 
