@@ -170,7 +170,7 @@ enum {
                            pipeline's arrangements and the slot replay's shapes (HISTORY.md 2.8); 15: rank kernels with eight wavefronts per half
                            CU; 16: host-buffer copies on two streams of their own instead of the context's stream; 17 / 18: k_decode_spec with
                            the round-3 table formats / with the nibble-major ones whatever the batch size (default: by size); 19: the general k_decode_spec
-                           where the instance specialised for all-raw-history models would run */
+                           where the instance specialised for all-raw-history models would run; 20: w3_export_steps_*: the row kernel's direct store form */
     W3_OPT_FAULT_BLOCK = 10, /* test hook, with W3_OPT_VARIANT bit 32: the one block the injected fault hits (-1 = every block, default) */
     W3_OPT_HOST_CHUNK_BLOCKS = 12, /* w3_encode_blocks: blocks per pipelined piece of a host-buffer call (0 = default: equal pieces of at most
                            4,096 blocks; tests use small values to get ragged pieces).  w3_decode_blocks, w3_decode_ranges, w3_crc32_blocks, their
@@ -569,6 +569,63 @@ typedef struct w3_export_entropy_profile {
 int w3_export_entropy_device(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *d_in, size_t n, uint32_t *d_counters, void *stream);
 int w3_export_entropy_staged(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t n, uint32_t *counters);
 int w3_export_entropy_get_profile(const w3_ctx *ctx, w3_export_entropy_profile *out);
+
+/* ---- per-step statistics: what every model said before every coded bit (csrc/w3_steps.h) ---------------------------
+ * README.md:9 again: a network that mixes or post-processes a CM's predictions trains on the predictions, not on a final table.  These
+ * calls write one ROW per coded bit: row t = 8 i + k belongs to input byte i and bit k (k = 0: the MSB — the order of w3_predict_blocks'
+ * p_out), every value the prediction BEFORE that step's update; blocks restart the model, as everywhere.  Columns, 2 bytes each, C per row:
+ *   one per leaf            in the spec's postfix leaf order; a FrozenModel leaf has no stream: the constant 32768
+ *   mix                     the root before any APM stage (OpinionMixer2 over the leaves; equals the leaf where there is one)
+ *   one per APM stage       in chain order
+ *   bit                     with W3_STEPS_COL_BIT: the coded bit (0 / 1; 0.0 / 1.0 in F16)
+ * The last model column (col_final) is what the coder is given: it equals w3_predict_blocks' output.  Nobody should hard-code the
+ * order: w3_steps_layout_of (host only, no device needed) tells it; col_apm0 and col_bit are UINT32_MAX where there is no such column.
+ * Formats, all exact:  W3_STEPS_P_U16      Counter::p / the stage's output as is (uint16)
+ *                      W3_STEPS_STRETCH_I16  the build's stretch[p >> 4] (w3_stretch_squash), -2047 .. 2047 (int16)
+ *                      W3_STEPS_STRETCH_F16  that integer / 256 as IEEE binary16 — exact: |v| < 2^11, and the division is an exponent
+ *                                            shift.  (bfloat16 cannot hold these values exactly and is not offered.)
+ *   w3_export_steps_device  d_in, d_rows on ctx's GPU; d_rows 16-byte aligned (W3_E_INVALID), rows_cap >= 8 n C 2 bytes (W3_E_NOSPACE), both
+ *                           checked before anything is launched.  n == 0 is W3_OK.  Specs and sizes the two-phase predict kernels do not
+ *                           cover (n < 8, block_size > 2^24): W3_E_UNSUPPORTED, as w3_predict_blocks.  W3_E_INVALID while a job is in flight.
+ *                           n < 2^32 - 4096 per call: the rows of a larger input do not fit one buffer anyway (1e9 bytes x 6 columns =
+ *                           96 GB), a caller walks it in runs of whole blocks.  stream NULL = the context's; the call synchronises it.
+ *   w3_export_steps_staged  host input of ANY length, host rows: pieces of whole blocks (W3_OPT_HOST_CHUNK_BLOCKS blocks per piece;
+ *                           0 = as many as give 2 GiB of rows).
+ * The rows come from the same LDS-add rounds as an encode, and carry the same insurance: the sampled re-prediction (W3_OPT_VERIFY) runs
+ * on the leaves' streams before any APM stage; on a mismatch the call predicts again with ballot rounds, counts it in
+ * w3_timing.n_lds_faults, and the context stays on them.  W3_OPT_TUNE bit 20: the row kernel's direct store form (same rows).
+ * w3_export_steps_get_profile: the last call's times (under W3_OPT_TIMING; sums over the staged form's pieces) and byte counts.
+ * Not built: Counter confidence counts as columns, AC-over-Huffman streams, a submit / wait form, several GPUs.          */
+enum { W3_STEPS_P_U16 = 0, W3_STEPS_STRETCH_I16 = 1, W3_STEPS_STRETCH_F16 = 2 };
+enum { W3_STEPS_COL_BIT = 1 };
+typedef struct w3_steps_layout {
+    uint32_t n_cols, n_leaves, col_mix, col_apm0, n_apm, col_final, col_bit, elem_bytes;
+} w3_steps_layout;
+typedef struct w3_steps_profile {
+    float    predict_ms, apm_ms, rows_ms, total_ms;   /* predict phase; APM stages and their copies; the row kernel; first to last kernel */
+    uint64_t bytes_read, bytes_written;               /* the row kernel's */
+    uint32_t n_lds_faults, direct_stores;             /* as w3_timing's; 1 = the row kernel ran its direct store form */
+} w3_steps_profile;
+int w3_steps_layout_of(const w3_model_spec *spec, uint32_t format, uint32_t flags, w3_steps_layout *out);
+int w3_export_steps_device(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *d_in, size_t n, size_t block_size, uint32_t format,
+                           uint32_t flags, void *d_rows, size_t rows_cap, void *stream);
+int w3_export_steps_staged(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t n, size_t block_size, uint32_t format,
+                           uint32_t flags, void *rows, size_t rows_cap);
+int w3_export_steps_get_profile(const w3_ctx *ctx, w3_steps_profile *out);
+
+/* ---- ... and back: code from a caller's probabilities -------------------------------------------------------------------------------
+ * The one number the reference's drivers print for a model — the coded size under the real 32-bit coder (main.rs:103-109) — for a
+ * stream of probabilities the CALLER supplies, e.g. a trained mixer's output over the rows above: ac.encode(bit, p) with p = d_p[8 i + k]
+ * (uint16, 16-byte aligned, the step order above) in place of model.predict().  There is no model: nothing is predicted or verified.
+ * The other arguments and the output are w3_encode_blocks_device's (the block container's streams) and w3_encode_stats_device's (the
+ * ACStats bit counts).  The coders need p in 1 .. 65535 (a zero would make the coder's interval empty): d_p is checked on the device
+ * first, and with a zero in it the call returns W3_E_INVALID — w3_last_error names the first such step and their count — before any
+ * coder kernel is launched and with no output touched.  n < 8 or block_size > 2^24: W3_E_UNSUPPORTED (the two-phase coders' limits).
+ * There is NO decode counterpart: a decoder needs p for bit t before it knows bit t - 1, and cannot ask an external network per bit.   */
+int w3_encode_probs_device(w3_ctx *ctx, const uint8_t *d_in, size_t n, size_t block_size, const uint16_t *d_p,
+                           uint8_t *d_out, size_t out_cap, uint32_t *d_block_lens, uint64_t *d_total, void *stream);
+int w3_encode_stats_probs_device(w3_ctx *ctx, const uint8_t *d_in, size_t n, size_t block_size, const uint16_t *d_p,
+                                 uint32_t *d_block_bits, void *stream);
 
 /* ---- the reference's whole-file container ----------------------------------
  * compress()/decompress() of main.rs:89-144: b"w30i" + u64 BE length + ONE

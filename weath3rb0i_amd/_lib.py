@@ -74,6 +74,20 @@ class ExportEntropyProfile(C.Structure):   # w3_export_entropy_profile
     _fields_ = [("base", ExportProfile), ("key_ms", C.c_float), ("huff_fixed_epochs", C.c_uint64)]
 
 
+class StepsLayout(C.Structure):   # w3_steps_layout
+    _fields_ = [(k, C.c_uint32) for k in ("n_cols", "n_leaves", "col_mix", "col_apm0", "n_apm", "col_final", "col_bit", "elem_bytes")]
+
+
+class StepsProfile(C.Structure):   # w3_steps_profile
+    _fields_ = [("predict_ms", C.c_float), ("apm_ms", C.c_float), ("rows_ms", C.c_float), ("total_ms", C.c_float),
+                ("bytes_read", C.c_uint64), ("bytes_written", C.c_uint64), ("n_lds_faults", C.c_uint32), ("direct_stores", C.c_uint32)]
+
+
+W3_STEPS_P_U16, W3_STEPS_STRETCH_I16, W3_STEPS_STRETCH_F16 = 0, 1, 2   # include/w3hip.h "per-step statistics"
+W3_STEPS_COL_BIT = 1
+W3_STEPS_NO_COL = 0xFFFFFFFF
+W3_TUNE_STEPS_DIRECT = 1 << 20   # W3_OPT_TUNE: the row kernel's direct store form
+
 W3_STAT_TILE, W3_STAT_BATCH, W3_HIST_REP = 4096, 64, 16  # include/w3hip.h "table preparation on the device"
 
 EXPORTS = [
@@ -94,6 +108,8 @@ EXPORTS = [
     "w3_huff_tables_from_counts", "w3_table_prep_profile",
     "w3_export_counters_device", "w3_export_counters_staged", "w3_export_get_profile",
     "w3_export_entropy_device", "w3_export_entropy_staged", "w3_export_entropy_get_profile",
+    "w3_steps_layout_of", "w3_export_steps_device", "w3_export_steps_staged", "w3_export_steps_get_profile",
+    "w3_encode_probs_device", "w3_encode_stats_probs_device",
 ]
 
 _lib = None
@@ -203,6 +219,13 @@ def load():
         getattr(lib, "w3_export_%s_staged" % which).argtypes = [vp, C.POINTER(ModelSpec), vp, sz, vp]
     lib.w3_export_get_profile.argtypes = [vp, C.POINTER(ExportProfile)]
     lib.w3_export_entropy_get_profile.argtypes = [vp, C.POINTER(ExportEntropyProfile)]
+    u32 = C.c_uint32
+    lib.w3_steps_layout_of.argtypes = [C.POINTER(ModelSpec), u32, u32, C.POINTER(StepsLayout)]
+    lib.w3_export_steps_device.argtypes = [vp, C.POINTER(ModelSpec), vp, sz, sz, u32, u32, vp, sz, vp]
+    lib.w3_export_steps_staged.argtypes = [vp, C.POINTER(ModelSpec), vp, sz, sz, u32, u32, vp, sz]
+    lib.w3_export_steps_get_profile.argtypes = [vp, C.POINTER(StepsProfile)]
+    lib.w3_encode_probs_device.argtypes = [vp, vp, sz, sz, vp, vp, sz, vp, vp, vp]
+    lib.w3_encode_stats_probs_device.argtypes = [vp, vp, sz, sz, vp, vp, vp]
     lib.w3_rccl_library.argtypes = [C.c_char_p]
     lib.w3_rccl_status.argtypes = [C.c_char_p, sz]
     _lib = lib

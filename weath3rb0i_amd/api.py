@@ -382,6 +382,139 @@ class Context:
         out.update(key_ms=p.key_ms, huff_fixed_epochs=p.huff_fixed_epochs)
         return out
 
+    # ---- per-step statistics (include/w3hip.h "per-step statistics"; csrc/w3_steps.h) ----
+    _STEPS_FORMATS = {"p_u16": L.W3_STEPS_P_U16, "stretch_i16": L.W3_STEPS_STRETCH_I16, "stretch_f16": L.W3_STEPS_STRETCH_F16}
+    _STEPS_NUMPY = {"p_u16": np.uint16, "stretch_i16": np.int16, "stretch_f16": np.float16}
+
+    @staticmethod
+    def steps_layout(model, format="stretch_f16", bit=False):
+        """w3_steps_layout_of: the columns of a row of export_steps* for this model -> dict(n_cols, n_leaves, col_mix, col_apm0, n_apm,
+        col_final, col_bit, elem_bytes); col_apm0 / col_bit are None where there is no such column.  Host only: needs no context
+        (Context.steps_layout(model, ...)) and no device."""
+        spec = model.spec() if isinstance(model, Model) else model
+        lay = L.StepsLayout()
+        # (a format or flags value given as a number goes through as it is: the library refuses what it does not know)
+        fmt = Context._STEPS_FORMATS.get(format, 0xFFFF) if isinstance(format, str) else int(format)
+        flags = (L.W3_STEPS_COL_BIT if bit else 0) if isinstance(bit, bool) else int(bit)
+        rc = L.load().w3_steps_layout_of(C.byref(spec), fmt, flags, C.byref(lay))
+        if rc:
+            raise W3Error(rc, "w3_steps_layout_of: malformed spec, or an unknown format or flag")
+        out = {k: getattr(lay, k) for k, _ in L.StepsLayout._fields_}
+        for k in ("col_apm0", "col_bit"):
+            if out[k] == L.W3_STEPS_NO_COL:
+                out[k] = None
+        return out
+
+    @staticmethod
+    def _steps_format(format):
+        """the export calls take a format by NAME (steps_layout also passes numbers through, for the library to refuse)"""
+        if not isinstance(format, str) or format not in Context._STEPS_FORMATS:
+            raise W3Error(L.W3_E_INVALID, "format: one of %s" % ", ".join(sorted(Context._STEPS_FORMATS)))
+        return Context._STEPS_FORMATS[format]
+
+    @staticmethod
+    def _probs_args(d_in, d_p):
+        import torch
+        if d_in.dtype != torch.uint8 or not d_in.is_cuda or not d_in.is_contiguous():
+            raise W3Error(L.W3_E_INVALID, "d_in: a contiguous torch.uint8 CUDA tensor")
+        if d_p.numel() != 8 * d_in.numel() or d_p.element_size() != 2 or not d_p.is_contiguous() or d_p.device != d_in.device:
+            raise W3Error(L.W3_E_INVALID, "d_p: a contiguous tensor of 8 n 16-bit values on d_in's device")
+
+    @staticmethod
+    def _steps_torch_dtype(format):
+        import torch
+        if format == "p_u16":
+            return getattr(torch, "uint16", torch.int16)
+        return torch.int16 if format == "stretch_i16" else torch.float16
+
+    def export_steps_device(self, model, d_in, block_size, format="stretch_f16", bit=True, out=None, stream=None):
+        """w3_export_steps_device: one row per coded bit of what every part of the model said before it — a column per leaf, the mix, a
+        column per APM stage, and (bit=True) the coded bit; steps_layout() names the columns.  d_in: a contiguous torch.uint8 CUDA
+        tensor; the bytes never leave the device.  format: "p_u16" (Counter::p as is), "stretch_i16" (stretch[p >> 4], -2047 .. 2047),
+        "stretch_f16" (that / 256, exact).  -> a CUDA tensor [8 n, C] of torch.uint16 / int16 / float16 (`out` when given: a contiguous
+        tensor of that shape and dtype on d_in's device).  Where this torch build has no uint16, "p_u16" rows come as torch.int16
+        holding the same bits."""
+        import torch
+        if d_in.dtype != torch.uint8 or not d_in.is_cuda or not d_in.is_contiguous():
+            raise W3Error(L.W3_E_INVALID, "d_in: a contiguous torch.uint8 CUDA tensor")
+        fmt = self._steps_format(format)
+        spec = model.spec() if isinstance(model, Model) else model
+        lay = self.steps_layout(spec, format, bool(bit))
+        n, cols, dt = d_in.numel(), lay["n_cols"], self._steps_torch_dtype(format)
+        if out is None:
+            out = torch.empty((8 * n, cols), dtype=dt, device=d_in.device)
+        elif out.dtype != dt or tuple(out.shape) != (8 * n, cols) or not out.is_contiguous() or out.device != d_in.device:
+            raise W3Error(L.W3_E_INVALID, "out: a contiguous %s tensor of shape (%d, %d) on d_in's device" % (dt, 8 * n, cols))
+        st = C.c_void_p(stream) if stream else None
+        self._chk(self.lib.w3_export_steps_device(self.h, C.byref(spec), C.c_void_p(d_in.data_ptr()), n, block_size, fmt,
+                                                  L.W3_STEPS_COL_BIT if bit else 0, C.c_void_p(out.data_ptr()), out.numel() * 2, st))
+        return out
+
+    def export_steps(self, model, data, block_size, format="stretch_f16", bit=True):
+        """w3_export_steps_staged: the same rows from host `data` of any length, through the device in pieces of whole blocks
+        (set_host_chunk_blocks).  -> np.ndarray [8 n, C] of uint16 / int16 / float16"""
+        fmt = self._steps_format(format)
+        spec = model.spec() if isinstance(model, Model) else model
+        lay = self.steps_layout(spec, format, bool(bit))
+        a = _u8(data)
+        rows = np.empty((8 * len(a), lay["n_cols"]), dtype=self._STEPS_NUMPY[format])
+        self._chk(self.lib.w3_export_steps_staged(self.h, C.byref(spec), a.ctypes.data_as(C.c_void_p), len(a), block_size, fmt,
+                                                  L.W3_STEPS_COL_BIT if bit else 0, rows.ctypes.data_as(C.c_void_p), rows.nbytes))
+        return rows
+
+    def iter_steps(self, model, d_in, block_size, blocks_per_batch, format="stretch_f16", bit=True, stream=None):
+        """export_steps_device in batches of `blocks_per_batch` whole blocks — a workload's rows do not fit one tensor (1e9 bytes x 6
+        columns is 96 GB).  Yields (first_step, rows): rows is a view of ONE reused tensor (consume or copy it before the next batch),
+        rows[j] is step first_step + j."""
+        n, run = d_in.numel(), int(blocks_per_batch) * int(block_size)
+        if run <= 0:
+            raise W3Error(L.W3_E_INVALID, "blocks_per_batch and block_size must be positive")
+        buf = None
+        for o0 in range(0, n, run):
+            piece = d_in[o0:o0 + run]
+            if buf is None:
+                buf = self.export_steps_device(model, piece, block_size, format, bit, stream=stream)
+                rows = buf
+            else:
+                rows = self.export_steps_device(model, piece, block_size, format, bit, out=buf[:8 * piece.numel()], stream=stream)
+            yield 8 * o0, rows
+
+    def steps_profile(self):
+        """w3_export_steps_get_profile: what the last export_steps* call did (the times under set_timing())"""
+        p = L.StepsProfile()
+        self._chk(self.lib.w3_export_steps_get_profile(self.h, C.byref(p)))
+        return {k: getattr(p, k) for k, _ in L.StepsProfile._fields_}
+
+    def encode_probs_device(self, d_in, block_size, d_p, out_cap=None, stream=None):
+        """w3_encode_probs_device: the block container's streams with the caller's probabilities in place of a model's — d_p: a
+        contiguous CUDA tensor of 8 n 16-bit values (uint16, or int16 holding the same bits; 16-byte aligned), d_p[8 i + k] = P(bit k of
+        byte i is 1), each in 1 .. 65535 (a zero is refused: W3_E_INVALID names the first such step).  -> (out: torch.uint8 CUDA tensor of
+        the concatenated streams, block_lens: torch.int32 [nb]).  There is no decode counterpart."""
+        import torch
+        self._probs_args(d_in, d_p)
+        n = d_in.numel()
+        nb = (n + block_size - 1) // block_size if block_size else 0
+        cap = int(out_cap) if out_cap is not None else int(self.lib.w3_max_compressed_size(n, block_size))
+        out = torch.empty(max(cap, 1), dtype=torch.uint8, device=d_in.device)
+        lens = torch.zeros(max(nb, 1), dtype=torch.int32, device=d_in.device)
+        total = torch.zeros(1, dtype=torch.int64, device=d_in.device)
+        st = C.c_void_p(stream) if stream else None
+        self._chk(self.lib.w3_encode_probs_device(self.h, C.c_void_p(d_in.data_ptr()), n, block_size, C.c_void_p(d_p.data_ptr()),
+                                                  C.c_void_p(out.data_ptr()), cap, C.c_void_p(lens.data_ptr()), C.c_void_p(total.data_ptr()), st))
+        return out[: int(total.item())], lens[:nb]
+
+    def encode_stats_probs_device(self, d_in, block_size, d_p, stream=None):
+        """w3_encode_stats_probs_device: the ACStats bit counts (encode_stats) of the same coding -> torch.int32 [nb] CUDA tensor"""
+        import torch
+        self._probs_args(d_in, d_p)
+        n = d_in.numel()
+        nb = (n + block_size - 1) // block_size if block_size else 0
+        bits = torch.zeros(max(nb, 1), dtype=torch.int32, device=d_in.device)
+        st = C.c_void_p(stream) if stream else None
+        self._chk(self.lib.w3_encode_stats_probs_device(self.h, C.c_void_p(d_in.data_ptr()), n, block_size, C.c_void_p(d_p.data_ptr()),
+                                                        C.c_void_p(bits.data_ptr()), st))
+        return bits[:nb]
+
     def predict_blocks(self, model, data, block_size):
         spec = model.spec()
         a = _u8(data)

@@ -887,6 +887,66 @@ static inline int tp_after_predict(TwoPhaseWs &ws, hipStream_t s_pred, const Par
     return W3_OK;
 }
 
+// The coder over the streams ws.mix names (at most 4 of them mixed on the fly by the x3 / x4 / x5 kernels; the others read ONE stream: the
+// single source, or the merged ws.P).  tp_code_stage ends in it; w3_encode_probs_device runs it alone over a caller's stream.
+static inline int tp_coder(TwoPhaseWs &ws, hipStream_t s, int coder, bool x3, const uint8_t *d_in, size_t n, size_t block_size, uint32_t nb, uint8_t *stripes,
+                           uint32_t stripe_cap, uint32_t *d_lens, uint32_t *d_flag, hipEvent_t *ev, w3_timing *tm, std::string &err) {
+    int rc;
+    if (w3_tune_env("W3_DEBUG_NOSTORE")) { err = "W3_DEBUG_NOSTORE: predict-only timing experiment"; return W3_E_UNSUPPORTED; }
+    if ((rc = tp_ensure(ws.redo, ws.redo_cap, (size_t)nb * 4, err))) return rc;
+    const uint32_t limit = std::min<uint32_t>(ws.opt.acc_limit, 46u);
+    if (ev) (void)hipEventRecord(ev[2 * W3_EV_CODER], s);
+    if (x3) {
+        w3::Coder3Args c3;
+        memset(&c3, 0, sizeof c3);
+        c3.in = d_in; c3.n = n; c3.block_size = (uint32_t)block_size; c3.nblocks = nb;
+        for (int l = 0; l < ws.mix.n_src; l++) c3.src[l] = ws.mix.src[l];
+        c3.stripes = stripes; c3.stripe_cap = stripe_cap; c3.out_len = d_lens; c3.flags = d_flag; c3.redo = (uint32_t *)ws.redo;
+        c3.acc_limit = limit;
+        c3.out_bits = ws.out_bits;
+        c3.prio_mo = (ws.opt.tune >> 7) & 1u;
+        const dim3 grid((nb + 63) / 64);
+        // x3: three waves.  x4 / x5: M, X, O, and a second M-wave when the leaves are mixed on the fly (L > 1).
+        // x5 has half the LDS: it leaves room beside it for the next call's predict workgroups.
+        auto launch = [&](auto lc) {
+            constexpr int L = decltype(lc)::value;
+            const dim3 blk(L > 1 && coder != 4 ? 256 : 192);
+            if (coder == 4) hipLaunchKernelGGL(w3::k_coder_x3<L>, grid, blk, 0, s, c3);
+            else if (coder == 5) hipLaunchKernelGGL(w3::k_coder_x5<L>, grid, blk, 0, s, c3);
+            else hipLaunchKernelGGL(w3::k_coder_x4<L>, grid, blk, 0, s, c3);
+        };
+        switch (ws.mix.n_src) {
+        case 1: launch(std::integral_constant<int, 1>()); break;
+        case 2: launch(std::integral_constant<int, 2>()); break;
+        case 3: launch(std::integral_constant<int, 3>()); break;
+        default: launch(std::integral_constant<int, 4>()); break;
+        }
+        if (tm) tm->coder_bytes = (uint64_t)n * (16 * ws.mix.n_src + 1);
+    } else {
+        w3::CoderArgs ca;
+        memset(&ca, 0, sizeof ca);
+        ca.in = d_in; ca.n = n; ca.block_size = (uint32_t)block_size; ca.nblocks = nb;
+        ca.P = ws.mix.n_src == 1 ? ws.mix.src[0] : (const uint4 *)ws.P;   // (one source: the stream itself — ws.P after an APM stage or a single leaf)
+        ca.stripes = stripes; ca.stripe_cap = stripe_cap; ca.out_len = d_lens; ca.flags = d_flag;
+        ca.acc_limit = limit;
+        ca.out_bits = ws.out_bits;
+        if (coder == 2) {
+            ca.redo = nullptr;
+            hipLaunchKernelGGL(w3::k_coder, dim3((nb + 63) / 64), dim3(64), 0, s, ca);
+        } else {
+            ca.redo = (uint32_t *)ws.redo;
+            if (coder == 1) hipLaunchKernelGGL(w3::k_coder_fast, dim3((nb + 63) / 64), dim3(64), 0, s, ca);
+            else hipLaunchKernelGGL(w3::k_coder_x2, dim3((nb + 63) / 64), dim3(128), 0, s, ca);
+        }
+        if (tm) tm->coder_bytes = (uint64_t)n * 17;
+    }
+    if (ev) (void)hipEventRecord(ev[2 * W3_EV_CODER + 1], s);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { err = std::string("coder launch: ") + hipGetErrorString(e); return W3_E_HIP; }
+    if (tm) tm->n_coder_launches = 1;
+    return W3_OK;
+}
+
 // wait_ev: one more event the stage waits for (the NEXT call's first predict half); rec_after_apm: recorded when the APM stages are
 // through (the next call's rank kernels wait for it).  Either may be null.
 static inline int tp_code_stage(TwoPhaseWs &ws, hipStream_t s_pred, hipStream_t s, const ParsedSpec &ps, const uint8_t *d_in, size_t n, size_t block_size,
@@ -924,58 +984,7 @@ static inline int tp_code_stage(TwoPhaseWs &ws, hipStream_t s_pred, hipStream_t 
     if ((rc = twophase_apm(ws, s, ps, d_in, n, block_size, nb, ev, tm, err))) return rc;   // leaves ws.P as the one source stream
     if (rec_after_apm) (void)hipEventRecord(rec_after_apm, s);
     if (verify_on && !verify_in_place && (rc = fork_verify(s))) return rc;
-    if (w3_tune_env("W3_DEBUG_NOSTORE")) { err = "W3_DEBUG_NOSTORE: predict-only timing experiment"; return W3_E_UNSUPPORTED; }
-    if ((rc = tp_ensure(ws.redo, ws.redo_cap, (size_t)nb * 4, err))) return rc;
-    const uint32_t limit = std::min<uint32_t>(ws.opt.acc_limit, 46u);
-    if (ev) (void)hipEventRecord(ev[2 * W3_EV_CODER], s);
-    if (x3) {
-        w3::Coder3Args c3;
-        memset(&c3, 0, sizeof c3);
-        c3.in = d_in; c3.n = n; c3.block_size = (uint32_t)block_size; c3.nblocks = nb;
-        for (int l = 0; l < ws.mix.n_src; l++) c3.src[l] = ws.mix.src[l];
-        c3.stripes = stripes; c3.stripe_cap = stripe_cap; c3.out_len = d_lens; c3.flags = d_flag; c3.redo = (uint32_t *)ws.redo;
-        c3.acc_limit = limit;
-        c3.out_bits = ws.out_bits;
-        c3.prio_mo = (ws.opt.tune >> 7) & 1u;
-        const dim3 grid((nb + 63) / 64);
-        // x3: three waves.  x4 / x5: M, X, O, and a second M-wave when the leaves are mixed on the fly (L > 1).
-        // x5 has half the LDS: it leaves room beside it for the next call's predict workgroups.
-        auto launch = [&](auto lc) {
-            constexpr int L = decltype(lc)::value;
-            const dim3 blk(L > 1 && coder != 4 ? 256 : 192);
-            if (coder == 4) hipLaunchKernelGGL(w3::k_coder_x3<L>, grid, blk, 0, s, c3);
-            else if (coder == 5) hipLaunchKernelGGL(w3::k_coder_x5<L>, grid, blk, 0, s, c3);
-            else hipLaunchKernelGGL(w3::k_coder_x4<L>, grid, blk, 0, s, c3);
-        };
-        switch (ws.mix.n_src) {
-        case 1: launch(std::integral_constant<int, 1>()); break;
-        case 2: launch(std::integral_constant<int, 2>()); break;
-        case 3: launch(std::integral_constant<int, 3>()); break;
-        default: launch(std::integral_constant<int, 4>()); break;
-        }
-        if (tm) tm->coder_bytes = (uint64_t)n * (16 * ws.mix.n_src + 1);
-    } else {
-        w3::CoderArgs ca;
-        memset(&ca, 0, sizeof ca);
-        ca.in = d_in; ca.n = n; ca.block_size = (uint32_t)block_size; ca.nblocks = nb; ca.P = (const uint4 *)ws.P;
-        ca.stripes = stripes; ca.stripe_cap = stripe_cap; ca.out_len = d_lens; ca.flags = d_flag;
-        ca.acc_limit = limit;
-        ca.out_bits = ws.out_bits;
-        if (coder == 2) {
-            ca.redo = nullptr;
-            hipLaunchKernelGGL(w3::k_coder, dim3((nb + 63) / 64), dim3(64), 0, s, ca);
-        } else {
-            ca.redo = (uint32_t *)ws.redo;
-            if (coder == 1) hipLaunchKernelGGL(w3::k_coder_fast, dim3((nb + 63) / 64), dim3(64), 0, s, ca);
-            else hipLaunchKernelGGL(w3::k_coder_x2, dim3((nb + 63) / 64), dim3(128), 0, s, ca);
-        }
-        if (tm) tm->coder_bytes = (uint64_t)n * 17;
-    }
-    if (ev) (void)hipEventRecord(ev[2 * W3_EV_CODER + 1], s);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { err = std::string("coder launch: ") + hipGetErrorString(e); return W3_E_HIP; }
-    if (tm) tm->n_coder_launches = 1;
-    return W3_OK;
+    return tp_coder(ws, s, coder, x3, d_in, n, block_size, nb, stripes, stripe_cap, d_lens, d_flag, ev, tm, err);
 }
 
 // s_pred: the predict phase's launch stream; s: the stream of the APM stages, the coder and whatever the caller enqueues next

@@ -32,6 +32,7 @@
 #include "w3_prep.h"
 #include "w3_export.h"
 #include "w3_export_entropy.h"
+#include "w3_steps.h"
 
 using namespace w3;
 
@@ -126,6 +127,10 @@ struct w3_ctx {
     w3_export_entropy_profile exp_prof{};           // (w3_export_get_profile returns its base)
     // ... for OrderNEntropy leaves (w3_export_entropy.h): the keys of one epoch, the Huffman key stage's state words
     DevBuf exp_k, exp_hs;
+    // the per-step statistics export (w3_steps.h): the stream copies the row kernel reads (a single leaf's, before an APM stage rewrites it in
+    // place, and every stage's but the last), the staged form's rows, the zero count of a caller's stream; what the last call did
+    DevBuf steps_copies, steps_rows, probs_res;
+    w3_steps_profile steps_prof{};
     uint64_t crc_res[2] = {~0ull, 0};
     // What a job takes from the context when a call is prepared (hand_options): the two-phase options (w3_ctx_set_option), the
     // context-mixing look-up tables in cm_luts, and the lane-order self-test's verdict (-1 not run yet under this variant, 1 = returning
@@ -341,7 +346,7 @@ extern "C" int w3_ctx_set_option(w3_ctx *ctx, int opt, int64_t value) {
         ctx->opt.slot_budget_mb = (uint32_t)value;
         return W3_OK;
     case W3_OPT_TUNE:
-        if (value < 0 || value > 0xFFFFF) return W3_E_INVALID;
+        if (value < 0 || value > 0x1FFFFF) return W3_E_INVALID;
         ctx->opt.tune = (uint32_t)value;
         return W3_OK;
     case W3_OPT_FAULT_BLOCK:
@@ -808,37 +813,14 @@ static void fill_timing(w3_ctx *ctx, Job &J, const w3_timing &ptm, uint64_t tota
     if (timed) collect_timing(J.ev, J.tp, ps.n_apm > 0, ps.has_slot, packed, ctx->timing);
 }
 
-// d_out == nullptr: counting-sink mode (ACStats, helpers.rs:60-90) — the streams are coded into the stripes as usual, the
-// pack is skipped and only J.bits (per-block bit counts) is of interest; d_block_lens may then be a scratch buffer.
-// Synchronous: returns when the output is complete.  J = the job whose workspace is used (jobs[0] for every synchronous entry point;
-// w3_encode_wait redoes a job of its own here).
-static int encode_core(w3_ctx *ctx, Job &J, const w3_model_spec *spec, const uint8_t *d_in, size_t n, size_t block_size,
-                       uint8_t *d_out, size_t out_cap, uint32_t *d_block_lens, uint64_t *d_total, void *stream) {
-    int rc = check_args(ctx, n, block_size);
-    if (rc) return rc;
-    ParsedSpec ps;
-    if ((rc = parse_spec(spec, ps))) { ctx->err = "malformed model spec"; return rc; }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    const uint32_t nb = (uint32_t)((n + block_size - 1) / block_size);
-    memset(&ctx->timing, 0, sizeof ctx->timing);
-    ENSURE(ctx, ctx->total, 8);
-    uint64_t *total_p = d_total ? d_total : (uint64_t *)ctx->total.p;
-    if (nb == 0) {
-        HIPCHK(ctx, hipMemsetAsync(total_p, 0, 8, s));
-        HIPCHK(ctx, hipStreamSynchronize(s));
-        return W3_OK;
-    }
-    if (!d_in || !d_block_lens) return W3_E_INVALID;
-    const bool two = twophase_supported(ps, block_size, n) && ctx->opt_path != W3_PATH_GENERIC;   // Counter and slot-state leaves + APM chain (decode: k_generic / k_cm)
-    if (ctx->opt_path == W3_PATH_TWOPHASE && !two) { ctx->err = "spec/block size not covered by the two-phase path"; return W3_E_UNSUPPORTED; }
-    if (!two && J.index) { ctx->err = "internal: the lane-per-block path runs on job 0"; return W3_E_INVALID; }
-    if ((rc = job_prepare(ctx, J, ps, s, two, (ctx->opt.variant & W3_VAR_HALF_CU) != 0, n, block_size, nb))) return rc;
-
-    hipEvent_t *evp = ctx->opt_timing ? J.ev : nullptr;
-    uint32_t cap = default_stripe_cap(block_size);
-    w3_timing ptm;
-    memset(&ptm, 0, sizeof ptm);
+// The attempts of one synchronous encode on job J (encode_core's, for a model's streams and for a caller's alike: the attempt is what
+// differs between the two): `attempt(cap)` enqueues one attempt's kernels with stripes of `cap` bytes per block; its status words are
+// read back, handed-back blocks are recoded, and the attempt is repeated on the ballot path or with the worst-case stripes where the words
+// ask for it (w3_jobs.h).  cap: in = the first attempt's stripes, out = the last one's.  two: the attempts run the two-phase coder.
+template <class Attempt>
+static int encode_attempts(w3_ctx *ctx, Job &J, hipStream_t s, bool two, const uint8_t *d_in, size_t n, size_t block_size, uint32_t nb,
+                           uint32_t *d_block_lens, hipEvent_t *evp, uint32_t &cap, Attempt &&attempt) {
+    int rc;
     bool cap_raised = false, fault_seen = false;
     uint32_t lds_faults = 0;
     auto read_status = [&](JobStatus &st) -> int {
@@ -846,24 +828,11 @@ static int encode_core(w3_ctx *ctx, Job &J, const w3_model_spec *spec, const uin
         HIPCHK(ctx, hipStreamSynchronize(s));
         return W3_OK;
     };
-    for (int attempt = 0; attempt < 4; attempt++) {
+    for (int k = 0; k < 4; k++) {
         ENSURE(ctx, J.stripes, (size_t)nb * cap);
         HIPCHK(ctx, hipMemsetAsync(J.flag.p, 0, 4 * ST_WORDS, s));
         if (evp) HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_TOTAL], s));
-        if (two) {
-            memset(&ptm, 0, sizeof ptm);
-            rc = twophase_encode(J.tp, s, s, ps, d_in, n, block_size, nb, (uint8_t *)J.stripes.p, cap, d_block_lens, (uint32_t *)J.flag.p, evp, &ptm, ctx->err);
-            if (rc) return rc;
-            ctx->timing.path = W3_PATH_TWOPHASE;
-        } else {
-            if (evp) HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_PREDICT], s));
-            LaneIo io;
-            io.in = d_in; io.stripe_cap = cap; io.out_len = d_block_lens;
-            rc = lane_run<false>(ctx, s, ps, block_size, n, nb, io);
-            if (evp) HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_PREDICT + 1], s));
-            ctx->timing.path = W3_PATH_GENERIC;
-            if (rc) return rc;
-        }
+        if ((rc = attempt(cap))) return rc;
         JobStatus st{};
         if ((rc = read_status(st))) return rc;
         JobAction act = job_classify(st, cap_raised, fault_seen, two);
@@ -892,6 +861,70 @@ static int encode_core(w3_ctx *ctx, Job &J, const w3_model_spec *spec, const uin
         ctx->timing.n_recoded_blocks = 0;
     }
     ctx->timing.n_lds_faults = lds_faults;
+    return W3_OK;
+}
+
+// d_out == nullptr: counting-sink mode (ACStats, helpers.rs:60-90) — the streams are coded into the stripes as usual, the
+// pack is skipped and only J.bits (per-block bit counts) is of interest; d_block_lens may then be a scratch buffer.
+// Synchronous: returns when the output is complete.  J = the job whose workspace is used (jobs[0] for every synchronous entry point;
+// w3_encode_wait redoes a job of its own here).
+// d_p != nullptr: no model — the coder runs over the caller's stream d_p (w3_encode_probs_device, which has checked it; `spec` is not read).
+static int encode_core(w3_ctx *ctx, Job &J, const w3_model_spec *spec, const uint8_t *d_in, size_t n, size_t block_size,
+                       uint8_t *d_out, size_t out_cap, uint32_t *d_block_lens, uint64_t *d_total, void *stream, const uint16_t *d_p = nullptr) {
+    int rc = check_args(ctx, n, block_size);
+    if (rc) return rc;
+    ParsedSpec ps;
+    if (!d_p && (rc = parse_spec(spec, ps))) { ctx->err = "malformed model spec"; return rc; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    const uint32_t nb = (uint32_t)((n + block_size - 1) / block_size);
+    memset(&ctx->timing, 0, sizeof ctx->timing);
+    ENSURE(ctx, ctx->total, 8);
+    uint64_t *total_p = d_total ? d_total : (uint64_t *)ctx->total.p;
+    if (nb == 0) {
+        HIPCHK(ctx, hipMemsetAsync(total_p, 0, 8, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        return W3_OK;
+    }
+    if (!d_in || !d_block_lens) return W3_E_INVALID;
+    const bool two = d_p || (twophase_supported(ps, block_size, n) && ctx->opt_path != W3_PATH_GENERIC);   // Counter and slot-state leaves + APM chain (decode: k_generic / k_cm)
+    if (ctx->opt_path == W3_PATH_TWOPHASE && !two) { ctx->err = "spec/block size not covered by the two-phase path"; return W3_E_UNSUPPORTED; }
+    if (!two && J.index) { ctx->err = "internal: the lane-per-block path runs on job 0"; return W3_E_INVALID; }
+    if ((rc = job_prepare(ctx, J, ps, s, two, (ctx->opt.variant & W3_VAR_HALF_CU) != 0, n, block_size, nb))) return rc;
+
+    hipEvent_t *evp = ctx->opt_timing ? J.ev : nullptr;
+    uint32_t cap = default_stripe_cap(block_size);
+    w3_timing ptm;
+    memset(&ptm, 0, sizeof ptm);
+    rc = encode_attempts(ctx, J, s, two, d_in, n, block_size, nb, d_block_lens, evp, cap, [&](uint32_t cap_now) -> int {
+        int r;
+        if (d_p) {   // the coder part of tp_code_stage over the one stream
+            memset(&ptm, 0, sizeof ptm);
+            TwoPhaseWs &ws = J.tp;
+            ws.P_valid = false; ws.used_lds_atomics = false;
+            memset(&ws.mix, 0, sizeof ws.mix);
+            ws.mix.src[0] = (const uint4 *)d_p; ws.mix.n_src = 1;
+            const TpPlan pl = tp_plan(ws, ps);
+            r = tp_coder(ws, s, pl.coder, pl.x3, d_in, n, block_size, nb, (uint8_t *)J.stripes.p, cap_now, d_block_lens, (uint32_t *)J.flag.p, evp, &ptm, ctx->err);
+            if (r) return r;
+            ctx->timing.path = W3_PATH_TWOPHASE;
+        } else if (two) {
+            memset(&ptm, 0, sizeof ptm);
+            r = twophase_encode(J.tp, s, s, ps, d_in, n, block_size, nb, (uint8_t *)J.stripes.p, cap_now, d_block_lens, (uint32_t *)J.flag.p, evp, &ptm, ctx->err);
+            if (r) return r;
+            ctx->timing.path = W3_PATH_TWOPHASE;
+        } else {
+            if (evp) HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_PREDICT], s));
+            LaneIo io;
+            io.in = d_in; io.stripe_cap = cap_now; io.out_len = d_block_lens;
+            r = lane_run<false>(ctx, s, ps, block_size, n, nb, io);
+            if (evp) HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_PREDICT + 1], s));
+            ctx->timing.path = W3_PATH_GENERIC;
+            if (r) return r;
+        }
+        return W3_OK;
+    });
+    if (rc) return rc;
     uint64_t total = 0;
     if (d_out) {
         if (evp) HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_PACK], s));
@@ -904,7 +937,10 @@ static int encode_core(w3_ctx *ctx, Job &J, const w3_model_spec *spec, const uin
         if (evp) HIPCHK(ctx, hipEventRecord(evp[2 * W3_EV_TOTAL + 1], s));
         HIPCHK(ctx, hipStreamSynchronize(s));
     }
-    if (two) fill_timing(ctx, J, ptm, total, ps, evp != nullptr, d_out != nullptr);
+    if (d_p) {   // no model: only the coder's, the pack's and the call's events were recorded
+        fill_timing(ctx, J, ptm, total, ps, false, d_out != nullptr);
+        if (evp) { ctx->timing.coder_ms = elapsed_ev(evp, W3_EV_CODER); ctx->timing.pack_ms = d_out ? elapsed_ev(evp, W3_EV_PACK) : 0.f; ctx->timing.total_ms = elapsed_ev(evp, W3_EV_TOTAL); }
+    } else if (two) fill_timing(ctx, J, ptm, total, ps, evp != nullptr, d_out != nullptr);
     else if (evp) { ctx->timing.generic_ms = elapsed_ev(evp, W3_EV_PREDICT); ctx->timing.pack_ms = d_out ? elapsed_ev(evp, W3_EV_PACK) : 0.f; ctx->timing.total_ms = elapsed_ev(evp, W3_EV_TOTAL); }
     ctx->timing.n_parts = 1;
     if (d_out && total > out_cap) { ctx->err = "out_cap too small"; return W3_E_NOSPACE; }
@@ -1355,6 +1391,67 @@ extern "C" int w3_encode_stats_device(w3_ctx *ctx, const w3_model_spec *spec, co
     rc = encode_core(ctx, ctx->jobs[0], spec, d_in, n, block_size, nullptr, 0, (uint32_t *)ctx->lens.p, nullptr, stream);
     if (rc) return rc;
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    HIPCHK(ctx, hipMemcpyAsync(d_block_bits, ctx->jobs[0].bits.p, nb * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return W3_OK;
+}
+
+// ---------------------------------------------------------------------------
+// code from a caller's probability stream (include/w3hip.h: w3_encode_probs_device)
+// ---------------------------------------------------------------------------
+// Everything before the coder: the arguments, and the zero count of d_p.  The coders rely on p in 1 .. 65535, so NO coder kernel is
+// launched unless the count read back here is 0.
+static int probs_check(w3_ctx *ctx, const uint8_t *d_in, size_t n, size_t block_size, const uint16_t *d_p, hipStream_t s) {
+    if (!d_in || !d_p) return W3_E_INVALID;
+    if (((uintptr_t)d_p & 15u) != 0) { ctx->err = "d_p must be 16-byte aligned"; return W3_E_INVALID; }
+    if (block_size > (1u << 24) || n < 8) { ctx->err = "a caller's stream is coded by the two-phase coders: n >= 8, block_size <= 2^24"; return W3_E_UNSUPPORTED; }
+    ENSURE(ctx, ctx->probs_res, 16);
+    const unsigned long long init[2] = {0ull, ~0ull};
+    unsigned long long res[2] = {0ull, ~0ull};
+    HIPCHK(ctx, hipMemcpyAsync(ctx->probs_res.p, init, 16, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_count_zero_p, dim3((unsigned)std::min<uint64_t>(((uint64_t)n + 255) / 256, 256 * 8)), dim3(256), 0, s, (const uint4 *)d_p, (uint64_t)n,
+                       (unsigned long long *)ctx->probs_res.p);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(res, ctx->probs_res.p, 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    if (res[0]) {
+        ctx->err = "d_p holds " + std::to_string(res[0]) + " zero probabilities, the first at step " + std::to_string(res[1]) + " (the coder needs p in 1 .. 65535)";
+        return W3_E_INVALID;
+    }
+    return W3_OK;
+}
+
+extern "C" int w3_encode_probs_device(w3_ctx *ctx, const uint8_t *d_in, size_t n, size_t block_size, const uint16_t *d_p,
+                                      uint8_t *d_out, size_t out_cap, uint32_t *d_block_lens, uint64_t *d_total, void *stream) {
+    int rc = check_args(ctx, n, block_size);
+    if (rc) return rc;
+    if (n && (!d_out || !d_block_lens)) return W3_E_INVALID;
+    if ((rc = jobs_idle(ctx))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    if (n == 0) {   // (no blocks: a total of 0, as w3_encode_blocks_device gives)
+        ENSURE(ctx, ctx->total, 8);
+        HIPCHK(ctx, hipMemsetAsync(d_total ? (void *)d_total : ctx->total.p, 0, 8, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        return W3_OK;
+    }
+    if ((rc = probs_check(ctx, d_in, n, block_size, d_p, s))) return rc;
+    return encode_core(ctx, ctx->jobs[0], nullptr, d_in, n, block_size, d_out, out_cap, d_block_lens, d_total, stream, d_p);
+}
+
+extern "C" int w3_encode_stats_probs_device(w3_ctx *ctx, const uint8_t *d_in, size_t n, size_t block_size, const uint16_t *d_p,
+                                            uint32_t *d_block_bits, void *stream) {
+    int rc = check_args(ctx, n, block_size);
+    if (rc) return rc;
+    const size_t nb = (n + block_size - 1) / block_size;
+    if (nb == 0) return W3_OK;
+    if (!d_block_bits) return W3_E_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if ((rc = jobs_idle(ctx))) return rc;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    if ((rc = probs_check(ctx, d_in, n, block_size, d_p, s))) return rc;
+    ENSURE(ctx, ctx->lens, nb * 4);
+    if ((rc = encode_core(ctx, ctx->jobs[0], nullptr, d_in, n, block_size, nullptr, 0, (uint32_t *)ctx->lens.p, nullptr, stream, d_p))) return rc;
     HIPCHK(ctx, hipMemcpyAsync(d_block_bits, ctx->jobs[0].bits.p, nb * 4, hipMemcpyDeviceToDevice, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
     return W3_OK;
@@ -3647,6 +3744,183 @@ extern "C" int w3_predict_blocks(w3_ctx *ctx, const w3_model_spec *spec, const u
     d_p = (const uint16_t *)ctx->jobs[0].tp.P;
     HIPCHK(ctx, hipStreamSynchronize(s));
     HIPCHK(ctx, hipMemcpy(p_out, d_p, n * 16, hipMemcpyDeviceToHost));
+    return W3_OK;
+}
+
+// ---------------------------------------------------------------------------
+// per-step statistics export (include/w3hip.h: w3_export_steps_device; csrc/w3_steps.h)
+// ---------------------------------------------------------------------------
+extern "C" int w3_steps_layout_of(const w3_model_spec *spec, uint32_t format, uint32_t flags, w3_steps_layout *out) {
+    if (!out) return W3_E_INVALID;
+    ParsedSpec ps;
+    if (const int rc = parse_spec(spec, ps)) return rc;
+    StepsLayout l;
+    if (!steps_layout((uint32_t)ps.n_leaves, (uint32_t)ps.n_apm, format, flags, l)) return W3_E_INVALID;
+    out->n_cols = l.n_cols; out->n_leaves = l.n_leaves; out->col_mix = l.col_mix; out->col_apm0 = l.col_apm0; out->n_apm = l.n_apm;
+    out->col_final = l.col_final; out->col_bit = l.col_bit; out->elem_bytes = l.elem_bytes;
+    return W3_OK;
+}
+
+template <bool STAGED>
+static void steps_launch(uint32_t C, dim3 grid, uint32_t lds, hipStream_t s, const StepsArgs &a) {
+    switch (C) {   // (the bench model with the bit column has 6 columns, init_model() 3)
+    case 2: hipLaunchKernelGGL((k_steps_rows<2, STAGED>), grid, dim3(64), lds, s, a); break;
+    case 3: hipLaunchKernelGGL((k_steps_rows<3, STAGED>), grid, dim3(64), lds, s, a); break;
+    case 4: hipLaunchKernelGGL((k_steps_rows<4, STAGED>), grid, dim3(64), lds, s, a); break;
+    case 5: hipLaunchKernelGGL((k_steps_rows<5, STAGED>), grid, dim3(64), lds, s, a); break;
+    case 6: hipLaunchKernelGGL((k_steps_rows<6, STAGED>), grid, dim3(64), lds, s, a); break;
+    case 7: hipLaunchKernelGGL((k_steps_rows<7, STAGED>), grid, dim3(64), lds, s, a); break;
+    case 8: hipLaunchKernelGGL((k_steps_rows<8, STAGED>), grid, dim3(64), lds, s, a); break;
+    default: hipLaunchKernelGGL((k_steps_rows<0, STAGED>), grid, dim3(64), lds, s, a); break;
+    }
+}
+
+// The rows of n input bytes (whole blocks but for the last) at d_in into d_rows, on job 0's workspace: the predict phase, the sampled
+// verification of its LDS-add rounds exactly as an encode runs it, the APM stages ONE AT A TIME with a copy of ws.P after each, the row
+// kernel.  Synchronous.  prof: the call's times and counts are ADDED (the staged form sums its pieces).
+static int steps_run(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, const StepsLayout &lay, uint32_t format, const uint8_t *d_in, size_t n,
+                     size_t block_size, void *d_rows, w3_steps_profile &prof) {
+    Job &J = ctx->jobs[0];
+    TwoPhaseWs &ws = J.tp;
+    const uint32_t nb = (uint32_t)((n + block_size - 1) / block_size);
+    int rc;
+    if ((rc = job_prepare(ctx, J, ps, s, true, false, n, block_size, nb))) return rc;
+    if (!ctx->stretch && (rc = stage_cm_luts(ctx, s))) return rc;   // (the formats' table: job_prepare stages it only for models that use it)
+    ws.stretch = ctx->stretch; ws.squash = ctx->squash;
+    int n_live = 0;
+    for (int l = 0; l < ps.n_leaves; l++) n_live += leaf_class(ps.leaf[l]) != LEAF_FROZEN;
+    // ws.P is rewritten by every stage, and by the first one IN PLACE where a single live leaf wrote its stream there: copies
+    const bool leaf_in_P = n_live == 1 && ps.n_apm > 0;
+    const size_t n_copies = (leaf_in_P ? 1 : 0) + (ps.n_apm > 1 ? (size_t)ps.n_apm - 1 : 0);
+    ENSURE(ctx, ctx->steps_copies, n_copies * n * 16);
+    hipEvent_t *ev = ctx->opt_timing ? J.ev : nullptr;
+    uint32_t lds_faults = 0;
+    for (int attempt = 0; attempt < 2; attempt++) {
+        HIPCHK(ctx, hipMemsetAsync(J.flag.p, 0, 4 * ST_WORDS, s));
+        if (ev) HIPCHK(ctx, hipEventRecord(ev[2 * W3_EV_TOTAL], s));
+        if ((rc = twophase_predict(ws, s, ps, d_in, n, block_size, nb, false, nullptr, ev, nullptr, ctx->err))) return rc;
+        // the insurance of every encode (twophase_verify): here always before the first stage, which also covers the single leaf whose
+        // stream that stage rewrites in place
+        if ((rc = twophase_verify(ws, s, ps, d_in, n, block_size, nb, (uint32_t *)J.flag.p + ST_ORDER_FAULT, ctx->err))) return rc;
+        StepsArgs a;
+        memset(&a, 0, sizeof a);
+        uint8_t *copy = (uint8_t *)ctx->steps_copies.p;
+        const auto leaf_streams = ws.mix;   // (twophase_apm replaces ws.mix by its one output stream)
+        for (int l = 0, k = 0; l < ps.n_leaves; l++) {
+            if (leaf_class(ps.leaf[l]) == LEAF_FROZEN) continue;
+            a.leaf[l] = leaf_streams.src[k++];
+            if (leaf_in_P) {
+                HIPCHK(ctx, hipMemcpyAsync(copy, a.leaf[l], n * 16, hipMemcpyDeviceToDevice, s));
+                a.leaf[l] = (const uint4 *)copy; copy += n * 16;
+            }
+        }
+        if (ev) HIPCHK(ctx, hipEventRecord(ev[2 * W3_EV_APM], s));
+        for (int j = 0; j < ps.n_apm; j++) {
+            // the chain's own stream, a stage per call: after the first one ws.P_valid is set and the next stage reads ws.P, as the chain does
+            ParsedSpec one = ps;
+            one.n_apm = 1; one.apm[0] = ps.apm[j];
+            if ((rc = twophase_apm(ws, s, one, d_in, n, block_size, nb, nullptr, nullptr, ctx->err))) return rc;
+            a.apm[j] = (const uint4 *)ws.P;
+            if (j + 1 < ps.n_apm) {
+                HIPCHK(ctx, hipMemcpyAsync(copy, ws.P, n * 16, hipMemcpyDeviceToDevice, s));
+                a.apm[j] = (const uint4 *)copy; copy += n * 16;
+            }
+        }
+        if (ev) HIPCHK(ctx, hipEventRecord(ev[2 * W3_EV_APM + 1], s));
+        a.in = d_in; a.n = n; a.stretch = ctx->stretch; a.rows = (uint4 *)d_rows;
+        a.n_leaves = lay.n_leaves; a.n_apm = lay.n_apm; a.n_cols = lay.n_cols; a.format = format; a.col_bit = lay.col_bit;
+        const dim3 grid(steps_grid(steps_tiles(n), W3_STEPS_GRID_CAP));
+        if (ev) HIPCHK(ctx, hipEventRecord(ev[2 * W3_EV_CODER], s));
+        if (ctx->opt.tune & W3_TUNE_STEPS_DIRECT) steps_launch<false>(lay.n_cols, grid, steps_lds_bytes(lay.n_cols), s, a);
+        else steps_launch<true>(lay.n_cols, grid, steps_lds_bytes(lay.n_cols), s, a);
+        HIPCHK(ctx, hipGetLastError());
+        if (ev) { HIPCHK(ctx, hipEventRecord(ev[2 * W3_EV_CODER + 1], s)); HIPCHK(ctx, hipEventRecord(ev[2 * W3_EV_TOTAL + 1], s)); }
+        JobStatus st{};
+        HIPCHK(ctx, hipMemcpyAsync(st.w, J.flag.p, sizeof st.w, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        if (!st.order_fault()) break;
+        // the LDS-add rounds were not lane-ordered under this load: predict again with the ballot rounds, and stay on them (as encode_core does)
+        if (attempt) { ctx->err = "predict streams differ from their ballot-round re-prediction even without LDS-add rounds (internal error)"; return W3_E_HIP; }
+        lds_faults += st.order_fault();
+        use_ballot_rounds(ctx);
+    }
+    ctx->timing.n_lds_faults += lds_faults;
+    prof.n_lds_faults += lds_faults;
+    prof.bytes_read += (uint64_t)n * (16ull * (n_live + ps.n_apm) + (lay.col_bit != W3_STEPS_NO_COL ? 1 : 0));
+    prof.bytes_written += steps_rows_bytes(n, lay.n_cols);
+    if (ev) {
+        prof.predict_ms += elapsed_ev(ev, W3_EV_PREDICT); prof.rows_ms += elapsed_ev(ev, W3_EV_CODER); prof.total_ms += elapsed_ev(ev, W3_EV_TOTAL);
+        if (ps.n_apm) prof.apm_ms += elapsed_ev(ev, W3_EV_APM);
+    }
+    return W3_OK;
+}
+
+// the checks both forms share, in the order include/w3hip.h gives; *go = there is something to do
+static int steps_args(w3_ctx *ctx, const w3_model_spec *spec, const void *in, size_t n, size_t block_size, uint32_t format, uint32_t flags, const void *rows,
+                      size_t rows_cap, bool one_device, ParsedSpec &ps, StepsLayout &lay, bool *go) {
+    *go = false;
+    int rc = check_args(ctx, n, block_size, one_device);
+    if (rc) return rc;
+    if ((rc = jobs_idle(ctx))) return rc;   // (the predict phase runs on job 0's workspace)
+    if ((rc = parse_spec(spec, ps))) { ctx->err = "malformed model spec"; return rc; }
+    if (!steps_layout((uint32_t)ps.n_leaves, (uint32_t)ps.n_apm, format, flags, lay)) { ctx->err = "unknown W3_STEPS_* format or flag"; return W3_E_INVALID; }
+    memset(&ctx->steps_prof, 0, sizeof ctx->steps_prof);
+    ctx->steps_prof.direct_stores = (ctx->opt.tune & W3_TUNE_STEPS_DIRECT) ? 1u : 0u;
+    if (n == 0) return W3_OK;
+    if (!in || !rows) return W3_E_INVALID;
+    if (((uintptr_t)rows & 15u) != 0) { ctx->err = "rows must be 16-byte aligned"; return W3_E_INVALID; }
+    if (rows_cap < steps_rows_bytes(n, lay.n_cols)) { ctx->err = "rows_cap too small: " + std::to_string(steps_rows_bytes(n, lay.n_cols)) + " bytes needed"; return W3_E_NOSPACE; }
+    if (!twophase_supported(ps, block_size, n)) { ctx->err = "spec not covered by the two-phase predict kernels"; return W3_E_UNSUPPORTED; }
+    memset(&ctx->timing, 0, sizeof ctx->timing);
+    ctx->timing.path = W3_PATH_TWOPHASE; ctx->timing.n_parts = 0;
+    *go = true;
+    return W3_OK;
+}
+
+extern "C" int w3_export_steps_device(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *d_in, size_t n, size_t block_size, uint32_t format,
+                                      uint32_t flags, void *d_rows, size_t rows_cap, void *stream) {
+    ParsedSpec ps;
+    StepsLayout lay;
+    bool go;
+    int rc = steps_args(ctx, spec, d_in, n, block_size, format, flags, d_rows, rows_cap, true, ps, lay, &go);
+    if (rc || !go) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ctx->timing.n_parts = 1;
+    return steps_run(ctx, stream ? (hipStream_t)stream : ctx->stream, ps, lay, format, d_in, n, block_size, d_rows, ctx->steps_prof);
+}
+
+extern "C" int w3_export_steps_staged(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, size_t n, size_t block_size, uint32_t format,
+                                      uint32_t flags, void *rows, size_t rows_cap) {
+    ParsedSpec ps;
+    StepsLayout lay;
+    bool go;
+    int rc = steps_args(ctx, spec, in, n, block_size, format, flags, rows, rows_cap, false, ps, lay, &go);
+    if (rc || !go) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    // pieces of whole blocks; a piece's rows are C x 16 bytes per input byte, so the default piece is 2 GiB of ROWS, not of input
+    const uint64_t auto_blocks = std::max<uint64_t>(1, (1ull << 31) / (16ull * lay.n_cols * block_size));
+    const uint64_t run_blocks = ctx->host_chunk_blocks ? (uint64_t)ctx->host_chunk_blocks : auto_blocks;
+    const size_t piece = (size_t)steps_piece_len(n, block_size, run_blocks, 0);
+    if (piece >= (1ull << 32) - 4096u) { ctx->err = "W3_OPT_HOST_CHUNK_BLOCKS: a piece must stay below 4 GiB of input"; return W3_E_UNSUPPORTED; }
+    if (n % piece && n % piece < 8) { ctx->err = "a last piece below 8 bytes is not covered by the two-phase predict kernels"; return W3_E_UNSUPPORTED; }
+    ENSURE(ctx, ctx->io_in, piece);
+    ENSURE(ctx, ctx->steps_rows, (size_t)steps_rows_bytes(piece, lay.n_cols));
+    VcallPin pin(ctx, verify_call(ctx, n, block_size));   // (one call, one number for the verification's rotation, whatever the pieces)
+    for (size_t o0 = 0; o0 < n;) {
+        const size_t len = (size_t)steps_piece_len(n, block_size, run_blocks, o0);
+        HIPCHK(ctx, hipMemcpyAsync(ctx->io_in.p, in + o0, len, hipMemcpyHostToDevice, s));
+        if ((rc = steps_run(ctx, s, ps, lay, format, (const uint8_t *)ctx->io_in.p, len, block_size, ctx->steps_rows.p, ctx->steps_prof))) return rc;
+        HIPCHK(ctx, hipMemcpy((uint8_t *)rows + steps_rows_bytes(o0, lay.n_cols), ctx->steps_rows.p, (size_t)steps_rows_bytes(len, lay.n_cols), hipMemcpyDeviceToHost));
+        ctx->timing.n_parts++;
+        o0 += len;
+    }
+    return W3_OK;
+}
+
+extern "C" int w3_export_steps_get_profile(const w3_ctx *ctx, w3_steps_profile *out) {
+    if (!ctx || !out) return W3_E_INVALID;
+    *out = ctx->steps_prof;
     return W3_OK;
 }
 
