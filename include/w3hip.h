@@ -69,10 +69,32 @@ enum {
  *                          subtree.  align = context kind (W3_APM_ORDER0: partial byte, 256 rows;
  *                          W3_APM_ORDER1: partial byte | previous byte << 8, 65536 rows),
  *                          max_bits = adaptation rate (1..15).  Only as a chain at the root.
+ *   node  W3_NODE_MIX       : logistic mixer with learned weights (integer-exact, fresh per block): pops the
+ *                          N = bits (2..8) preceding subtrees, each a single leaf (W3_NODE_ORDERN of any history, not frozen, or
+ *                          W3_NODE_SLOT_STATE).  align = weight-set selector (W3_MIX_ONE: one set; W3_MIX_ORDER0: 256 sets, row
+ *                          c0 = the partial byte with its leading 1, as an ORDER0 APM row; row 0 is unused), max_bits = rate
+ *                          (4..20), every other field 0.  State w[S][N] int32, every weight starts at 65536 / N (65536 = 1.0),
+ *                          WMAX = 2^20 - 1.  Per step, with the leaves' p_i before the bit in spec leaf order and the row before the bit:
+ *                              s_i = stretch[p_i >> 4]                     (-2047 .. 2047)
+ *                              dot = sum_i ((w_i * s_i) >> 8)              (int32, arithmetic shifts = floor)
+ *                              d   = clamp(dot >> 8, -2047, 2047),  p = squash[d + 2047]        (the node's output)
+ *                              err = (bit << 16) - p
+ *                              w_i = clamp(w_i + ((s_i * err + (1 << (rate - 1))) >> rate), -WMAX, WMAX)
+ *                          The whole step is 32-bit arithmetic (csrc/w3_mix_plan.h is its one copy).  A spec has at most one MIX
+ *                          node, its N leaves are all the spec's leaves, and only W3_NODE_APM nodes may follow it.  Bad field
+ *                          values or nothing to pop: W3_E_INVALID.  Valid shapes that are not built — a BestOfTwo or frozen leaf
+ *                          under it, leaves beside it, a second MIX, MIX after an APM — W3_E_UNSUPPORTED.  Not exported:
+ *                          w3_export_steps_* and w3_steps_layout_of return W3_E_UNSUPPORTED for a spec with a MIX node.
+ *                          Encode: W3_PATH_TWOPHASE runs the mixer as a stage between the predict kernels and the APM stages
+ *                          (k_lmix, csrc/w3_lmix.h; w3_timing.mix_ms), W3_PATH_GENERIC the lane-per-block kernels, W3_PATH_AUTO the
+ *                          stage only for shapes at which it has been measured to win, else the lane kernels; the
+ *                          streams are the same.  Decode: the lane-per-block kernels.
  */
-enum { W3_NODE_ORDERN = 1, W3_NODE_BEST_OF_TWO = 2, W3_NODE_SLOT_STATE = 3, W3_NODE_APM = 4 };
+enum { W3_NODE_ORDERN = 1, W3_NODE_BEST_OF_TWO = 2, W3_NODE_SLOT_STATE = 3, W3_NODE_APM = 4, W3_NODE_MIX = 5 };
 enum { W3_HIST_NONE = 0, W3_HIST_RAW = 1, W3_HIST_AC = 2, W3_HIST_HUFF = 3 };
 enum { W3_APM_ORDER0 = 0, W3_APM_ORDER1 = 1 };
+enum { W3_MIX_ONE = 0, W3_MIX_ORDER0 = 1 };
+#define W3_MIX_MAX_INPUTS 8
 #define W3_MAX_NODES  31
 #define W3_MAX_LEAVES 16
 #define W3_MAX_APM    4
@@ -739,6 +761,7 @@ typedef struct w3_timing {
     float    part_ms[4];   /* k_partition8 / k_partition pass of wide leaf w */
     float    rank_ms[4];   /* k_rank_sorted of wide leaf w */
     float    small_ms;     /* k_predict_small launches of the time-ordered Counter leaves (H <= 8, raw history), together */
+    float    mix_ms;       /* logistic mixer stage of the two-phase path (k_lmix / k_lmix_one); 0 for specs without a W3_NODE_MIX */
 } w3_timing;
 int w3_get_timing(const w3_ctx *ctx, w3_timing *out);
 

@@ -45,6 +45,8 @@ static void push(w3_model_spec &s, uint8_t kind, uint8_t bits = 0, uint8_t align
 //   order012          : the commented alternative of main.rs:148-150 in today's types, BestOfTwo(BestOfTwo(Order0, Order1), OrderN(27,3))
 //   order012apm       : + one APM stage (BASELINE configs[1]; build-defined)
 //   fullcm            : + slot-state leaves of order 1-4 and two APM stages (BASELINE configs[2])
+//   order012mix       : order012's three leaves under the logistic mixer (W3_NODE_MIX, ORDER0 weight sets, rate 14) instead of the tree
+//   fullcmmix         : fullcm's seven leaves under the logistic mixer, its two APM stages behind it
 static w3_model_spec init_model() {
     w3_model_spec s;
     memset(&s, 0, sizeof s);
@@ -56,6 +58,14 @@ static w3_model_spec init_model() {
         s.nodes[0].history = W3_HIST_AC;
         const uint16_t book1[8] = {1, 50188, 62497, 15819, 22545, 31499, 22988, 29616};  // stationary.rs:41
         memcpy(s.nodes[0].table, book1, sizeof book1);
+        return s;
+    }
+    if (name == "order012mix" || name == "fullcmmix") {
+        push(s, W3_NODE_ORDERN, 11, 3); push(s, W3_NODE_ORDERN, 19, 3); push(s, W3_NODE_ORDERN, 27, 3);
+        if (name == "fullcmmix")
+            for (uint8_t order = 1; order <= 4; order++) push(s, W3_NODE_SLOT_STATE, order, 0, 0, 14);
+        push(s, W3_NODE_MIX, (uint8_t)s.n_nodes, W3_MIX_ORDER0, 14);
+        if (name == "fullcmmix") { push(s, W3_NODE_APM, 0, W3_APM_ORDER0, 7); push(s, W3_NODE_APM, 0, W3_APM_ORDER1, 6); }
         return s;
     }
     if (name != "order012" && name != "order012apm" && name != "fullcm") { fprintf(stderr, "unknown W3_MODEL %s\n", name.c_str()); exit(1); }

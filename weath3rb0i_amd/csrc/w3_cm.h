@@ -11,6 +11,7 @@
 // reference has the primitives but no model that uses them.  Definitions: DESIGN.md §2.4.
 #pragma once
 #include "w3_generic.h"
+#include "w3_mix_plan.h"
 #include "w3_tables.h"
 
 namespace w3 {
@@ -22,10 +23,20 @@ struct ApmParam {
     uint64_t off;        // byte offset of this stage's u16[rows][33] table inside the lane's region
 };
 
+// Logistic mixer over the leaves (W3_NODE_MIX; the step: w3_mix_plan.h): n = 0 when the spec has none.
+struct MixParam {
+    uint8_t  n;          // inputs = the spec's leaves
+    uint8_t  select;     // MIX_ONE / MIX_ORDER0
+    uint8_t  rate;
+    uint8_t  pad[5];
+    uint64_t off;        // byte offset of the int32[sets][n] weights inside the lane's region
+};
+
 struct CmArgs {
     GenericArgs g;
     int n_apm;
     ApmParam apm[W3_MAX_APM];
+    MixParam mix;
     const uint2   *st;        // [kStSize] {prob | next0 << 16, next1 | conf << 16}
     const int16_t *stretch;   // [4096]
     const uint16_t *squash;   // [4095] (APM table initialisation only)
@@ -116,11 +127,27 @@ __global__ void __launch_bounds__(256) k_cm_init_apm(uint8_t *tables, uint64_t l
     }
 }
 
-template <bool DECODE>
+// every lane's mixer weights start at 65536 / n: cnt int32 words per lane
+__global__ void __launch_bounds__(256) k_cm_init_mix(uint8_t *tables, uint64_t lane_stride, uint64_t off, uint32_t cnt, uint32_t n_lanes, int32_t w0) {
+    const uint64_t total = (uint64_t)cnt * n_lanes;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t lane = i / cnt;
+        reinterpret_cast<int32_t *>(tables + lane * lane_stride + off)[i - lane * cnt] = w0;
+    }
+}
+
+// MIX: the leaves feed a logistic mixer (a.mix) instead of the BestOfTwo tree; its squash table is staged in LDS beside the others.
+template <bool DECODE, bool MIX = false>
 __global__ void __launch_bounds__(64) k_cm(CmArgs a) {
     __shared__ uint2   s_st[kStSize];
     __shared__ int16_t s_str[4096];
     for (uint32_t i = threadIdx.x; i < (uint32_t)kStSize; i += 64u) s_st[i] = a.st[i];
+    const uint16_t *s_sq = nullptr;
+    if constexpr (MIX) {
+        __shared__ uint16_t s_squash[4096];
+        for (uint32_t i = threadIdx.x; i < 4095u; i += 64u) s_squash[i] = a.squash[i];
+        s_sq = s_squash;
+    }
     for (uint32_t i = threadIdx.x; i < 4096u; i += 64u) s_str[i] = a.stretch[i];
     __shared__ LeafParam s_leaf[W3_MAX_LEAVES];
     __shared__ ApmParam s_apm[W3_MAX_APM];
@@ -159,6 +186,7 @@ __global__ void __launch_bounds__(64) k_cm(CmArgs a) {
             // predict: leftmost leaf of maximal |p - 1/2| (BestOfTwo tree, models/mod.rs:67-69)
             uint32_t p = 32768u, best = 0u; bool first = true;
             uint32_t *cslot[W3_MAX_LEAVES]; uint32_t st[W3_MAX_LEAVES];
+            int32_t ms[MIX ? W3_MAX_LEAVES : 1];   // MIX: stretch of every leaf's p
             for (int l = 0; l < g.n_leaves; l++) {
                 const LeafParam &lp = s_leaf[l];
                 uint32_t pl = 32768u;
@@ -172,6 +200,16 @@ __global__ void __launch_bounds__(64) k_cm(CmArgs a) {
                 }
                 const uint32_t d = opinion_dist(pl);
                 if (first || d > best) { p = pl; best = d; first = false; }
+                if constexpr (MIX) ms[l] = s_str[pl >> 4];
+            }
+            // logistic mixer over the leaves (w3_mix_plan.h): the weight set of the row, read before the bit
+            int32_t *mw = nullptr; int32_t mp = 0;
+            if constexpr (MIX) {
+                mw = reinterpret_cast<int32_t *>(lane_tbl + a.mix.off) + mix_row(a.mix.select, c0) * a.mix.n;
+                int32_t dot = 0;
+                for (int l = 0; l < g.n_leaves; l++) dot += mix_term(mw[l], ms[l]);
+                mp = (int32_t)s_sq[mix_d(dot) + 2047];
+                p = (uint32_t)mp;
             }
             // APM chain (build-defined): refine p through each stage
             uint16_t *aslot[W3_MAX_APM];
@@ -189,6 +227,10 @@ __global__ void __launch_bounds__(64) k_cm(CmArgs a) {
             if (DECODE) { bit = dec.decode(p); byte = (byte << 1) | bit; }
             else bit = (byte >> s) & 1u;
             // Model::update = adapt (train the current context) then advance  models/mod.rs:28-31
+            if constexpr (MIX) {
+                const int32_t err = mix_err(bit, mp);
+                for (int l = 0; l < g.n_leaves; l++) mw[l] = mix_update(mw[l], ms[l], err, a.mix.rate);
+            }
             for (int k = 0; k < a.n_apm; k++) {
                 const int tv = (int)*aslot[k];
                 *aslot[k] = (uint16_t)(tv + (((bit ? 65535 : 0) - tv) >> s_apm[k].rate));   // arithmetic shift = floor
@@ -293,12 +335,18 @@ __device__ __forceinline__ uint32_t cmc_select(cm_lds_u32 *cb, uint32_t tag, con
     return (uint32_t)id;
 }
 
-template <bool DECODE>
+template <bool DECODE, bool MIX = false>
 __global__ void __launch_bounds__(64) k_cm_staged(CmArgs a) {
     __shared__ uint2   s_st[kStSize];
     __shared__ int16_t s_str[4096];
     __shared__ cm_u32x4 s_cell[W3_CM_STAGED_MAX][6][64];
     for (uint32_t i = threadIdx.x; i < (uint32_t)kStSize; i += 64u) s_st[i] = a.st[i];
+    const uint16_t *s_sq = nullptr;
+    if constexpr (MIX) {
+        __shared__ uint16_t s_squash[4096];
+        for (uint32_t i = threadIdx.x; i < 4095u; i += 64u) s_squash[i] = a.squash[i];
+        s_sq = s_squash;
+    }
     for (uint32_t i = threadIdx.x; i < 4096u; i += 64u) s_str[i] = a.stretch[i];
     __shared__ LeafParam s_leaf[W3_MAX_LEAVES];
     __shared__ ApmParam s_apm[W3_MAX_APM];
@@ -358,6 +406,7 @@ __global__ void __launch_bounds__(64) k_cm_staged(CmArgs a) {
             // predict: leftmost leaf of maximal |p - 1/2| (BestOfTwo tree, models/mod.rs:67-69)
             uint32_t p = 32768u, best = 0u; bool first = true;
             uint32_t *cslot[W3_MAX_LEAVES]; uint32_t st[W3_MAX_LEAVES];
+            int32_t ms[MIX ? W3_MAX_LEAVES : 1];   // MIX: stretch of every leaf's p
             for (int l = 0; l < g.n_leaves; l++) {
                 const LeafParam &lp = s_leaf[l];
                 uint32_t pl = 32768u;
@@ -373,6 +422,16 @@ __global__ void __launch_bounds__(64) k_cm_staged(CmArgs a) {
                 }
                 const uint32_t d = opinion_dist(pl);
                 if (first || d > best) { p = pl; best = d; first = false; }
+                if constexpr (MIX) ms[l] = s_str[pl >> 4];
+            }
+            // logistic mixer over the leaves (w3_mix_plan.h): the weight set of the row, read before the bit
+            int32_t *mw = nullptr; int32_t mp = 0;
+            if constexpr (MIX) {
+                mw = reinterpret_cast<int32_t *>(lane_tbl + a.mix.off) + mix_row(a.mix.select, c0) * a.mix.n;
+                int32_t dot = 0;
+                for (int l = 0; l < g.n_leaves; l++) dot += mix_term(mw[l], ms[l]);
+                mp = (int32_t)s_sq[mix_d(dot) + 2047];
+                p = (uint32_t)mp;
             }
             // APM chain (build-defined): refine p through each stage
             uint16_t *aslot[W3_MAX_APM];
@@ -390,6 +449,10 @@ __global__ void __launch_bounds__(64) k_cm_staged(CmArgs a) {
             if (DECODE) { bit = dec.decode(p); byte = (byte << 1) | bit; }
             else bit = (byte >> s) & 1u;
             // Model::update = adapt (train the current context) then advance  models/mod.rs:28-31
+            if constexpr (MIX) {
+                const int32_t err = mix_err(bit, mp);
+                for (int l = 0; l < g.n_leaves; l++) mw[l] = mix_update(mw[l], ms[l], err, a.mix.rate);
+            }
             for (int k = 0; k < a.n_apm; k++) {
                 const int tv = (int)*aslot[k];
                 *aslot[k] = (uint16_t)(tv + (((bit ? 65535 : 0) - tv) >> s_apm[k].rate));   // arithmetic shift = floor

@@ -430,6 +430,7 @@ static inline bool decode_spec_has_slot(const CmArgs &ca) {
 }
 static inline bool decode_spec_covers(const CmArgs &ca) {
     if (ca.g.n_leaves < 1 || ca.g.n_leaves > 8 || ca.n_apm > 2) return false;
+    if (ca.mix.n) return false;   // a logistic mixer over the leaves: the lane kernels decode it (w3_cm.h)
     for (int l = 0; l < ca.g.n_leaves; l++) {
         const LeafParam &lp = ca.g.leaf[l];
         if (lp.kind == 0 && !lp.frozen && lp.align < 2) return false;

@@ -1,5 +1,6 @@
 // w3_twophase.h — host orchestration of the two-phase encoder:
 //   predict (w3_predict.h): all leaves' Counter probabilities for every step, merged into P
+//   mix     (w3_lmix.h)   : specs with a logistic mixer node — the leaves' streams through the learned weights into P
 //   code    (w3_coder.h)  : lane-per-block arithmetic coder over P
 // Covered specs: every leaf is FrozenModel, or has alignment_bits == 3 and
 //   H = bits-3 <= 8 (any history), or H in {16, 24} with raw history.
@@ -17,6 +18,7 @@
 #include "w3_coder.h"
 #include "w3_coder4.h"
 #include "w3_coder5.h"
+#include "w3_lmix.h"
 #include "w3_predict.h"
 #include "w3_predict_wave.h"
 #include "w3_slot.h"
@@ -49,8 +51,8 @@ enum { W3_VAR_NO_LDS_ATOMICS = 1, W3_VAR_PARTITION4 = 2, W3_VAR_NO_CHAINED_PARTI
 
 // event slots (pairs: ev[2 * slot], ev[2 * slot + 1]) of one encode
 enum { W3_EV_PREDICT = 0, W3_EV_CODER = 1, W3_EV_PACK = 2, W3_EV_TOTAL = 3, W3_EV_APM = 4, W3_EV_SLOT = 5, W3_EV_ACHASH = 6,
-       W3_EV_PART0 = 7 /* .. 10: partition pass of wide leaf w */, W3_EV_RANK0 = 11 /* .. 14: rank kernel of wide leaf w */, W3_EV_SMALL = 15,
-       W3_EV_SLOTS = 16 };
+       W3_EV_PART0 = 7 /* .. 10: partition pass of wide leaf w */, W3_EV_RANK0 = 11 /* .. 14: rank kernel of wide leaf w */, W3_EV_SMALL = 15, W3_EV_MIX = 16,
+       W3_EV_SLOTS = 17 };
 #define W3_NEV (2 * W3_EV_SLOTS)
 
 // What w3_ctx_set_option sets for the two-phase path.  The context owns the block; a workspace takes a copy when a call is prepared.
@@ -703,7 +705,7 @@ static inline int twophase_predict_b(TwoPhaseWs &ws, hipStream_t s, const Parsed
     }
     if (n_live >= 1) ma.n_src = n_live;
     if (n_live == 1) ws.P_valid = true;   // the single leaf wrote ws.P itself
-    if (need_P && !ws.P_valid) {
+    if (need_P && !ws.P_valid && !ps.has_mix) {   // (a mixer node's P is the mixer stage's, never OpinionMixer2's: twophase_lmix)
         if ((rc = twophase_mix(ws, s, n, err))) return rc;
         bytes += n * 16 * (n_live + 1);
     }
@@ -772,6 +774,37 @@ static inline int twophase_verify(TwoPhaseWs &ws, hipStream_t s, const ParsedSpe
                            ws.mix.src[map[k]], v.mix.src[k], (uint64_t)n, (uint32_t)block_size, nb, S, rot, d_mismatch);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { err = std::string("verify launch: ") + hipGetErrorString(e); return W3_E_HIP; }
+    return W3_OK;
+}
+
+// Logistic mixer node (w3_lmix.h): turns the N leaves' streams into the stream ws.P and leaves it as the one source, exactly as
+// twophase_apm does — the APM stages then run in their "behind a stage" forms, the coders see one source, and twophase_mix (the
+// recode path, the more-than-8-sources fallback) finds P valid and never merges such a spec's leaves OpinionMixer2-wise.
+static inline int twophase_lmix(TwoPhaseWs &ws, hipStream_t s, const ParsedSpec &ps, const uint8_t *d_in, size_t n, size_t block_size,
+                                uint32_t nb, hipEvent_t *ev, w3_timing *tm, std::string &err) {
+    if (!ps.has_mix) return W3_OK;
+    if (!ws.stretch || !ws.squash) { err = "mixer LUTs not staged"; return W3_E_HIP; }
+    const int N = ps.mix.bits;
+    if (ws.P_valid || ws.mix.n_src != N || N > (int)w3::MIX_MAX_INPUTS) { err = "mixer stage: the predict phase left " + std::to_string(ws.mix.n_src) + " streams for " + std::to_string(N) + " inputs (internal error)"; return W3_E_HIP; }
+    int rc = tp_ensure(ws.P, ws.P_cap, n * 16, err);
+    if (rc) return rc;
+    w3::LmixArgs la;
+    memset(&la, 0, sizeof la);
+    la.in = d_in; la.n = n; la.block_size = (uint32_t)block_size; la.nblocks = nb;
+    for (int l = 0; l < N; l++) {
+        la.src[l] = (const uint16_t *)ws.mix.src[l];
+        if ((const void *)la.src[l] == ws.P) { err = "mixer stage: a leaf stream aliases the output stream (internal error)"; return W3_E_HIP; }
+    }
+    la.P = (uint16_t *)ws.P; la.stretch = ws.stretch; la.squash = ws.squash; la.rate = ps.mix.max_bits;
+    if (ev) (void)hipEventRecord(ev[2 * W3_EV_MIX], s);
+    w3::lmix_launch(la, N, ps.mix.align, s);
+    if (ev) (void)hipEventRecord(ev[2 * W3_EV_MIX + 1], s);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { err = std::string("mixer launch: ") + hipGetErrorString(e); return W3_E_HIP; }
+    memset(&ws.mix, 0, sizeof ws.mix);
+    ws.mix.src[0] = (const uint4 *)ws.P; ws.mix.n_src = 1; ws.mix.P = (uint4 *)ws.P; ws.mix.n = n;
+    ws.P_valid = true;
+    if (tm) tm->predict_bytes += (uint64_t)n * (16ull * N + 1 + 16);
     return W3_OK;
 }
 
@@ -857,7 +890,7 @@ static inline int twophase_apm(TwoPhaseWs &ws, hipStream_t s, const ParsedSpec &
 // The encode in three pieces, so that w3_encode_submit can interleave two calls:
 //   twophase_predict (a + b)   on the predict stream
 //   tp_after_predict           verification of a single-leaf APM spec in place; records "predict phase through"
-//   tp_code_stage              APM stages, sampled verification (forked), coder — on the code stream
+//   tp_code_stage              mixer stage, APM stages, sampled verification (forked), coder — on the code stream
 // twophase_encode below is the three in sequence (one stream for both = one call at a time, phases strictly in order).
 struct TpPlan { int n_live, coder; bool x3, need_P, verify_on, verify_in_place; };
 static inline TpPlan tp_plan(const TwoPhaseWs &ws, const ParsedSpec &ps) {
@@ -865,8 +898,8 @@ static inline TpPlan tp_plan(const TwoPhaseWs &ws, const ParsedSpec &ps) {
     p.n_live = 0;
     for (int l = 0; l < ps.n_leaves; l++) p.n_live += leaf_class(ps.leaf[l]) != LEAF_FROZEN;
     p.coder = ws.half_cu && ws.opt.coder_mode == 0 ? 5 : ws.opt.coder_mode;   // half-CU shapes: k_coder_x5 in k_coder_x4's place
-    p.x3 = (p.coder == 0 || p.coder == 4 || p.coder == 5) && (p.n_live <= 4 || ps.n_apm > 0);   // more leaves: merge with k_mix first, then k_coder_x2
-    p.need_P = !p.x3 && ps.n_apm == 0;
+    p.x3 = (p.coder == 0 || p.coder == 4 || p.coder == 5) && (p.n_live <= 4 || ps.n_apm > 0 || ps.has_mix);   // more leaves: merge with k_mix first, then k_coder_x2
+    p.need_P = !p.x3 && ps.n_apm == 0 && !ps.has_mix;   // (a mixer stage, like an APM stage, leaves ws.P as the one source)
     p.verify_on = false; p.verify_in_place = false;
     return p;
 }
@@ -981,6 +1014,7 @@ static inline int tp_code_stage(TwoPhaseWs &ws, hipStream_t s_pred, hipStream_t 
         verify_forked = true;
         return vr;
     };
+    if ((rc = twophase_lmix(ws, s, ps, d_in, n, block_size, nb, ev, tm, err))) return rc;   // (specs with a mixer node) leaves ws.P as the one source stream
     if ((rc = twophase_apm(ws, s, ps, d_in, n, block_size, nb, ev, tm, err))) return rc;   // leaves ws.P as the one source stream
     if (rec_after_apm) (void)hipEventRecord(rec_after_apm, s);
     if (verify_on && !verify_in_place && (rc = fork_verify(s))) return rc;

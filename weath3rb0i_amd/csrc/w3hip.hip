@@ -395,6 +395,7 @@ static int parse_spec(const w3_model_spec *spec, ParsedSpec &ps) {
     if (!spec || spec->n_nodes == 0 || spec->n_nodes > W3_MAX_NODES) return W3_E_INVALID;
     if (spec->n_huff > W3_MAX_HUFF || (spec->n_huff && !spec->huff)) return W3_E_INVALID;   // (the spec must be zero-initialised: w3hip.h)
     int depth = 0;
+    bool plain_leaves = true;   // every subtree on the stack is a single adaptive leaf (what a W3_NODE_MIX can pop)
     uint32_t huff_used = 0;   // table sets some W3_HIST_HUFF leaf refers to: only those are read
     ps = ParsedSpec();
     for (uint32_t i = 0; i < spec->n_nodes; i++) {
@@ -407,7 +408,19 @@ static int parse_spec(const w3_model_spec *spec, ParsedSpec &ps) {
             ps.apm[ps.n_apm++] = nd;
             continue;
         }
-        if (ps.n_apm) return nd.kind == W3_NODE_ORDERN || nd.kind == W3_NODE_SLOT_STATE || nd.kind == W3_NODE_BEST_OF_TWO ? W3_E_UNSUPPORTED : W3_E_INVALID;
+        if (nd.kind == W3_NODE_MIX) {
+            // logistic mixer over the N preceding single leaves (include/w3hip.h): the one mixer of the spec, over all its leaves
+            if (!mix_params_ok(nd.bits, nd.align, nd.max_bits) || nd.history || nd.frozen || nd.log_cells || nd.reserved) return W3_E_INVALID;
+            for (int k = 0; k < 8; k++)
+                if (nd.table[k]) return W3_E_INVALID;
+            if (ps.has_mix || ps.n_apm) return W3_E_UNSUPPORTED;   // a second mixer, a mixer behind an APM stage: valid, not built
+            if (depth < (int)nd.bits) return W3_E_INVALID;
+            if (!plain_leaves || depth != (int)nd.bits) return W3_E_UNSUPPORTED;   // BestOfTwo / frozen leaves under it, leaves beside it
+            ps.has_mix = true; ps.mix = nd;
+            depth = 1;
+            continue;
+        }
+        if (ps.n_apm || ps.has_mix) return nd.kind == W3_NODE_ORDERN || nd.kind == W3_NODE_SLOT_STATE || nd.kind == W3_NODE_BEST_OF_TWO ? W3_E_UNSUPPORTED : W3_E_INVALID;
         if (nd.kind == W3_NODE_ORDERN) {
             // OrderN::new allocates 1<<bits counters; masks are u32/u8 (ordern.rs:35-43)
             if (nd.bits < 1 || nd.bits > 32 || nd.align > 7 || nd.align > nd.bits) return W3_E_INVALID;
@@ -420,6 +433,7 @@ static int parse_spec(const w3_model_spec *spec, ParsedSpec &ps) {
             }
             if (ps.n_leaves == W3_MAX_LEAVES) return W3_E_UNSUPPORTED;
             ps.leaf[ps.n_leaves++] = nd;
+            plain_leaves &= !nd.frozen;
             depth++;
         } else if (nd.kind == W3_NODE_SLOT_STATE) {
             if (nd.bits > 7 || nd.log_cells < 1 || nd.log_cells > 24 || nd.frozen) return W3_E_INVALID;
@@ -429,6 +443,7 @@ static int parse_spec(const w3_model_spec *spec, ParsedSpec &ps) {
             depth++;
         } else if (nd.kind == W3_NODE_BEST_OF_TWO) {
             if (depth < 2) return W3_E_INVALID;
+            plain_leaves = false;
             depth--;
         } else {
             return W3_E_INVALID;
@@ -603,7 +618,7 @@ static int cm_luts(w3_ctx *ctx, hipStream_t s, CmArgs &ca) {
 }
 
 // The per-lane table region: the Counter tables and slot-leaf hash maps (layout_generic), then, for specs with APM stages or slot
-// leaves, rounded up to 16 bytes, the APM tables.  Returns the lane stride.
+// leaves, rounded up to 16 bytes, the APM tables and the logistic mixer's weights.  Returns the lane stride.
 static uint64_t layout_lane(const ParsedSpec &ps, size_t block_size, CmArgs &ca) {
     uint64_t off = layout_generic(ps, block_size, ca.g);
     if (!ps.is_cm()) return off;
@@ -615,6 +630,11 @@ static uint64_t layout_lane(const ParsedSpec &ps, size_t block_size, CmArgs &ca)
         ca.apm[k].off = off;
         // (272 rows per page of 256: k_decode_spec keeps the table nibble-major, 17 groups of 16 node columns — w3_decode_spec.h)
         off += ((ps.apm[k].align == W3_APM_ORDER1 ? 256ull : 1ull) * 272 * 33 * 2 + 15) / 16 * 16;
+    }
+    if (ps.has_mix) {   // the mixer's weights int32[S][N], behind the APM tables
+        ca.mix.n = ps.mix.bits; ca.mix.select = ps.mix.align; ca.mix.rate = ps.mix.max_bits;
+        ca.mix.off = off;
+        off += ((uint64_t)mix_sets(ps.mix.align) * ps.mix.bits * 4 + 15) / 16 * 16;
     }
     return off;
 }
@@ -631,6 +651,11 @@ static void lane_launch(const CmArgs &ca, uint32_t cnt, hipStream_t s, bool unst
     const int nl = ca.g.n_leaves;
     int n_slot = 0;
     for (int l = 0; l < nl; l++) n_slot += ca.g.leaf[l].kind == 1;
+    if (ca.mix.n) {   // a logistic mixer over the leaves: the run-time leaf loops, by the same staged rule (never k_cm_nl / k_generic*)
+        void (*const staged)(CmArgs) = k_cm_staged<DECODE, true>, (*const plain)(CmArgs) = k_cm<DECODE, true>;
+        hipLaunchKernelGGL(n_slot <= W3_CM_STAGED_MAX && !unstaged ? staged : plain, grid, blk, 0, s, ca);
+        return;
+    }
     const bool batch = !n_slot && nl >= 1 && nl <= 4;
     if (!n_slot && !ca.n_apm) hipLaunchKernelGGL(batch ? plain_nl[nl - 1] : k_generic<DECODE>, grid, blk, 0, s, ca.g);
     else hipLaunchKernelGGL(batch ? cm_nl[nl - 1] : n_slot <= W3_CM_STAGED_MAX && !unstaged ? k_cm_staged<DECODE> : k_cm<DECODE>, grid, blk, 0, s, ca);
@@ -679,6 +704,9 @@ static int lane_run(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, size_t blo
         for (int k = 0; k < ca.n_apm; k++)
             hipLaunchKernelGGL(k_cm_init_apm, dim3(2048), dim3(256), 0, s, g.tables, lane_stride, ca.apm[k].off,
                                nm_tables ? (ca.apm[k].ctx_kind ? 256u * 272u : 272u) : (ca.apm[k].ctx_kind ? 65536u : 256u), cnt, ca.squash, nm_tables ? 1u : 0u);
+        if (ca.mix.n)
+            hipLaunchKernelGGL(k_cm_init_mix, dim3(std::min<uint32_t>(2048u, (uint32_t)(((uint64_t)cnt * mix_sets(ca.mix.select) * ca.mix.n + 255) / 256))), dim3(256), 0, s,
+                               g.tables, lane_stride, ca.mix.off, mix_sets(ca.mix.select) * ca.mix.n, cnt, mix_w_init(ca.mix.n));
         if (spec_dec) launch_decode_spec(ca, cnt, s, decode_group_bits(ctx));
         else lane_launch<DECODE>(ca, cnt, s, (ctx->opt.variant & W3_VAR_CM_UNSTAGED) != 0);
         HIPCHK(ctx, hipGetLastError());
@@ -689,6 +717,15 @@ static int lane_run(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, size_t blo
 // ---------------------------------------------------------------------------
 // encode (device-resident)
 // ---------------------------------------------------------------------------
+// Does an encode of this spec and shape take the two-phase path?  W3_PATH_GENERIC never, W3_PATH_TWOPHASE wherever the predict kernels
+// cover the spec, W3_PATH_AUTO likewise — but for a spec with a logistic mixer node only where the mixer stage has been measured to beat
+// the lane kernel (lmix_auto_twophase, w3_lmix.h).
+static bool takes_twophase(const w3_ctx *ctx, const ParsedSpec &ps, size_t block_size, size_t n) {
+    if (ctx->opt_path == W3_PATH_GENERIC || !twophase_supported(ps, block_size, n)) return false;
+    if (ps.has_mix && ctx->opt_path == W3_PATH_AUTO) return lmix_auto_twophase((n + block_size - 1) / block_size, block_size);
+    return true;
+}
+
 static uint32_t default_stripe_cap(size_t block_size) {
     // realistic bound 2N+64 (adaptive Counter regret is small); the exact bound 16N+8 is the retry size
     uint64_t c = 2 * (uint64_t)block_size + 64;
@@ -716,9 +753,10 @@ static float elapsed_ev(hipEvent_t *ev, int slot) {
 }
 
 // per-kernel launch times of one two-phase encode from its events (W3_OPT_TIMING)
-static void collect_timing(hipEvent_t *ev, const TwoPhaseWs &ws, bool has_apm, bool has_slot, bool packed, w3_timing &t) {
+static void collect_timing(hipEvent_t *ev, const TwoPhaseWs &ws, bool has_apm, bool has_slot, bool has_mix, bool packed, w3_timing &t) {
     t.predict_ms = elapsed_ev(ev, W3_EV_PREDICT); t.coder_ms = elapsed_ev(ev, W3_EV_CODER);
     if (has_apm) t.apm_ms = elapsed_ev(ev, W3_EV_APM);
+    if (has_mix) t.mix_ms = elapsed_ev(ev, W3_EV_MIX);
     if (has_slot) t.slot_ms = elapsed_ev(ev, W3_EV_SLOT);
     if (ws.achash_timed) t.achash_ms = elapsed_ev(ev, W3_EV_ACHASH);
     t.n_wide = (uint32_t)std::min(ws.n_wide, 4);
@@ -810,7 +848,7 @@ static void fill_timing(w3_ctx *ctx, Job &J, const w3_timing &ptm, uint64_t tota
     ctx->timing.coder_bytes = ptm.coder_bytes + total; ctx->timing.predict_bytes = ptm.predict_bytes;
     ctx->timing.n_coder_launches = ptm.n_coder_launches; ctx->timing.n_slot_launches = ptm.n_slot_launches;
     ctx->timing.n_parts = 1;
-    if (timed) collect_timing(J.ev, J.tp, ps.n_apm > 0, ps.has_slot, packed, ctx->timing);
+    if (timed) collect_timing(J.ev, J.tp, ps.n_apm > 0, ps.has_slot, ps.has_mix, packed, ctx->timing);
 }
 
 // The attempts of one synchronous encode on job J (encode_core's, for a model's streams and for a caller's alike: the attempt is what
@@ -887,7 +925,7 @@ static int encode_core(w3_ctx *ctx, Job &J, const w3_model_spec *spec, const uin
         return W3_OK;
     }
     if (!d_in || !d_block_lens) return W3_E_INVALID;
-    const bool two = d_p || (twophase_supported(ps, block_size, n) && ctx->opt_path != W3_PATH_GENERIC);   // Counter and slot-state leaves + APM chain (decode: k_generic / k_cm)
+    const bool two = d_p || takes_twophase(ctx, ps, block_size, n);   // Counter and slot-state leaves + APM chain (decode: k_generic / k_cm)
     if (ctx->opt_path == W3_PATH_TWOPHASE && !two) { ctx->err = "spec/block size not covered by the two-phase path"; return W3_E_UNSUPPORTED; }
     if (!two && J.index) { ctx->err = "internal: the lane-per-block path runs on job 0"; return W3_E_INVALID; }
     if ((rc = job_prepare(ctx, J, ps, s, two, (ctx->opt.variant & W3_VAR_HALF_CU) != 0, n, block_size, nb))) return rc;
@@ -986,7 +1024,7 @@ static PipelinePlan pipeline_plan(const ParsedSpec &ps, size_t nb, uint32_t tune
 // Does w3_encode_submit only enqueue this call (true), or run it to completion inside the call (false: specs outside the predict kernels,
 // and specs whose slot-state leaves walk hash maps in HBM)?
 static bool submit_pipelines(const w3_ctx *ctx, const ParsedSpec &ps, uint32_t nb, size_t block_size, size_t n) {
-    const bool two = nb > 0 && twophase_supported(ps, block_size, n) && ctx->opt_path != W3_PATH_GENERIC;
+    const bool two = nb > 0 && takes_twophase(ctx, ps, block_size, n);
     // Specs with slot-state leaves are pipelined when the leaves run as the sorted replay (w3_slot2.h: no hash maps sized from the memory
     // that happens to be free) — two jobs at most: a job's event records are 32 bytes per input byte and leaf.
     const bool slot_async = ps.has_slot && slot_sorted_by_default(ps, nb, block_size, n) && !(ctx->opt.variant & (W3_VAR_SLOT_TABLE | W3_VAR_NO_LDS_ATOMICS)) && ctx->lds_order != 0;
@@ -1072,7 +1110,7 @@ extern "C" int w3_encode_submit(w3_ctx *ctx, const w3_model_spec *spec, const ui
             HIPCHK(ctx, hipEventSynchronize(O.ev_done));
             if (O.index == 0 && O.timed && !O.tm_snap) {   // job 0's events are about to be recorded again
                 memset(&O.tm_ev, 0, sizeof O.tm_ev);
-                collect_timing(O.ev, O.tp, O.call.ps.n_apm > 0, O.call.ps.has_slot, true, O.tm_ev);
+                collect_timing(O.ev, O.tp, O.call.ps.n_apm > 0, O.call.ps.has_slot, O.call.ps.has_mix, true, O.tm_ev);
                 O.tm_snap = true;
             }
         }
@@ -1622,7 +1660,7 @@ static size_t host_chunk_blocks(const w3_ctx *ctx, const ParsedSpec &ps, size_t 
 // one more piece's timing into a call's sums (n_parts counts the pieces; path and n_wide are the last piece's)
 static void timing_add(w3_timing &sum, const w3_timing &t) {
     sum.predict_ms += t.predict_ms; sum.coder_ms += t.coder_ms; sum.pack_ms += t.pack_ms; sum.generic_ms += t.generic_ms; sum.total_ms += t.total_ms;
-    sum.apm_ms += t.apm_ms; sum.slot_ms += t.slot_ms; sum.achash_ms += t.achash_ms; sum.small_ms += t.small_ms;
+    sum.apm_ms += t.apm_ms; sum.slot_ms += t.slot_ms; sum.achash_ms += t.achash_ms; sum.small_ms += t.small_ms; sum.mix_ms += t.mix_ms;
     for (int w = 0; w < 4; w++) { sum.part_ms[w] += t.part_ms[w]; sum.rank_ms[w] += t.rank_ms[w]; }
     sum.path = t.path; sum.n_wide = t.n_wide; sum.n_parts += 1;
     sum.n_coder_launches += t.n_coder_launches; sum.coder_bytes += t.coder_bytes; sum.predict_bytes += t.predict_bytes;
@@ -3738,8 +3776,9 @@ extern "C" int w3_predict_blocks(w3_ctx *ctx, const w3_model_spec *spec, const u
     HIPCHK(ctx, hipMemcpyAsync(ctx->io_in.p, in, n, hipMemcpyHostToDevice, s));
     const uint16_t *d_p = nullptr;
     if ((rc = attach_aux_streams(ctx, ctx->jobs[0]))) return rc;
-    rc = twophase_predict(ctx->jobs[0].tp, s, ps, (const uint8_t *)ctx->io_in.p, n, block_size, nb, ps.n_apm == 0, &d_p, nullptr, &ctx->timing, ctx->err);
+    rc = twophase_predict(ctx->jobs[0].tp, s, ps, (const uint8_t *)ctx->io_in.p, n, block_size, nb, ps.n_apm == 0 && !ps.has_mix, &d_p, nullptr, &ctx->timing, ctx->err);
     if (rc) return rc;
+    if ((rc = twophase_lmix(ctx->jobs[0].tp, s, ps, (const uint8_t *)ctx->io_in.p, n, block_size, nb, nullptr, &ctx->timing, ctx->err))) return rc;
     if ((rc = twophase_apm(ctx->jobs[0].tp, s, ps, (const uint8_t *)ctx->io_in.p, n, block_size, nb, nullptr, &ctx->timing, ctx->err))) return rc;
     d_p = (const uint16_t *)ctx->jobs[0].tp.P;
     HIPCHK(ctx, hipStreamSynchronize(s));
@@ -3754,6 +3793,7 @@ extern "C" int w3_steps_layout_of(const w3_model_spec *spec, uint32_t format, ui
     if (!out) return W3_E_INVALID;
     ParsedSpec ps;
     if (const int rc = parse_spec(spec, ps)) return rc;
+    if (ps.has_mix) return W3_E_UNSUPPORTED;   // (the rows' mix column is OpinionMixer2's: steps_args)
     StepsLayout l;
     if (!steps_layout((uint32_t)ps.n_leaves, (uint32_t)ps.n_apm, format, flags, l)) return W3_E_INVALID;
     out->n_cols = l.n_cols; out->n_leaves = l.n_leaves; out->col_mix = l.col_mix; out->col_apm0 = l.col_apm0; out->n_apm = l.n_apm;
@@ -3863,6 +3903,8 @@ static int steps_args(w3_ctx *ctx, const w3_model_spec *spec, const void *in, si
     if (rc) return rc;
     if ((rc = jobs_idle(ctx))) return rc;   // (the predict phase runs on job 0's workspace)
     if ((rc = parse_spec(spec, ps))) { ctx->err = "malformed model spec"; return rc; }
+    // the row kernel recomputes the mix column with OpinionMixer2 (mix_p); a logistic mixer's column would have to come from a copy of ws.P
+    if (ps.has_mix) { ctx->err = "w3_export_steps_*: specs with a logistic mixer node (W3_NODE_MIX) are not exported"; return W3_E_UNSUPPORTED; }
     if (!steps_layout((uint32_t)ps.n_leaves, (uint32_t)ps.n_apm, format, flags, lay)) { ctx->err = "unknown W3_STEPS_* format or flag"; return W3_E_INVALID; }
     memset(&ctx->steps_prof, 0, sizeof ctx->steps_prof);
     ctx->steps_prof.direct_stores = (ctx->opt.tune & W3_TUNE_STEPS_DIRECT) ? 1u : 0u;

@@ -470,6 +470,43 @@ class APM(Model, Mixer):
         return self.model._nodes() + [nd]
 
 
+class LogisticMixer(Model, Mixer):
+    """Logistic mixer with learned weights (W3_NODE_MIX, include/w3hip.h): BUILD-DEFINED, integer-exact, fresh per
+    block.  p = squash(sum_i w_i stretch(p_i)) over 2..8 single leaves (Counter-table leaves of any history, not frozen, and slot-state
+    leaves), the weight set selected by nothing (ONE) or by the partial byte (ORDER0: 256 sets), trained after every bit by
+    w_i += (stretch(p_i) * err + round) >> rate.  Decodable: the lane-per-block kernels run it bit by bit."""
+    ONE, ORDER0 = L.W3_MIX_ONE, L.W3_MIX_ORDER0
+
+    def __init__(self, models, select=L.W3_MIX_ORDER0, rate=14):
+        self.models, self.select, self.rate = list(models), int(select), int(rate)
+
+    @classmethod
+    def new(cls, models, select=L.W3_MIX_ORDER0, rate=14):
+        return cls(models, select, rate)
+
+    def _huff_sets(self):
+        return [h for m in self.models for h in m._huff_sets()]
+
+    def _nodes(self):
+        nd = L.Node()
+        nd.kind = L.W3_NODE_MIX
+        if not (0 <= len(self.models) <= 255 and 0 <= self.select <= 255 and 0 <= self.rate <= 255):
+            raise W3Error(L.W3_E_INVALID, "u8 parameter out of range")
+        nd.bits, nd.align, nd.max_bits = len(self.models), self.select, self.rate
+        return [n for m in self.models for n in m._nodes()] + [nd]
+
+
+def order012_mix(select=LogisticMixer.ORDER0, rate=14):
+    """the three Counter orders of the bench's model under the logistic mixer instead of the BestOfTwo tree"""
+    return LogisticMixer([Order0(), Order1(), OrderN(27, 3)], select, rate)
+
+
+def full_cm_mix(log_cells=14):
+    """full_cm()'s seven leaves under the logistic mixer, its two APM stages behind it"""
+    leaves = [Order0(), Order1(), OrderN(27, 3)] + [SlotModel(order, log_cells) for order in (1, 2, 3, 4)]
+    return APM(APM(LogisticMixer(leaves), APM.ORDER0, 7), APM.ORDER1, 6)
+
+
 def full_cm(log_cells=14):
     """BASELINE.json configs[2] — "full 12-bit state-table CM (all src/models + APM chain)": the three Counter
     orders, four slot-state orders, OpinionMixer2 selection, two APM stages."""
