@@ -88,7 +88,8 @@ enum {
  *                          Encode: W3_PATH_TWOPHASE runs the mixer as a stage between the predict kernels and the APM stages
  *                          (k_lmix, csrc/w3_lmix.h; w3_timing.mix_ms), W3_PATH_GENERIC the lane-per-block kernels, W3_PATH_AUTO the
  *                          stage only for shapes at which it has been measured to win, else the lane kernels; the
- *                          streams are the same.  Decode: the lane-per-block kernels.
+ *                          streams are the same.  Decode: the sixteen-lane decoder for W3_MIX_ORDER0 where w3_decode_spec_covers
+ *                          says so (the 15 nodes of a nibble's tree have 15 different rows), else the lane-per-block kernels.
  */
 enum { W3_NODE_ORDERN = 1, W3_NODE_BEST_OF_TWO = 2, W3_NODE_SLOT_STATE = 3, W3_NODE_APM = 4, W3_NODE_MIX = 5 };
 enum { W3_HIST_NONE = 0, W3_HIST_RAW = 1, W3_HIST_AC = 2, W3_HIST_HUFF = 3 };
@@ -207,8 +208,8 @@ enum {
                            (0 = default; the result is the same).  A multiple of 1 KiB, at most 2^28: anything else is W3_E_INVALID */
 };
 enum { W3_PATH_AUTO = 0, W3_PATH_GENERIC = 1, W3_PATH_TWOPHASE = 2,
-       W3_PATH_SPEC = 3 /* reported only (w3_timing.path of the AC-over-Huffman decode and ranges calls that took the sixteen-lane decoder);
-                           W3_OPT_PATH does not accept it */ };
+       W3_PATH_SPEC = 3 /* reported only (w3_timing.path of the AC-over-Huffman decode and ranges calls that took the sixteen-lane decoder;
+                           w3_last_decode_path after a w3_decode_blocks* / w3_decode_ranges* call that did); W3_OPT_PATH does not accept it */ };
 int         w3_ctx_set_option(w3_ctx *ctx, int opt, int64_t value);
 
 /* Upper bound on the concatenated block streams for n input bytes. */
@@ -281,6 +282,20 @@ int w3_decode_ranges(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *in, 
 int w3_decode_ranges_device(w3_ctx *ctx, const w3_model_spec *spec, const uint8_t *d_in, size_t in_len, const uint32_t *d_block_lens,
                             size_t nblocks, size_t block_size, uint64_t orig_len, const w3_range *ranges /* host */, size_t n_ranges,
                             uint8_t *d_out, size_t out_cap, size_t *out_len, void *stream);
+
+/* ---- which kernels decode ------------------------------------------------------------------------------------------------------
+ * w3_decode_blocks*, w3_decode_ranges* and their _checked forms run one of two kernel families: the sixteen-lane decoder, which
+ * evaluates a nibble's whole context tree at once (csrc/w3_decode_spec.h: up to 8 leaves — Counter leaves with alignment_bits >= 2,
+ * slot-state leaves — under BestOfTwo nodes or a W3_MIX_ORDER0 mixer, and at most 2 APM stages), or the lane-per-block kernels
+ * (everything else, a W3_MIX_ONE mixer among it; W3_OPT_VARIANT bit 1024 asks for them by name).  The output is the same.
+ *   w3_decode_spec_covers   host only, the twin of w3_aoh_decode_spec_covers: 1 where the sixteen-lane decoder takes a decode of this
+ *                           spec under default options, 0 where the lane kernels do, the negative W3_E_* code of w3_spec_validate for
+ *                           a spec that call refuses.
+ *   w3_last_decode_path     W3_PATH_SPEC or W3_PATH_GENERIC: the family the context's most recent call of those named above launched,
+ *                           by the decision actually taken (options included); 0 before any decode.  w3_timing is not touched by a
+ *                           decode.  (The AC-over-Huffman family reports through w3_timing.path.)                                  */
+int w3_decode_spec_covers(const w3_model_spec *spec);
+int w3_last_decode_path(const w3_ctx *ctx);
 
 /* ---- integrity: CRC-32 per block, and decodes that verify it -----------------------------------------------------------------
  * The reference has no counterpart (one stream per file, no checksum: main.rs:89-144); build-defined on the block container.  An

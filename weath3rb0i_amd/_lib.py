@@ -111,6 +111,7 @@ EXPORTS = [
     "w3_export_entropy_device", "w3_export_entropy_staged", "w3_export_entropy_get_profile",
     "w3_steps_layout_of", "w3_export_steps_device", "w3_export_steps_staged", "w3_export_steps_get_profile",
     "w3_encode_probs_device", "w3_encode_stats_probs_device",
+    "w3_decode_spec_covers", "w3_last_decode_path",
 ]
 
 _lib = None
@@ -227,6 +228,10 @@ def load():
     lib.w3_export_steps_get_profile.argtypes = [vp, C.POINTER(StepsProfile)]
     lib.w3_encode_probs_device.argtypes = [vp, vp, sz, sz, vp, vp, sz, vp, vp, vp]
     lib.w3_encode_stats_probs_device.argtypes = [vp, vp, sz, sz, vp, vp, vp]
+    lib.w3_decode_spec_covers.argtypes = [C.POINTER(ModelSpec)]
+    lib.w3_decode_spec_covers.restype = C.c_int
+    lib.w3_last_decode_path.argtypes = [vp]
+    lib.w3_last_decode_path.restype = C.c_int
     lib.w3_rccl_library.argtypes = [C.c_char_p]
     lib.w3_rccl_status.argtypes = [C.c_char_p, sz]
     _lib = lib

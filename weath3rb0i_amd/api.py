@@ -382,6 +382,22 @@ class Context:
         out.update(key_ms=p.key_ms, huff_fixed_epochs=p.huff_fixed_epochs)
         return out
 
+    # ---- which kernels decode (include/w3hip.h "which kernels decode") ----
+    @staticmethod
+    def decode_spec_covers(model):
+        """w3_decode_spec_covers: whether the sixteen-lane decoder takes a decode of this model under default options (False: the
+        lane-per-block kernels do).  Host only: needs no context and no device.  A spec the library refuses raises W3Error."""
+        spec = model.spec() if isinstance(model, Model) else model
+        rc = L.load().w3_decode_spec_covers(C.byref(spec))
+        if rc < 0:
+            raise W3Error(rc, "w3_decode_spec_covers: the spec is refused")
+        return bool(rc)
+
+    def last_decode_path(self):
+        """w3_last_decode_path: L.W3_PATH_SPEC or L.W3_PATH_GENERIC, the kernel family this context's most recent decode_blocks* /
+        decode_ranges* call launched; 0 before any decode"""
+        return int(self.lib.w3_last_decode_path(self.h))
+
     # ---- per-step statistics (include/w3hip.h "per-step statistics"; csrc/w3_steps.h) ----
     _STEPS_FORMATS = {"p_u16": L.W3_STEPS_P_U16, "stretch_i16": L.W3_STEPS_STRETCH_I16, "stretch_f16": L.W3_STEPS_STRETCH_F16}
     _STEPS_NUMPY = {"p_u16": np.uint16, "stretch_i16": np.int16, "stretch_f16": np.float16}

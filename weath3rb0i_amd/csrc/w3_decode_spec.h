@@ -16,8 +16,10 @@
 // A wavefront holds four blocks: 3,815 wavefronts at enwik9 size instead of 239, and the chip hides the round trips it still has.
 // Model tables: the lane-per-block decoder's layout (layout_generic / layout_lane), one region per block.
 // Covered: up to 8 leaves — Counter-table leaves of any history kind with alignment_bits >= 2 (FrozenModel leaves too), slot-state leaves (HS
-// below) — and 0..2 APM stages.  Everything else (alignment 0 / 1: the nibble's own updates feed its later contexts; longer chains) stays on
-// the lane-per-block kernels, which also remain the cross-check (W3_OPT_VARIANT bit 1024).
+// below) — mixed by the OpinionMixer2 tree or by a logistic mixer node whose weight set is selected by the partial byte (W3_MIX_ORDER0: MIX
+// below), and 0..2 APM stages.  Everything else (alignment 0 / 1: the nibble's own updates feed its later contexts; longer chains; a
+// W3_MIX_ONE mixer, whose single weight set every bit trains for the next) stays on the lane-per-block kernels, which also remain the
+// cross-check (W3_OPT_VARIANT bit 1024).
 #pragma once
 #include "w3_cm.h"
 
@@ -156,7 +158,14 @@ __device__ __forceinline__ void bucket_lookup16(uint32_t *tbl, uint32_t bmask, u
 // what a SMALL batch — a few wavefronts per SIMD, nothing to hide latency behind — is bound by: below W3_DECODE_NM_MIN_BLOCKS the round-3
 // formats (slot-by-slot probes, row-major APM tables) stay.  A template parameter, not a run-time flag: the flag's branches alone cost the
 // small batches 18 % (profiles/r4_decode/).
-template <int NL, int NA, int D, bool HS = false, bool NM = false, bool RAW = false, int KM = 0>
+// MIX = the leaves feed a logistic mixer node (a.mix, W3_MIX_ORDER0; the step: w3_mix_plan.h) instead of the OpinionMixer2 selection.  The
+// weight set of a step is row c0 of the block's int32[256][N] table, c0 the partial byte with its leading 1 — and the 15 nodes (k, x) of a
+// nibble's tree have 15 different c0_n = (c0 << k) | x: no two nodes share a weight word, so the 15 dot products are taken side by side from
+// the weights as they stand when the nibble starts (the weight loads are issued first, beside the Counter look-ups), and afterwards the four
+// path nodes train their own rows.  The first nibble of a byte touches rows 1..15, the second rows 16..255: a row is read again two nibbles
+// later at the earliest, so — as for the APM tables — no fence beyond what the leaves ask for (fence_each) is needed.  (W3_MIX_ONE has one
+// weight set: every bit's update feeds the next bit's dot product; it stays on the lane kernels.)  D = 4 only.
+template <int NL, int NA, int D, bool HS = false, bool NM = false, bool RAW = false, int KM = 0, bool MIX = false>
 __global__ void __launch_bounds__(64) k_decode_spec(CmArgs a) {
     // RAW: every Counter leaf is live, over raw history, alignment 3, bits >= 6, and bit l of KM says whether leaf l is a slot-state leaf — all known
     // at compile time (decode_spec_all_raw / launch_decode_spec)
@@ -164,8 +173,15 @@ __global__ void __launch_bounds__(64) k_decode_spec(CmArgs a) {
     static_assert(RAW || KM == 0, "the leaf-kind mask belongs to the RAW instances");
     constexpr uint32_t LPB = 1u << D, BPW = 64u / LPB;        // lanes per block, blocks per wavefront
     static_assert(!HS || D == 4, "slot-state leaves: one Cell per nibble");
-    __shared__ int16_t s_str[NA > 0 ? 4096 : 1];
-    if (NA > 0) for (uint32_t i = threadIdx.x; i < 4096u; i += 64u) s_str[i] = a.stretch[i];
+    static_assert(!MIX || D == 4, "the mixer's rows are disjoint over a nibble's tree");
+    __shared__ int16_t s_str[(NA > 0 || MIX) ? 4096 : 1];
+    const uint16_t *s_sq = nullptr;
+    if constexpr (MIX) {   // the mixer's squash table, as k_cm
+        __shared__ uint16_t s_squash[4096];
+        for (uint32_t i = threadIdx.x; i < 4095u; i += 64u) s_squash[i] = a.squash[i];
+        s_sq = s_squash;
+    }
+    if (NA > 0 || MIX) for (uint32_t i = threadIdx.x; i < 4096u; i += 64u) s_str[i] = a.stretch[i];
     __shared__ uint2 s_st[HS ? kStSize : 1];
     if (HS) for (uint32_t i = threadIdx.x; i < (uint32_t)kStSize; i += 64u) s_st[i] = a.st[i];
     // the nibble's Cell of every (row, slot leaf), staged in w3_cm.h's layout: "lane" v = 8 * row + leaf of [chunk][64] x 16 B
@@ -219,6 +235,18 @@ __global__ void __launch_bounds__(64) k_decode_spec(CmArgs a) {
             uint32_t p = 32768u, best = 0u;
             uint8_t *cellp[HS ? NL : 1]; uint32_t sid[HS ? NL : 1];
             cm_u32x4 cq[HS ? NL : 1];
+            const uint32_t c0_n = (c0 << k) | x;
+            // MIX: the node's weight row (unused entries of the eight-leaf launch: weight and input 0), in flight beside everything below
+            int32_t mw[MIX ? NL : 1], ms[MIX ? NL : 1], mp = 0;
+            uint32_t *mrow = nullptr;
+            if constexpr (MIX) {
+                mrow = reinterpret_cast<uint32_t *>(blk_tbl + a.mix.off) + mix_row(a.mix.select, c0_n) * a.mix.n;
+#pragma unroll
+                for (int l = 0; l < NL; l++) {
+                    ms[l] = 0;
+                    mw[l] = (RAW || (uint32_t)l < a.mix.n) ? (int32_t)pl_ld32(mrow + l) : 0;   // (RAW: N = NL)
+                }
+            }
             if (HS) {
                 // the nibble's Cell of every slot-state leaf: lanes 0..5 of the row fetch its six 16-byte chunks into LDS, lane 0 selects the slot
                 // there (and evicts on a miss: cmc_select of w3_cm.h, hashmap.rs:42-71), the row learns the slot's id
@@ -282,10 +310,16 @@ __global__ void __launch_bounds__(64) k_decode_spec(CmArgs a) {
                 const uint32_t pl = (HS && is_slot(l)) ? (s_st[val[l]].x & 0xFFFFu)      // StateTable::p, state_table/mod.rs:47-49
                                   : RAW ? counter_p_packed(val[l])
                                   : lp[l].frozen ? 32768u : counter_p_packed(val[l]);
-                const uint32_t d = opinion_dist(pl);
-                if (first_leaf || d > best) { p = pl; best = d; first_leaf = false; }
+                if constexpr (MIX) ms[l] = s_str[pl >> 4];
+                else {
+                    const uint32_t d = opinion_dist(pl);
+                    if (first_leaf || d > best) { p = pl; best = d; first_leaf = false; }
+                }
             }
-            const uint32_t c0_n = (c0 << k) | x;
+            if constexpr (MIX) {
+                mp = (int32_t)s_sq[mix_predict_d(mw, ms, NL) + 2047];   // 22 .. 65514: never 0, decode_nz holds
+                p = (uint32_t)mp;
+            }
             uint16_t *aslot[NA > 0 ? NA : 1]; int tv[NA > 0 ? NA : 1];
 #pragma unroll
             for (int s = 0; s < NA; s++) {   // APM chain (build-defined), as k_cm_nl
@@ -360,6 +394,12 @@ __global__ void __launch_bounds__(64) k_decode_spec(CmArgs a) {
                 }
             }
             if (on) {
+                if constexpr (MIX) {   // the path node trains its own row from the mixer's p (before any APM stage) and what it predicted with
+                    mix_train(mw, ms, NL, mybit, mp, a.mix.rate);
+#pragma unroll
+                    for (int l = 0; l < NL; l++)
+                        if (RAW || (uint32_t)l < a.mix.n) pl_st32(mrow + l, (uint32_t)mw[l]);
+                }
 #pragma unroll
                 for (int l = 0; l < NL; l++) {
                     if (!is_ctr(l)) continue;
@@ -405,7 +445,7 @@ __global__ void __launch_bounds__(64) k_decode_spec(CmArgs a) {
                     pl_st16(aslot[s], (uint16_t)(tv[s] + (((mybit ? 65535 : 0) - tv[s]) >> s_apm[s].rate)));   // arithmetic shift = floor
             }
             // With alignment_bits >= 3 the two nibbles of a byte have disjoint contexts (t mod 8 is part of them) and disjoint APM rows
-            // (1..15 / 16..255): what this nibble stored can only be read two nibbles on — after the next nibble's loads have been waited
+            // and mixer rows (1..15 / 16..255): what this nibble stored can only be read two nibbles on — after the next nibble's loads have been waited
             // for, and gfx9's one counter for loads and stores then covers these stores too.  Only alignment 2 has to wait here.
             if (fence_each) {
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -430,7 +470,9 @@ static inline bool decode_spec_has_slot(const CmArgs &ca) {
 }
 static inline bool decode_spec_covers(const CmArgs &ca) {
     if (ca.g.n_leaves < 1 || ca.g.n_leaves > 8 || ca.n_apm > 2) return false;
-    if (ca.mix.n) return false;   // a logistic mixer over the leaves: the lane kernels decode it (w3_cm.h)
+    // a logistic mixer over the leaves: rows selected by the partial byte are disjoint over a nibble's tree (MIX above).  W3_MIX_ONE has a
+    // single weight set, which every bit trains before the next bit's dot product reads it: the lane kernels decode it (w3_cm.h)
+    if (ca.mix.n && ca.mix.select != MIX_ORDER0) return false;
     for (int l = 0; l < ca.g.n_leaves; l++) {
         const LeafParam &lp = ca.g.leaf[l];
         if (lp.kind == 0 && !lp.frozen && lp.align < 2) return false;
@@ -463,13 +505,13 @@ static inline bool decode_spec_full_cm_shape(const CmArgs &ca) {
     }
     return true;
 }
-template <bool NM>
+template <bool NM, bool MIX = false>
 static inline void launch_decode_spec_full_cm(const CmArgs &ca, uint32_t cnt, hipStream_t s) {
     const dim3 grid((cnt + 3u) / 4u), blk(64);
     switch (ca.n_apm) {
-    case 0: hipLaunchKernelGGL((k_decode_spec<W3_DS_FULLCM_NL, 0, 4, true, NM, true, W3_DS_FULLCM_KM>), grid, blk, 0, s, ca); break;
-    case 1: hipLaunchKernelGGL((k_decode_spec<W3_DS_FULLCM_NL, 1, 4, true, NM, true, W3_DS_FULLCM_KM>), grid, blk, 0, s, ca); break;
-    default: hipLaunchKernelGGL((k_decode_spec<W3_DS_FULLCM_NL, 2, 4, true, NM, true, W3_DS_FULLCM_KM>), grid, blk, 0, s, ca); break;
+    case 0: hipLaunchKernelGGL((k_decode_spec<W3_DS_FULLCM_NL, 0, 4, true, NM, true, W3_DS_FULLCM_KM, MIX>), grid, blk, 0, s, ca); break;
+    case 1: hipLaunchKernelGGL((k_decode_spec<W3_DS_FULLCM_NL, 1, 4, true, NM, true, W3_DS_FULLCM_KM, MIX>), grid, blk, 0, s, ca); break;
+    default: hipLaunchKernelGGL((k_decode_spec<W3_DS_FULLCM_NL, 2, 4, true, NM, true, W3_DS_FULLCM_KM, MIX>), grid, blk, 0, s, ca); break;
     }
 }
 
@@ -477,25 +519,25 @@ static inline void launch_decode_spec_full_cm(const CmArgs &ca, uint32_t cnt, hi
 #define W3_DECODE_NM_MIN_BLOCKS 8192u   // batches of at least this many blocks decode with the nibble-major table formats (measured: 4e8 B 462 against 490 MiB/s, 1e9 B 885 against 684)
 
 // up to eight leaves (the full CM has seven) and slot-state leaves: one instantiation with NL = 8, unused entries marked kind 2
-template <bool HS, bool NM>
+template <bool HS, bool NM, bool MIX = false>
 static inline void launch_decode_spec_8(CmArgs ca, uint32_t cnt, hipStream_t s) {
     for (int l = ca.g.n_leaves; l < 8; l++) { ca.g.leaf[l] = LeafParam{}; ca.g.leaf[l].kind = 2; ca.g.leaf[l].frozen = 1; }
     const dim3 grid((cnt + 3u) / 4u), blk(64);
     switch (ca.n_apm) {
-    case 0: hipLaunchKernelGGL((k_decode_spec<8, 0, 4, HS, NM>), grid, blk, 0, s, ca); break;
-    case 1: hipLaunchKernelGGL((k_decode_spec<8, 1, 4, HS, NM>), grid, blk, 0, s, ca); break;
-    default: hipLaunchKernelGGL((k_decode_spec<8, 2, 4, HS, NM>), grid, blk, 0, s, ca); break;
+    case 0: hipLaunchKernelGGL((k_decode_spec<8, 0, 4, HS, NM, false, 0, MIX>), grid, blk, 0, s, ca); break;
+    case 1: hipLaunchKernelGGL((k_decode_spec<8, 1, 4, HS, NM, false, 0, MIX>), grid, blk, 0, s, ca); break;
+    default: hipLaunchKernelGGL((k_decode_spec<8, 2, 4, HS, NM, false, 0, MIX>), grid, blk, 0, s, ca); break;
     }
 }
 
-template <int NL, int D, bool NM, bool RAW = false>
+template <int NL, int D, bool NM, bool RAW = false, bool MIX = false>
 static inline void launch_decode_spec_na(const CmArgs &ca, uint32_t cnt, hipStream_t s) {
     constexpr uint32_t BPW = 64u >> D;
     const dim3 grid((cnt + BPW - 1u) / BPW), blk(64);
     switch (ca.n_apm) {
-    case 0: hipLaunchKernelGGL((k_decode_spec<NL, 0, D, false, NM, RAW>), grid, blk, 0, s, ca); break;
-    case 1: hipLaunchKernelGGL((k_decode_spec<NL, 1, D, false, NM, RAW>), grid, blk, 0, s, ca); break;
-    default: hipLaunchKernelGGL((k_decode_spec<NL, 2, D, false, NM, RAW>), grid, blk, 0, s, ca); break;
+    case 0: hipLaunchKernelGGL((k_decode_spec<NL, 0, D, false, NM, RAW, 0, MIX>), grid, blk, 0, s, ca); break;
+    case 1: hipLaunchKernelGGL((k_decode_spec<NL, 1, D, false, NM, RAW, 0, MIX>), grid, blk, 0, s, ca); break;
+    default: hipLaunchKernelGGL((k_decode_spec<NL, 2, D, false, NM, RAW, 0, MIX>), grid, blk, 0, s, ca); break;
     }
 }
 // table formats of this batch (the APM tables' initialisation must agree: lane_run asks the same question)
@@ -508,6 +550,16 @@ static inline bool decode_spec_nibble_major(const CmArgs &ca, uint32_t cnt, int 
 // bits_per_group: 4 = the nibble (the shipped form), 2 = half a nibble (a tested variant)
 static inline void launch_decode_spec(const CmArgs &ca, uint32_t cnt, hipStream_t s, int bits_per_group) {
     const bool nm = decode_spec_nibble_major(ca, cnt, bits_per_group);
+    if (ca.mix.n) {
+        // a logistic mixer (nibble groups only: lane_run keeps the two-bit-group variant on the lane kernels).  The eight-leaf forms serve every
+        // covered spec; order012_mix()'s shape (three raw-history leaves) and full_cm_mix()'s have the compile-time-specialised instances of
+        // their trees (measured: profiles/mixer_decode/), W3_OPT_TUNE bit 19 keeps the eight-leaf form as for the trees
+        if (decode_spec_full_cm_shape(ca)) { if (nm) launch_decode_spec_full_cm<true, true>(ca, cnt, s); else launch_decode_spec_full_cm<false, true>(ca, cnt, s); return; }
+        if (ca.g.n_leaves == 3 && decode_spec_all_raw(ca)) { if (nm) launch_decode_spec_na<3, 4, true, true, true>(ca, cnt, s); else launch_decode_spec_na<3, 4, false, true, true>(ca, cnt, s); return; }
+        if (decode_spec_has_slot(ca)) { if (nm) launch_decode_spec_8<true, true, true>(ca, cnt, s); else launch_decode_spec_8<true, false, true>(ca, cnt, s); }
+        else { if (nm) launch_decode_spec_8<false, true, true>(ca, cnt, s); else launch_decode_spec_8<false, false, true>(ca, cnt, s); }
+        return;
+    }
     if (bits_per_group == 4 && decode_spec_full_cm_shape(ca)) { if (nm) launch_decode_spec_full_cm<true>(ca, cnt, s); else launch_decode_spec_full_cm<false>(ca, cnt, s); return; }
     if (decode_spec_has_slot(ca)) { if (nm) launch_decode_spec_8<true, true>(ca, cnt, s); else launch_decode_spec_8<true, false>(ca, cnt, s); return; }
     if (ca.g.n_leaves > 4) { if (nm) launch_decode_spec_8<false, true>(ca, cnt, s); else launch_decode_spec_8<false, false>(ca, cnt, s); return; }

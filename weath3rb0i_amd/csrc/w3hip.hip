@@ -108,6 +108,7 @@ struct w3_ctx {
     int opt_path = W3_PATH_AUTO;
     int opt_timing = 0;
     w3_timing timing{};
+    int last_decode_path = 0;   // w3_last_decode_path: the kernel family of the most recent w3_decode_* call (lane_run), 0 before any
     // workspace that is not a job's
     DevBuf tables, lens, total, io_in, io_out, coffs, misc, cm_luts, achash_luts, sweep;
     DevBuf aoh;   // AC over Huffman (w3_aoh.h): code tables in device form, configurations, block bit lengths, maxima and flags
@@ -671,6 +672,14 @@ struct LaneIo {
     const uint8_t *cin = nullptr; const uint32_t *clens = nullptr; uint8_t *dout = nullptr; const DecodeJob *jobs = nullptr; uint32_t n_jobs = 0;
 };
 
+// Does a decode take k_decode_spec?  Where the kernel covers the spec (decode_spec_covers), unless the lane kernels are asked for by name
+// (W3_VAR_DECODE_LANE: the cross-check) — and, for a spec with a logistic mixer, only with nibble groups: the two-bit-group variant
+// (decode_group_bits) is not built for it.  One rule for the launch, the APM tables' format (nm_tables below) and w3_decode_spec_covers.
+static bool decode_takes_spec(const CmArgs &ca, uint32_t variant, int group_bits) {
+    if (!decode_spec_covers(ca) || (variant & W3_VAR_DECODE_LANE)) return false;
+    return !(ca.mix.n && group_bits != 4);
+}
+
 template <bool DECODE>
 static int lane_run(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, size_t block_size, uint64_t n, uint32_t nb, const LaneIo &io) {
     CmArgs ca;
@@ -694,7 +703,8 @@ static int lane_run(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, size_t blo
         g.overflow = (uint32_t *)ctx->jobs[0].flag.p; g.out_bits = (uint32_t *)ctx->jobs[0].bits.p;
     }
     // the nibble's context tree at once, sixteen lanes per block (w3_decode_spec.h), where it applies
-    const bool spec_dec = DECODE && decode_spec_covers(ca) && !(ctx->opt.variant & W3_VAR_DECODE_LANE);
+    const bool spec_dec = DECODE && decode_takes_spec(ca, ctx->opt.variant, decode_group_bits(ctx));
+    if (DECODE) ctx->last_decode_path = spec_dec ? W3_PATH_SPEC : W3_PATH_GENERIC;   // (w3_last_decode_path; w3_timing is an encode's record)
     for (uint32_t first = 0; first < nl; first += lanes) {
         const uint32_t cnt = std::min(lanes, nl - first);
         g.first_block = first; g.n_lanes = cnt;
@@ -713,6 +723,16 @@ static int lane_run(w3_ctx *ctx, hipStream_t s, const ParsedSpec &ps, size_t blo
     }
     return W3_OK;
 }
+
+extern "C" int w3_decode_spec_covers(const w3_model_spec *spec) {
+    ParsedSpec ps;
+    if (const int rc = parse_spec(spec, ps)) return rc;
+    CmArgs ca;
+    memset(&ca, 0, sizeof ca);
+    layout_lane(ps, 65536, ca);   // (the leaves' kinds and alignments, the chain, the mixer: nothing the answer reads depends on the block size)
+    return decode_takes_spec(ca, 0u, 4) ? 1 : 0;
+}
+extern "C" int w3_last_decode_path(const w3_ctx *ctx) { return ctx ? ctx->last_decode_path : 0; }
 
 // ---------------------------------------------------------------------------
 // encode (device-resident)
