@@ -90,9 +90,24 @@ enum {
  *                          stage only for shapes at which it has been measured to win, else the lane kernels; the
  *                          streams are the same.  Decode: the sixteen-lane decoder for W3_MIX_ORDER0 where w3_decode_spec_covers
  *                          says so (the 15 nodes of a nibble's tree have 15 different rows), else the lane-per-block kernels.
+ *   leaf  W3_NODE_ORDERN with history = W3_HIST_MATCH : the match model, OrderNEntropy(11, 3, MatchHistory(min_len, log_slots))
+ *                          (integer-exact, fresh per block; csrc/w3_match_plan.h is the one copy of its arithmetic).
+ *                          bits = 11, align = 3, max_bits = min_len m (2..4), log_cells = log_slots L (8..20); table, reserved and
+ *                          frozen as for a W3_HIST_RAW leaf.  At byte boundary i of a block x, for k in (m, 2m) and i >= k:
+ *                              h_k = ((big-endian integer of x[i-k .. i-1]) * 0x9E3779B97F4A7C15 mod 2^64) >> (64 - L)
+ *                              c_k = T_k[h_k], then T_k[h_k] = i              (two tables of 2^L u32, 0 = empty at the block start)
+ *                              v_k = bytes of agreement of x[.. i-1] and x[.. c_k-1], at most min(32, c_k); 0 when c_k = 0
+ *                          the candidate is (c_2m, v_2m) if v_2m > v_m, else (c_m, v_m); v = 0 predicts nothing; else e = x[c] and
+ *                          lq = v for v < 16, 16 + ((v - 16) >> 2) above.  hash() at bit position j (MSB first) is
+ *                          (lq << 1) | bit (7-j) of e while the j known bits of the byte equal e's, else 0 (at most 41).
+ *                          m or L out of range: W3_E_INVALID.  bits != 11, align != 3 or a second match leaf in one spec:
+ *                          W3_E_UNSUPPORTED.  Otherwise an ORDERN leaf like any other (under BestOfTwo, under a MIX, APM stages
+ *                          behind, frozen).  Encode: W3_PATH_TWOPHASE computes the keys with one wavefront per block (k_match_keys,
+ *                          csrc/w3_match.h; w3_timing.match_ms); decode and W3_PATH_GENERIC: the lane-per-block kernels
+ *                          (w3_decode_spec_covers is 0).  w3_export_counters* and w3_export_entropy_* return W3_E_UNSUPPORTED.
  */
 enum { W3_NODE_ORDERN = 1, W3_NODE_BEST_OF_TWO = 2, W3_NODE_SLOT_STATE = 3, W3_NODE_APM = 4, W3_NODE_MIX = 5 };
-enum { W3_HIST_NONE = 0, W3_HIST_RAW = 1, W3_HIST_AC = 2, W3_HIST_HUFF = 3 };
+enum { W3_HIST_NONE = 0, W3_HIST_RAW = 1, W3_HIST_AC = 2, W3_HIST_HUFF = 3, W3_HIST_MATCH = 4 };
 enum { W3_APM_ORDER0 = 0, W3_APM_ORDER1 = 1 };
 enum { W3_MIX_ONE = 0, W3_MIX_ORDER0 = 1 };
 #define W3_MIX_MAX_INPUTS 8
@@ -106,9 +121,9 @@ typedef struct w3_node {
     uint8_t  bits;      /* bits_in_context   (1..32)                  */
     uint8_t  align;     /* alignment_bits    (0..7, <= bits)          */
     uint8_t  history;   /* W3_HIST_*                                  */
-    uint8_t  max_bits;  /* ACHistory max_bits (0..32)                 */
+    uint8_t  max_bits;  /* ACHistory max_bits (0..32); W3_HIST_MATCH: min_len (2..4) */
     uint8_t  frozen;    /* 1 = FrozenModel wrapper                    */
-    uint8_t  log_cells; /* SLOT_STATE: HashMap log_cell_count (1..24) */
+    uint8_t  log_cells; /* SLOT_STATE: HashMap log_cell_count (1..24); W3_HIST_MATCH: log_slots (8..20) */
     uint8_t  reserved;  /* W3_HIST_HUFF: index into spec->huff         */
     uint16_t table[8];  /* StationaryModel table, index 0 = MSB       */
 } w3_node;
@@ -777,6 +792,7 @@ typedef struct w3_timing {
     float    rank_ms[4];   /* k_rank_sorted of wide leaf w */
     float    small_ms;     /* k_predict_small launches of the time-ordered Counter leaves (H <= 8, raw history), together */
     float    mix_ms;       /* logistic mixer stage of the two-phase path (k_lmix / k_lmix_one); 0 for specs without a W3_NODE_MIX */
+    float    match_ms;     /* key stage of the match-model leaf on the two-phase path (k_match_keys; also inside predict_ms); 0 without one */
 } w3_timing;
 int w3_get_timing(const w3_ctx *ctx, w3_timing *out);
 

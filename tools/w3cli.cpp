@@ -47,6 +47,8 @@ static void push(w3_model_spec &s, uint8_t kind, uint8_t bits = 0, uint8_t align
 //   fullcm            : + slot-state leaves of order 1-4 and two APM stages (BASELINE configs[2])
 //   order012mix       : order012's three leaves under the logistic mixer (W3_NODE_MIX, ORDER0 weight sets, rate 14) instead of the tree
 //   fullcmmix         : fullcm's seven leaves under the logistic mixer, its two APM stages behind it
+//   order012matchmix  : order012mix with the match-model leaf (W3_HIST_MATCH, min_len 4, log_slots 16) as the mixer's fourth input
+//   fullcmmatchmix    : fullcmmix with the match-model leaf as the mixer's eighth input
 static w3_model_spec init_model() {
     w3_model_spec s;
     memset(&s, 0, sizeof s);
@@ -60,10 +62,13 @@ static w3_model_spec init_model() {
         memcpy(s.nodes[0].table, book1, sizeof book1);
         return s;
     }
+    const bool match = name == "order012matchmix" || name == "fullcmmatchmix";
+    if (match) name = name == "order012matchmix" ? "order012mix" : "fullcmmix";
     if (name == "order012mix" || name == "fullcmmix") {
         push(s, W3_NODE_ORDERN, 11, 3); push(s, W3_NODE_ORDERN, 19, 3); push(s, W3_NODE_ORDERN, 27, 3);
         if (name == "fullcmmix")
             for (uint8_t order = 1; order <= 4; order++) push(s, W3_NODE_SLOT_STATE, order, 0, 0, 14);
+        if (match) { push(s, W3_NODE_ORDERN, 11, 3, 4, 16); s.nodes[s.n_nodes - 1].history = W3_HIST_MATCH; }   // MatchHistory(min_len 4, log_slots 16)
         push(s, W3_NODE_MIX, (uint8_t)s.n_nodes, W3_MIX_ORDER0, 14);
         if (name == "fullcmmix") { push(s, W3_NODE_APM, 0, W3_APM_ORDER0, 7); push(s, W3_NODE_APM, 0, W3_APM_ORDER1, 6); }
         return s;

@@ -7,4 +7,5 @@ from .api import (MAGIC_STR, Context, aoh_container_ranges, encode_blocks_sharde
                   sharded_max_in_flight)
 from .models import (APM, ACHistory, ACHistoryCached, AdaptiveModel, BestOfTwoModel, FrozenModel, HashMap, HuffCode, HuffHistory, Mixer, Model,  # noqa: F401
                      OpinionMixer2, Order0, Order1, OrderN, OrderNEntropy, RawHistory, SlotModel, StateTable,
-                     StationaryModel, W3Error, full_cm, full_cm_mix, init_model, order012_mix, LogisticMixer)
+                     StationaryModel, W3Error, full_cm, full_cm_mix, init_model, order012_mix, LogisticMixer,
+                     MatchHistory, MatchModel, order012_match_mix, full_cm_match_mix)

@@ -12,7 +12,7 @@ W3_NODE_ORDERN, W3_NODE_BEST_OF_TWO, W3_NODE_SLOT_STATE, W3_NODE_APM, W3_NODE_MI
 W3_APM_ORDER0, W3_APM_ORDER1 = 0, 1
 W3_MIX_ONE, W3_MIX_ORDER0 = 0, 1
 W3_MAX_APM = 4
-W3_HIST_NONE, W3_HIST_RAW, W3_HIST_AC, W3_HIST_HUFF = 0, 1, 2, 3
+W3_HIST_NONE, W3_HIST_RAW, W3_HIST_AC, W3_HIST_HUFF, W3_HIST_MATCH = 0, 1, 2, 3, 4
 W3_MAX_HUFF = 4
 W3_OK, W3_E_INVALID, W3_E_NOSPACE, W3_E_HIP, W3_E_UNSUPPORTED, W3_E_NOMEM, W3_E_FORMAT = 0, -1, -2, -3, -4, -5, -6
 W3_E_CORRUPT = -7
@@ -58,7 +58,7 @@ class Timing(C.Structure):
                 ("coder_bytes", C.c_uint64), ("predict_bytes", C.c_uint64), ("n_recoded_blocks", C.c_uint32), ("apm_ms", C.c_float),
                 ("slot_ms", C.c_float), ("n_slot_launches", C.c_uint32), ("achash_ms", C.c_float), ("n_parts", C.c_uint32),
                 ("n_lds_faults", C.c_uint32), ("n_wide", C.c_uint32), ("part_ms", C.c_float * 4), ("rank_ms", C.c_float * 4),
-                ("small_ms", C.c_float), ("mix_ms", C.c_float)]
+                ("small_ms", C.c_float), ("mix_ms", C.c_float), ("match_ms", C.c_float)]
 
 
 class PrepProfile(C.Structure):   # w3_prep_profile

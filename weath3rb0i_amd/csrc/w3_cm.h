@@ -137,7 +137,8 @@ __global__ void __launch_bounds__(256) k_cm_init_mix(uint8_t *tables, uint64_t l
 }
 
 // MIX: the leaves feed a logistic mixer (a.mix) instead of the BestOfTwo tree; its squash table is staged in LDS beside the others.
-template <bool DECODE, bool MIX = false>
+// MATCH: one leaf is the match model (W3_HIST_MATCH): its state and tables as in k_generic (w3_generic.h).
+template <bool DECODE, bool MIX = false, bool MATCH = false>
 __global__ void __launch_bounds__(64) k_cm(CmArgs a) {
     __shared__ uint2   s_st[kStSize];
     __shared__ int16_t s_str[4096];
@@ -179,6 +180,8 @@ __global__ void __launch_bounds__(64) k_cm(CmArgs a) {
 
     uint64_t hist64 = 0, hist_bytes = 0; uint32_t t = 0, c0 = 1, c1 = 0;
     HuffState hs;
+    MatchState mst;
+    const int ml = MATCH ? match_leaf_of(s_leaf, g.n_leaves) : -1;
     for (uint32_t i = 0; i < len; i++) {
         uint32_t byte = DECODE ? 0u : g.in[off + i];
         for (int s = 7; s >= 0; s--) {
@@ -195,7 +198,7 @@ __global__ void __launch_bounds__(64) k_cm(CmArgs a) {
                     st[l] = slot_get_state(cellp[l], sid[l], bit_id, nib_ctx);
                     pl = s_st[st[l]].x & 0xFFFFu;                       // StateTable::p  state_table/mod.rs:47-49
                 } else if (!lp.frozen) {
-                    cslot[l] = leaf_slot(lp, lane_tbl, leaf_ctx(lp, hist64, t, hs, a.g.huff));
+                    cslot[l] = leaf_slot(lp, lane_tbl, leaf_ctx<MATCH>(lp, hist64, t, hs, a.g.huff, &mst));
                     pl = counter_p_packed(*cslot[l]);
                 }
                 const uint32_t d = opinion_dist(pl);
@@ -255,6 +258,10 @@ __global__ void __launch_bounds__(64) k_cm(CmArgs a) {
         }
         if (g.n_huff) hs.push_byte(g.huff, g.n_huff, byte & 0xFFu);
         if (DECODE) g.dout[off + i] = (uint8_t)byte;
+        if constexpr (MATCH) {   // (w3_generic.h)
+            if (ml >= 0 && i + 1u < len)
+                match_advance(mst, match_tables(s_leaf[ml], lane_tbl), s_leaf[ml].max_bits, s_leaf[ml].log_cells, (DECODE ? (const uint8_t *)g.dout : g.in) + off, i + 1u, i + 1u);
+        }
     }
     if (!DECODE) {
         if (g.out_bits) g.out_bits[b] = enc.stats_bits();
@@ -335,7 +342,7 @@ __device__ __forceinline__ uint32_t cmc_select(cm_lds_u32 *cb, uint32_t tag, con
     return (uint32_t)id;
 }
 
-template <bool DECODE, bool MIX = false>
+template <bool DECODE, bool MIX = false, bool MATCH = false>
 __global__ void __launch_bounds__(64) k_cm_staged(CmArgs a) {
     __shared__ uint2   s_st[kStSize];
     __shared__ int16_t s_str[4096];
@@ -399,6 +406,8 @@ __global__ void __launch_bounds__(64) k_cm_staged(CmArgs a) {
 
     uint64_t hist64 = 0, hist_bytes = 0; uint32_t t = 0, c0 = 1, c1 = 0;
     HuffState hs;
+    MatchState mst;
+    const int ml = MATCH ? match_leaf_of(s_leaf, g.n_leaves) : -1;
     for (uint32_t i = 0; i < len; i++) {
         uint32_t byte = DECODE ? 0u : g.in[off + i];
         for (int s = 7; s >= 0; s--) {
@@ -417,7 +426,7 @@ __global__ void __launch_bounds__(64) k_cm_staged(CmArgs a) {
                     st[l] = cmc_state(cb, slot_idx(sid[l], bit_id, nib_ctx), r, v);
                     pl = s_st[st[l]].x & 0xFFFFu;                       // StateTable::p  state_table/mod.rs:47-49
                 } else if (!lp.frozen) {
-                    cslot[l] = leaf_slot(lp, lane_tbl, leaf_ctx(lp, hist64, t, hs, a.g.huff));
+                    cslot[l] = leaf_slot(lp, lane_tbl, leaf_ctx<MATCH>(lp, hist64, t, hs, a.g.huff, &mst));
                     pl = counter_p_packed(*cslot[l]);
                 }
                 const uint32_t d = opinion_dist(pl);
@@ -481,6 +490,10 @@ __global__ void __launch_bounds__(64) k_cm_staged(CmArgs a) {
         }
         if (g.n_huff) hs.push_byte(g.huff, g.n_huff, byte & 0xFFu);
         if (DECODE) g.dout[off + i] = (uint8_t)byte;
+        if constexpr (MATCH) {   // (w3_generic.h)
+            if (ml >= 0 && i + 1u < len)
+                match_advance(mst, match_tables(s_leaf[ml], lane_tbl), s_leaf[ml].max_bits, s_leaf[ml].log_cells, (DECODE ? (const uint8_t *)g.dout : g.in) + off, i + 1u, i + 1u);
+        }
     }
     if (!DECODE) {
         if (g.out_bits) g.out_bits[b] = enc.stats_bits();

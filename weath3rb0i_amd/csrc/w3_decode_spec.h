@@ -476,6 +476,7 @@ static inline bool decode_spec_covers(const CmArgs &ca) {
     for (int l = 0; l < ca.g.n_leaves; l++) {
         const LeafParam &lp = ca.g.leaf[l];
         if (lp.kind == 0 && !lp.frozen && lp.align < 2) return false;
+        if (lp.kind == 0 && lp.hist == W3_HIST_MATCH) return false;   // the match model: the lane kernels (DESIGN.md 7 names the follow-up)
     }
     return true;
 }

@@ -7,6 +7,7 @@
 // apply and under W3_VAR_DECODE_LANE, and the device's own cross-check of both.
 #pragma once
 #include "w3_device.h"
+#include "w3_match_plan.h"
 #include "../../include/w3hip.h"
 
 namespace w3 {
@@ -79,9 +80,29 @@ struct HuffState {
     }
 };
 
-__device__ __forceinline__ uint32_t leaf_ctx(const LeafParam &lp, uint64_t hist64, uint32_t t, const HuffState &hs, const w3_huff_table *huff) {
+// The match model (W3_HIST_MATCH; w3_match_plan.h): per lane the candidate's next byte e and the length bucket lq (0: no prediction), advanced
+// once per completed byte where HuffState::push_byte is.  The two candidate tables lie in the lane's table region right before the leaf's
+// Counter table (layout_generic) and start zeroed with it.  Only the kernels instantiated with MATCH carry any of this.
+__device__ __forceinline__ int match_leaf_of(const LeafParam *leaf, int n) {
+    for (int l = 0; l < n; l++)
+        if (leaf[l].kind == 0 && leaf[l].hist == W3_HIST_MATCH && !leaf[l].frozen) return l;
+    return -1;
+}
+__device__ __forceinline__ uint32_t *match_tables(const LeafParam &lp, uint8_t *lane_tbl) {
+    return reinterpret_cast<uint32_t *>(lane_tbl + lp.tbl_off - (8ull << lp.log_cells));
+}
+
+template <bool MATCH = false>
+__device__ __forceinline__ uint32_t leaf_ctx(const LeafParam &lp, uint64_t hist64, uint32_t t, const HuffState &hs, const w3_huff_table *huff,
+                                             const MatchState *ms = nullptr) {
     if (t == 0u) return 0u;
     uint32_t h;
+    if constexpr (MATCH) {
+        if (lp.hist == W3_HIST_MATCH) {
+            const uint32_t j = t & 7u;
+            return (match_key(ms->lq, ms->e, (uint32_t)hist64, j) << 3) | j;
+        }
+    }
     if (lp.hist == W3_HIST_HUFF) {
         const uint32_t al = t & 7u;
         const uint32_t rem = ((uint32_t)hist64 & ((1u << al) - 1u)) | (1u << al);   // the partial byte with a leading 1 (:71-73)
@@ -137,7 +158,7 @@ __device__ __forceinline__ void stage_leaves(LeafParam *s_leaf, const GenericArg
     __syncthreads();
 }
 
-template <bool DECODE>
+template <bool DECODE, bool MATCH = false>
 __global__ void __launch_bounds__(64) k_generic(GenericArgs a) {
     __shared__ LeafParam s_leaf[W3_MAX_LEAVES];
     stage_leaves(s_leaf, a);
@@ -155,6 +176,8 @@ __global__ void __launch_bounds__(64) k_generic(GenericArgs a) {
 
     uint64_t hist64 = 0; uint32_t t = 0;
     HuffState hs;
+    MatchState ms;
+    const int ml = MATCH ? match_leaf_of(s_leaf, a.n_leaves) : -1;
     for (uint32_t i = 0; i < len; i++) {
         uint32_t byte = DECODE ? 0u : a.in[off + i];
         for (int s = 7; s >= 0; s--) {
@@ -166,7 +189,7 @@ __global__ void __launch_bounds__(64) k_generic(GenericArgs a) {
                 uint32_t pl = 32768u;
                 slot[l] = nullptr;
                 if (!lp.frozen) {                       // FrozenModel never adapts: Counter stays (0,0)
-                    slot[l] = leaf_slot(lp, lane_tbl, leaf_ctx(lp, hist64, t, hs, a.huff));
+                    slot[l] = leaf_slot(lp, lane_tbl, leaf_ctx<MATCH>(lp, hist64, t, hs, a.huff, &ms));
                     pl = counter_p_packed(*slot[l]);
                 }
                 uint32_t d = opinion_dist(pl);
@@ -184,6 +207,10 @@ __global__ void __launch_bounds__(64) k_generic(GenericArgs a) {
         }
         if (a.n_huff) hs.push_byte(a.huff, a.n_huff, byte & 0xFFu);
         if (DECODE) a.dout[off + i] = (uint8_t)byte;
+        if constexpr (MATCH) {   // boundary i + 1 from the block's bytes [0, i]: the input, or what this lane has decoded
+            if (ml >= 0 && i + 1u < len)
+                match_advance(ms, match_tables(s_leaf[ml], lane_tbl), s_leaf[ml].max_bits, s_leaf[ml].log_cells, (DECODE ? a.dout : a.in) + off, i + 1u, i + 1u);
+        }
     }
     if (!DECODE) {
         if (a.out_bits) a.out_bits[b] = enc.stats_bits();

@@ -12,6 +12,7 @@ struct ParsedSpec {
     bool has_slot = false;
     bool has_mix = false;                 // the leaves feed a logistic mixer (W3_NODE_MIX: bits = inputs, align = selector, max_bits = rate)
     w3_node mix{};
+    bool has_match = false;               // one leaf is the match model (W3_HIST_MATCH: max_bits = min_len, log_cells = log_slots)
     uint32_t n_huff = 0;                  // HuffHistory table sets (caller's memory, valid during the call)
     const w3_huff_table *huff = nullptr;
     bool is_cm() const { return has_slot || n_apm > 0 || has_mix; }

@@ -19,6 +19,7 @@
 #include "w3_coder4.h"
 #include "w3_coder5.h"
 #include "w3_lmix.h"
+#include "w3_match.h"
 #include "w3_predict.h"
 #include "w3_predict_wave.h"
 #include "w3_slot.h"
@@ -52,7 +53,7 @@ enum { W3_VAR_NO_LDS_ATOMICS = 1, W3_VAR_PARTITION4 = 2, W3_VAR_NO_CHAINED_PARTI
 // event slots (pairs: ev[2 * slot], ev[2 * slot + 1]) of one encode
 enum { W3_EV_PREDICT = 0, W3_EV_CODER = 1, W3_EV_PACK = 2, W3_EV_TOTAL = 3, W3_EV_APM = 4, W3_EV_SLOT = 5, W3_EV_ACHASH = 6,
        W3_EV_PART0 = 7 /* .. 10: partition pass of wide leaf w */, W3_EV_RANK0 = 11 /* .. 14: rank kernel of wide leaf w */, W3_EV_SMALL = 15, W3_EV_MIX = 16,
-       W3_EV_SLOTS = 17 };
+       W3_EV_MATCH = 17, W3_EV_SLOTS = 18 };
 #define W3_NEV (2 * W3_EV_SLOTS)
 
 // What w3_ctx_set_option sets for the two-phase path.  The context owns the block; a workspace takes a copy when a call is prepared.
@@ -113,6 +114,8 @@ struct TwoPhaseWs {
     void *wave_tables = nullptr; size_t wave_tables_cap = 0;  // k_predict_wave: one Counter table per resident wavefront
     void *huff_redo = nullptr;          // k_huffkeys: per-block "recompute serially" flags
     size_t huff_redo_cap = 0;
+    void *match_tables = nullptr; size_t match_tables_cap = 0;   // k_match_keys: the two candidate tables of every resident wavefront
+    bool match_timed = false;           // the last predict recorded W3_EV_MATCH
     TwoPhaseOptions opt;       // the context's options as of the call being made (w3hip.hip hands them over when it prepares a call)
     uint64_t verify_calls = 0; // the call's number for the sample's rotation (w3_verify.h: counted per shape by the context)
     TwoPhaseWs *vws = nullptr; // workspace of that re-prediction (owned)
@@ -160,6 +163,8 @@ struct TwoPhaseWs {
         wave_tables = nullptr; wave_tables_cap = 0;
         if (huff_redo) (void)hipFree(huff_redo);
         huff_redo = nullptr; huff_redo_cap = 0;
+        if (match_tables) (void)hipFree(match_tables);
+        match_tables = nullptr; match_tables_cap = 0;
         if (streams) (void)hipFree(streams);
         if (rec) (void)hipFree(rec);
         if (splits) (void)hipFree(splits);
@@ -181,11 +186,13 @@ static inline int tp_ensure(void *&p, size_t &cap, size_t bytes, std::string &er
 }
 
 enum { LEAF_FROZEN = 0, LEAF_SMALL = 1, LEAF_SMALL_AC = 2, LEAF_WIDE1 = 3, LEAF_WIDE2 = 4, LEAF_SLOT = 5, LEAF_SMALL_HUFF = 6,
-       LEAF_WAVE = 7 /* any other Counter-table leaf: wave per block, table in HBM (w3_predict_wave.h) */, LEAF_NONE = -1 };
+       LEAF_WAVE = 7 /* any other Counter-table leaf: wave per block, table in HBM (w3_predict_wave.h) */,
+       LEAF_SMALL_MATCH = 8 /* the match-model leaf: keys from k_match_keys (w3_match.h), then k_predict_small<8, true> */, LEAF_NONE = -1 };
 
 static inline int leaf_class(const w3_node &nd) {
     if (nd.kind == W3_NODE_SLOT_STATE) return LEAF_SLOT;
     if (nd.frozen) return LEAF_FROZEN;
+    if (nd.history == W3_HIST_MATCH) return LEAF_SMALL_MATCH;   // (parse_spec: bits == 11, align == 3)
     if (nd.align != 3 || nd.bits < 3) return LEAF_WAVE;
     const int H = nd.bits - 3;
     if (nd.history == W3_HIST_HUFF) return H <= 8 ? LEAF_SMALL_HUFF : LEAF_WAVE;
@@ -298,7 +305,7 @@ static inline int twophase_predict_a(TwoPhaseWs &ws, hipStream_t s, const Parsed
                                      uint32_t nb, hipEvent_t *ev, std::string &err, bool join_all = false) {
     int rc = W3_OK;
     ws.P_valid = false;
-    ws.achash_timed = false;
+    ws.achash_timed = false; ws.match_timed = false;
     const bool lds_atomics = twophase_lds_order_ok(ws, s);
     ws.used_lds_atomics = false;
     const uint32_t grid_small = std::min<uint32_t>(nb, 256 * 20);   // (KEYS leaves; the plain ones: launch_small_shaped)
@@ -307,7 +314,7 @@ static inline int twophase_predict_a(TwoPhaseWs &ws, hipStream_t s, const Parsed
     bool need_keys = false, need_perm = false;
     for (int l = 0; l < ps.n_leaves; l++) {
         int c = leaf_class(ps.leaf[l]);
-        need_keys |= c == LEAF_SMALL_AC || c == LEAF_SMALL_HUFF;
+        need_keys |= c == LEAF_SMALL_AC || c == LEAF_SMALL_HUFF || c == LEAF_SMALL_MATCH;
         need_perm |= c == LEAF_WIDE1 || c == LEAF_WIDE2;
     }
     if (need_keys && (rc = tp_ensure(ws.keys, ws.keys_cap, n * 8, err))) return rc;
@@ -475,6 +482,26 @@ static inline int twophase_predict_a(TwoPhaseWs &ws, hipStream_t s, const Parsed
             pa.keys = (const uint2 *)ws.keys;
             launch_small<true>(nd.bits - 3, dim3(grid_small), s, pa);
             bytes += n * 17;
+        } else if (c == LEAF_SMALL_MATCH) {
+            // one wavefront per block, as many as the chip holds (latency-bound: w3_match.h) and the tables' budget allows
+            w3::MatchKeyArgs mk;
+            memset(&mk, 0, sizeof mk);
+            mk.in = d_in; mk.n = n; mk.block_size = (uint32_t)block_size; mk.nblocks = nb; mk.keys = (uint2 *)ws.keys;
+            mk.m = nd.max_bits; mk.L = nd.log_cells;
+            const uint64_t stride = 8ull << mk.L;
+            size_t free_b = 0, total_b = 0;
+            if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); err = "hipMemGetInfo failed"; return W3_E_HIP; }
+            const uint64_t budget = std::min<uint64_t>(((uint64_t)free_b + ws.match_tables_cap) / 2, 16ull << 30);
+            const uint64_t waves = std::min<uint64_t>(std::min<uint64_t>(nb, 256 * 16), budget / stride);
+            if (waves == 0) { err = "the match tables of one block (" + std::to_string(stride) + " B) exceed the device budget"; return W3_E_NOMEM; }
+            if ((rc = tp_ensure(ws.match_tables, ws.match_tables_cap, (size_t)(waves * stride), err))) return rc;
+            mk.tables = (uint32_t *)ws.match_tables;
+            if (ev) (void)hipEventRecord(ev[2 * W3_EV_MATCH], s);
+            hipLaunchKernelGGL(w3::k_match_keys, dim3((unsigned)waves), dim3(64), 0, s, mk);
+            if (ev) { (void)hipEventRecord(ev[2 * W3_EV_MATCH + 1], s); ws.match_timed = true; }
+            pa.keys = (const uint2 *)ws.keys;
+            launch_small<true>(nd.bits - 3, dim3(grid_small), s, pa);
+            bytes += n * (1 + 8 + 8) + n * 2 * (32 + 32);   // input, keys written and read; per boundary and table one entry read and (nearly always) one stored, as 32-byte sectors
         } else if (c == LEAF_SMALL) {
             // beside a wide leaf's rank kernel (bound by its scattered stores) instead of beside the partition passes: see below
             // (Two encodes in flight — join_all: at once on the launch stream, beside the partition passes on the side stream: the first

@@ -426,8 +426,14 @@ static int parse_spec(const w3_model_spec *spec, ParsedSpec &ps) {
             // OrderN::new allocates 1<<bits counters; masks are u32/u8 (ordern.rs:35-43)
             if (nd.bits < 1 || nd.bits > 32 || nd.align > 7 || nd.align > nd.bits) return W3_E_INVALID;
             if ((int)nd.bits - (int)nd.align > 31) return W3_E_INVALID;
-            if (nd.history > W3_HIST_HUFF) return W3_E_INVALID;
+            if (nd.history > W3_HIST_MATCH) return W3_E_INVALID;
             if (nd.history == W3_HIST_AC && nd.max_bits > 32) return W3_E_INVALID;
+            if (nd.history == W3_HIST_MATCH) {   // MatchHistory(min_len = max_bits, log_slots = log_cells): w3_match_plan.h
+                if (!match_params_ok(nd.max_bits, nd.log_cells)) return W3_E_INVALID;
+                if (nd.bits != MATCH_BITS || nd.align != MATCH_ALIGN) return W3_E_UNSUPPORTED;
+                if (ps.has_match) return W3_E_UNSUPPORTED;   // a second match leaf: valid, not built
+                ps.has_match = true;
+            }
             if (nd.history == W3_HIST_HUFF) {
                 if (nd.reserved >= spec->n_huff) return W3_E_INVALID;
                 huff_used |= 1u << nd.reserved;
@@ -491,6 +497,11 @@ static uint64_t layout_generic(const ParsedSpec &ps, size_t block_size, GenericA
         }
         lp.hist_mask = (uint32_t)((1ull << (nd.bits - nd.align)) - 1ull);
         if (nd.frozen) continue;
+        if (nd.history == W3_HIST_MATCH) {   // T_m and T_2m, 2^L u32 each, right BEFORE the leaf's Counter table (match_tables, w3_generic.h)
+            lp.log_cells = nd.log_cells;
+            off += 8ull << nd.log_cells;
+            lp.tbl_off = off;
+        }
         const CounterTable t = counter_table(nd.bits, (uint64_t)block_size * 8);
         lp.use_hash = t.use_hash; lp.hash_mask = t.use_hash ? (uint32_t)(t.slots - 1) : 0u;
         off += t.use_hash ? t.hash_bytes : t.direct_bytes;
@@ -652,6 +663,15 @@ static void lane_launch(const CmArgs &ca, uint32_t cnt, hipStream_t s, bool unst
     const int nl = ca.g.n_leaves;
     int n_slot = 0;
     for (int l = 0; l < nl; l++) n_slot += ca.g.leaf[l].kind == 1;
+    bool match = false;
+    for (int l = 0; l < nl; l++) match |= ca.g.leaf[l].kind == 0 && ca.g.leaf[l].hist == W3_HIST_MATCH && !ca.g.leaf[l].frozen;   // (frozen: no context is ever formed)
+    if (match) {   // a match-model leaf: the run-time leaf loops with the MATCH flag (never the _nl forms), with or without a mixer
+        if (!n_slot && !ca.n_apm && !ca.mix.n) { hipLaunchKernelGGL((k_generic<DECODE, true>), grid, blk, 0, s, ca.g); return; }
+        void (*const staged)(CmArgs) = ca.mix.n ? k_cm_staged<DECODE, true, true> : k_cm_staged<DECODE, false, true>;
+        void (*const plain)(CmArgs) = ca.mix.n ? k_cm<DECODE, true, true> : k_cm<DECODE, false, true>;
+        hipLaunchKernelGGL(n_slot <= W3_CM_STAGED_MAX && !unstaged ? staged : plain, grid, blk, 0, s, ca);
+        return;
+    }
     if (ca.mix.n) {   // a logistic mixer over the leaves: the run-time leaf loops, by the same staged rule (never k_cm_nl / k_generic*)
         void (*const staged)(CmArgs) = k_cm_staged<DECODE, true>, (*const plain)(CmArgs) = k_cm<DECODE, true>;
         hipLaunchKernelGGL(n_slot <= W3_CM_STAGED_MAX && !unstaged ? staged : plain, grid, blk, 0, s, ca);
@@ -782,6 +802,7 @@ static void collect_timing(hipEvent_t *ev, const TwoPhaseWs &ws, bool has_apm, b
     t.n_wide = (uint32_t)std::min(ws.n_wide, 4);
     for (int w = 0; w < ws.n_wide && w < 4; w++) { t.part_ms[w] = elapsed_ev(ev, W3_EV_PART0 + w); t.rank_ms[w] = elapsed_ev(ev, W3_EV_RANK0 + w); }
     if (ws.small_timed) t.small_ms = elapsed_ev(ev, W3_EV_SMALL);
+    if (ws.match_timed) t.match_ms = elapsed_ev(ev, W3_EV_MATCH);
     t.pack_ms = packed ? elapsed_ev(ev, W3_EV_PACK) : 0.f;
     t.total_ms = elapsed_ev(ev, W3_EV_TOTAL);
 }
@@ -1680,7 +1701,7 @@ static size_t host_chunk_blocks(const w3_ctx *ctx, const ParsedSpec &ps, size_t 
 // one more piece's timing into a call's sums (n_parts counts the pieces; path and n_wide are the last piece's)
 static void timing_add(w3_timing &sum, const w3_timing &t) {
     sum.predict_ms += t.predict_ms; sum.coder_ms += t.coder_ms; sum.pack_ms += t.pack_ms; sum.generic_ms += t.generic_ms; sum.total_ms += t.total_ms;
-    sum.apm_ms += t.apm_ms; sum.slot_ms += t.slot_ms; sum.achash_ms += t.achash_ms; sum.small_ms += t.small_ms; sum.mix_ms += t.mix_ms;
+    sum.apm_ms += t.apm_ms; sum.slot_ms += t.slot_ms; sum.achash_ms += t.achash_ms; sum.small_ms += t.small_ms; sum.mix_ms += t.mix_ms; sum.match_ms += t.match_ms;
     for (int w = 0; w < 4; w++) { sum.part_ms[w] += t.part_ms[w]; sum.rank_ms[w] += t.rank_ms[w]; }
     sum.path = t.path; sum.n_wide = t.n_wide; sum.n_parts += 1;
     sum.n_coder_launches += t.n_coder_launches; sum.coder_bytes += t.coder_bytes; sum.predict_bytes += t.predict_bytes;
@@ -3458,6 +3479,7 @@ extern "C" int w3_export_counters(w3_ctx *ctx, const w3_model_spec *spec, const 
     if ((rc = parse_spec(spec, ps))) return rc;
     if (ps.n_leaves != 1 || ps.n_apm || ps.has_slot || ps.leaf[0].frozen) { ctx->err = "w3_export_counters takes ONE adaptive Counter-table leaf"; return W3_E_UNSUPPORTED; }
     const w3_node &nd = ps.leaf[0];
+    if (ps.has_match) { ctx->err = "w3_export_counters: the match-model leaf (W3_HIST_MATCH) is not exported"; return W3_E_UNSUPPORTED; }
     if (nd.bits > 28) { ctx->err = "tables above 2^28 counters are not exported"; return W3_E_UNSUPPORTED; }
     if (n > (1u << 28)) { ctx->err = "single-stream export limited to 2^28 bytes"; return W3_E_UNSUPPORTED; }
     const size_t entries = (size_t)1 << nd.bits;

@@ -150,6 +150,23 @@ class HuffHistory:
         return o
 
 
+class MatchHistory:
+    """The match model's History (W3_HIST_MATCH, include/w3hip.h): BUILD-DEFINED, integer-exact, fresh per block.
+    At every byte boundary the most recent earlier position with the same min_len- and 2 min_len-byte context is looked up in two tables of
+    2^log_slots entries; the longer verified match (at most 32 bytes, the 2 min_len context only if strictly longer) predicts its next
+    byte, and hash() is (length bucket << 1 | expected bit) while the byte agrees with it, else 0.  For OrderNEntropy(11, 3, ...) only."""
+    kind = L.W3_HIST_MATCH
+    table = [0] * 8
+
+    def __init__(self, min_len=4, log_slots=16):
+        self.min_len, self.log_slots = int(min_len), int(log_slots)
+        self.max_bits = self.min_len   # (the node field that carries it)
+
+    @classmethod
+    def new(cls, min_len=4, log_slots=16):
+        return cls(min_len, log_slots)
+
+
 class HuffCode:
     """The code table of the AC-over-Huffman driver (bin/ac-over-huffman/main.rs:74-76): canonical(package_merge(histogram(buf),
     huffman_size)), codes NOT bit-reversed, len 0 = symbol absent.  new() builds it on the host (w3_huff_code_table: histogram of the
@@ -275,6 +292,10 @@ class AdaptiveModel(Model):
         nd = _leaf(self.bits, self.align, h.kind, h.max_bits, h.table, frozen=frozen)
         if h.kind == L.W3_HIST_HUFF:
             nd.reserved = getattr(Model._tls, "huff_index", {}).get(id(h), 0)
+        if h.kind == L.W3_HIST_MATCH:
+            if not 0 <= h.log_slots <= 255:
+                raise W3Error(L.W3_E_INVALID, "u8 parameter out of range")
+            nd.log_cells = h.log_slots
         return nd
 
     def _huff_sets(self):
@@ -504,6 +525,29 @@ def order012_mix(select=LogisticMixer.ORDER0, rate=14):
 def full_cm_mix(log_cells=14):
     """full_cm()'s seven leaves under the logistic mixer, its two APM stages behind it"""
     leaves = [Order0(), Order1(), OrderN(27, 3)] + [SlotModel(order, log_cells) for order in (1, 2, 3, 4)]
+    return APM(APM(LogisticMixer(leaves), APM.ORDER0, 7), APM.ORDER1, 6)
+
+
+class MatchModel(OrderNEntropy):
+    """The match-model leaf: OrderNEntropy(11, 3, MatchHistory(min_len, log_slots)).  An over-confident leaf under a BestOfTwoModel gets
+    selected too often, so the factories below put it under the logistic mixer only."""
+
+    def __init__(self, min_len=4, log_slots=16):
+        super().__init__(11, 3, MatchHistory(min_len, log_slots))
+
+    @classmethod
+    def new(cls, min_len=4, log_slots=16):
+        return cls(min_len, log_slots)
+
+
+def order012_match_mix(select=LogisticMixer.ORDER0, rate=14):
+    """order012_mix() with the match-model leaf as the mixer's fourth input"""
+    return LogisticMixer([Order0(), Order1(), OrderN(27, 3), MatchModel()], select, rate)
+
+
+def full_cm_match_mix(log_cells=14):
+    """full_cm_mix() with the match-model leaf as the mixer's eighth input"""
+    leaves = [Order0(), Order1(), OrderN(27, 3)] + [SlotModel(order, log_cells) for order in (1, 2, 3, 4)] + [MatchModel()]
     return APM(APM(LogisticMixer(leaves), APM.ORDER0, 7), APM.ORDER1, 6)
 
 
