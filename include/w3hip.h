@@ -219,8 +219,13 @@ enum {
     W3_OPT_AOH_BATCH_BLOCKS = 14, /* test hook in the manner of W3_OPT_HOST_CHUNK_BLOCKS: most blocks per batch of the two-phase form of AC over
                            Huffman, and most jobs per batch of its ranges calls and of the sixteen-lane full decode (0 = default: as many
                            as the device memory budget holds; the output is the same) */
-    W3_OPT_EXPORT_EPOCH = 15 /* test hook in the manner of W3_OPT_AOH_BATCH_BLOCKS: bytes per epoch of w3_export_counters_device / _staged
+    W3_OPT_EXPORT_EPOCH = 15, /* test hook in the manner of W3_OPT_AOH_BATCH_BLOCKS: bytes per epoch of w3_export_counters_device / _staged
                            (0 = default; the result is the same).  A multiple of 1 KiB, at most 2^28: anything else is W3_E_INVALID */
+    W3_OPT_WAVE_GRID = 16 /* test hook in the manner of W3_OPT_AOH_BATCH_BLOCKS: most wavefronts the two wavefront-per-block kernels of the
+                           two-phase predict phase (k_match_keys of the match-model leaf, k_predict_wave of the Counter leaves no LDS kernel
+                           covers) are launched with, so that a wavefront walks several blocks over its private table (0 = default: one per
+                           block up to what the chip and the memory budget hold; the output is the same).  The sampled verification's
+                           re-prediction takes the same cap.  Negative: W3_E_INVALID.  What a call ran with: w3_last_wave_grid */
 };
 enum { W3_PATH_AUTO = 0, W3_PATH_GENERIC = 1, W3_PATH_TWOPHASE = 2,
        W3_PATH_SPEC = 3 /* reported only (w3_timing.path of the AC-over-Huffman decode and ranges calls that took the sixteen-lane decoder;
@@ -311,6 +316,13 @@ int w3_decode_ranges_device(w3_ctx *ctx, const w3_model_spec *spec, const uint8_
  *                           decode.  (The AC-over-Huffman family reports through w3_timing.path.)                                  */
 int w3_decode_spec_covers(const w3_model_spec *spec);
 int w3_last_decode_path(const w3_ctx *ctx);
+
+/* ---- how many wavefronts walked the blocks --------------------------------------------------------------------------------------
+ * out[0] / out[1]: the grids (wavefronts, each with a private table in device memory) of the k_match_keys / k_predict_wave launches
+ * of the context's most recent two-phase predict phase (an encode, w3_predict_blocks, the exports), by the sizing actually done
+ * (W3_OPT_WAVE_GRID included); 0 where that kernel was not launched, the smallest of several k_predict_wave leaves'.  The sampled
+ * verification's launches are not reported.  W3_E_INVALID for a null argument.                                                      */
+int w3_last_wave_grid(const w3_ctx *ctx, uint32_t out[2]);
 
 /* ---- integrity: CRC-32 per block, and decodes that verify it -----------------------------------------------------------------
  * The reference has no counterpart (one stream per file, no checksum: main.rs:89-144); build-defined on the block container.  An

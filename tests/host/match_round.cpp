@@ -4,7 +4,10 @@
 // lane kernels' serial order (match_advance, knowing only the bytes before the boundary), both against the serial definition written out
 // here byte by byte.  Every byte index a header load touches is asserted inside [0, known) of its block, and every block lies in a heap
 // buffer of exactly its size.  Stand-alone: tests/test_match_round.py builds it with g++, once more under -fsanitize=undefined,address,
-// and with mutant headers that must fail.
+// and with mutant headers that must fail.  One wavefront's life over mixed blocks wraps the tags; a second part walks STEERED inputs (what
+// tests/match_ref.py: tag_blocks builds for the GPU test) — the blocks at sequence 0, 255, 510 one phrase, whose table entries no other block
+// touches, so that only the re-zeroing at the wrap and the tag check keep them from passing for candidates, some of them past the boundary
+// that looks them up or past a short last block's end — and one block of 70,000 bytes whose entries hold positions above bit 16.
 // usage: match_round [blocks per shape]
 #include <cstdint>
 #include <cstdio>
@@ -66,6 +69,7 @@ static uint32_t def_key(const Pred &p, uint32_t byte, uint32_t j) {
 // ---- the kernel's walk: one wavefront, its blocks one after the other over the same two tables ------------------------------------------
 struct Wave {
     uint32_t m, L, seq = 0;
+    uint64_t stale_rejected = 0, stale_past_boundary = 0, stale_past_end = 0, zeroings = 0, far_positions = 0;
     std::vector<uint32_t> tbl;
     Wave(uint32_t m_, uint32_t L_) : m(m_), L(L_), tbl((size_t)2 << L_, 0xDEADBEEFu) {}   // (the kernel zeroes them at tag 1: garbage until then)
 
@@ -73,7 +77,7 @@ struct Wave {
         using namespace w3;
         const uint32_t tag = seq % W3_MATCH_TAGS + 1u;
         seq++;
-        if (tag == 1u) std::fill(tbl.begin(), tbl.end(), 0u);
+        if (tag == 1u) { std::fill(tbl.begin(), tbl.end(), 0u); zeroings++; }
         for (uint32_t base = 0; base < len; base += 64u) {
             uint32_t c[2][64], v[2][64];
             for (uint32_t t = 0; t < 2u; t++) {
@@ -94,6 +98,12 @@ struct Wave {
                     const int nl = match_nearest_lower(M, lane);
                     c[t][lane] = !act[lane] ? 0u : nl >= 0 ? base + (uint32_t)nl : match_entry_pos(tag, old[lane]);
                     v[t][lane] = act[lane] ? match_length(blk, len, i, c[t][lane]) : 0u;
+                    if (act[lane] && nl < 0 && old[lane] != 0u && (old[lane] >> 24) != tag) {   // an earlier block's entry: what the tag is for
+                        stale_rejected++;
+                        stale_past_boundary += (old[lane] & 0xFFFFFFu) >= i;
+                        stale_past_end += (old[lane] & 0xFFFFFFu) > len;
+                    }
+                    far_positions += c[t][lane] >= 65536u;
                 }
                 for (uint32_t lane = 0; lane < 64u; lane++) {   // the stores, after every load of the round
                     uint64_t M = 0;
@@ -144,6 +154,70 @@ static void fill(uint8_t *x, uint32_t n, uint32_t shape) {
     }
 }
 
+// ---- the steered inputs ------------------------------------------------------------------------------------------------------------------
+// bs bytes without structure, but for one stretch of 2m + 1 bytes met twice (in the second round where there is one): an equal block's
+// entry for the contexts behind it lies past the first boundary that looks it up
+static std::vector<uint8_t> phrase(uint32_t bs, uint32_t m, uint32_t seed) {
+    std::vector<uint8_t> p(bs);
+    uint32_t s = seed * 2654435761u + 1u;
+    for (uint32_t i = 0; i < bs; i++) { s = s * 1103515245u + 12345u; p[i] = (uint8_t)(s >> 16); }
+    const uint32_t r = bs <= 64u ? bs / 2u : 64u, k = 2u * m + 1u < bs - r ? 2u * m + 1u : bs - r;
+    memcpy(p.data() + r, p.data(), k);
+    return p;
+}
+static bool share_an_entry(const std::vector<uint8_t> &a, const std::vector<uint8_t> &b, uint32_t m, uint32_t L) {
+    for (uint32_t t = 0; t < 2; t++)
+        for (uint32_t i = m << t; i < a.size(); i++)
+            for (uint32_t j = m << t; j < b.size(); j++)
+                if (def_hash(a.data(), i, m << t, L) == def_hash(b.data(), j, m << t, L)) return true;
+    return false;
+}
+static void walk_one(Wave &wave, const uint8_t *src, uint32_t n, const char *what) {
+    uint8_t *x = (uint8_t *)malloc(n);   // exactly the block
+    memcpy(x, src, n);
+    const std::vector<Pred> want = definition(x, n, wave.m, wave.L);
+    wave.block(x, n, want, what);
+    free(x);
+}
+static uint64_t steered() {
+    static const uint32_t cases[4][5] = {{520, 24, 12, 2, 12}, {520, 72, 0, 2, 12}, {300, 40, 0, 4, 16}, {520, 24, 0, 2, 8}};   // blocks, size, tail, m, L
+    uint64_t blocks = 0;
+    for (const auto &cs : cases) {
+        const uint32_t nb = cs[0], bs = cs[1], tail = cs[2], m = cs[3], L = cs[4];
+        const std::vector<uint8_t> A = phrase(bs, m, 1);
+        std::vector<uint8_t> other[2];
+        for (uint32_t seed = 2, k = 0; k < 2; seed++) {
+            std::vector<uint8_t> p = phrase(bs, m, seed);
+            if (!share_an_entry(A, p, m, L)) other[k++] = p;
+        }
+        Wave wave(m, L);
+        char what[64];
+        for (uint32_t b = 0; b < nb + (tail ? 1u : 0u); b++, blocks++) {
+            const std::vector<uint8_t> &p = b % W3_MATCH_TAGS == 0 ? A : other[b & 1u];
+            snprintf(what, sizeof what, "steered %ux%u block %u", nb, bs, b);
+            walk_one(wave, p.data(), b < nb ? bs : tail, what);
+        }
+        CHECK(wave.zeroings == (nb + (tail ? 1u : 0u) - 1u) / W3_MATCH_TAGS + 1u && wave.zeroings >= 2, "steered %ux%u: %llu zeroings", nb, bs, (unsigned long long)wave.zeroings);
+        CHECK(wave.stale_rejected > nb && wave.stale_past_boundary > 0, "steered %ux%u: %llu stale entries rejected, %llu at or past the boundary", nb, bs,
+              (unsigned long long)wave.stale_rejected, (unsigned long long)wave.stale_past_boundary);
+        CHECK(!tail || wave.stale_past_end > 0, "steered %ux%u: no stale entry past the short last block's end", nb, bs);
+    }
+    // one long block: a 40-byte phrase near the start, past offset 65,536 and once more behind that
+    {
+        const uint32_t n = 70000;
+        std::vector<uint8_t> x(n);
+        for (uint32_t i = 0; i < n; i++) x[i] = (uint8_t)rnd();
+        for (uint32_t o : {66000u, 68500u}) memcpy(x.data() + o, x.data() + 100, 40);
+        Wave wave(4, 20);
+        walk_one(wave, x.data(), n, "long block");
+        CHECK(wave.far_positions > 0, "long block: no candidate at position 65,536 or above");
+        const std::vector<Pred> want = definition(x.data(), n, 4, 20);
+        serial(x.data(), n, 4, 20, want, "long block");
+        blocks++;
+    }
+    return blocks;
+}
+
 int main(int argc, char **argv) {
     const uint32_t reps = argc > 1 ? (uint32_t)atoi(argv[1]) : 3u;
     static const uint32_t sizes[] = {1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 200, 1000, 4096};
@@ -166,6 +240,7 @@ int main(int argc, char **argv) {
                 }
         CHECK(reps < 2 || wave.seq > W3_MATCH_TAGS, "the tags did not wrap: %u blocks", wave.seq);
     }
+    blocks += steered();
     // the length bucket and the rules, spelled out
     for (uint32_t v = 1; v <= 32; v++) CHECK(w3::match_lq(v) == (v < 16 ? v : 16 + (v - 16) / 4) && w3::match_lq(v) <= 20, "lq(%u)", v);
     CHECK(w3::match_nearest_lower(0x8000000000000001ull, 63) == 0 && w3::match_nearest_lower(1ull, 0) == -1 && w3::match_nearest_lower(0xFFull, 5) == 4, "nearest lower lane");

@@ -350,3 +350,179 @@ def reached(name, m, L):
     st = collections.Counter()
     keys(DIRECTED[name], m, L, states=st)
     return st
+
+
+# ---- k_match_keys' walk: one wavefront, several blocks, the same two tagged tables (csrc/w3_match.h) ------------------------------------
+TAGS = 255
+WALK_MUTANTS = ["no_tag_check", "no_rezero_at_wrap", "rezero_short_table_only", "tag_mod_256", "tag_always_one_no_rezero", "pos_16_bits"]
+WRAP_MUTANTS = ("no_rezero_at_wrap", "rezero_short_table_only")
+WALK_STATES = ["stale_tag_rejected", "stale_pos_at_or_past_boundary", "stale_pos_past_short_last_block", "entry_cleared_at_wrap_would_have_hit",
+               "long_table_only_stale", "cand_65536_or_more_back", "cand_pos_65536_or_more"]
+
+
+def _walk_len(x, i, c):
+    """match_len for a candidate that may lie anywhere (a stale entry taken for a live one): a byte outside the block is unequal"""
+    if c == 0:
+        return 0
+    n, r, limit = len(x), 0, min(CAP, c)
+    while r < limit and 0 <= i - 1 - r and c - 1 - r < n and x[i - 1 - r] == x[c - 1 - r]:
+        r += 1
+    return r
+
+
+def wave_walk(data, block_size, waves, m, L, mutant=None, states=None):
+    """-> the keys (8 per byte) of every block, as `waves` wavefronts leave them: wavefront w takes blocks w, w + waves, ... in turn over
+    its two tables, in rounds of 64 boundaries (every lane reads the tables' state before the round, a lane's candidate is the nearest
+    lower lane of the round with its hash, else the entry read; the highest lane of a group stores), entries tagged with the wavefront's
+    block sequence, both tables zeroed when the tag returns to 1.  Without a mutant this equals keys() of each block alone."""
+    assert mutant is None or mutant in WALK_MUTANTS
+    blocks = [bytes(data[o:o + block_size]) for o in range(0, len(data), block_size)]
+    out = [None] * len(blocks)
+    for w in range(min(waves, len(blocks))):
+        T = ({}, {})
+        for seq, b in enumerate(range(w, len(blocks), waves)):
+            x = blocks[b]
+            n = len(x)
+            short_last = b == len(blocks) - 1 and n < block_size
+            if mutant == "tag_always_one_no_rezero":
+                tag = 1
+            else:
+                tag = seq % (256 if mutant == "tag_mod_256" else TAGS) + 1
+            cleared = ({}, {})
+            if tag == 1 and (seq == 0 or mutant not in ("no_rezero_at_wrap", "tag_always_one_no_rezero")):
+                if seq:
+                    cleared = (dict(T[0]), dict(T[1]))
+                T[0].clear()
+                if seq == 0 or mutant != "rezero_short_table_only":
+                    T[1].clear()
+            c = [[0] * n, [0] * n]
+            v = [[0] * n, [0] * n]
+            for base in range(0, n, 64):
+                hi = min(n, base + 64)
+                for t, k in enumerate((m, 2 * m)):
+                    seen = {}   # hash -> the highest lane of the round so far
+                    for i in range(max(base, k), hi):
+                        h = ctx_hash(x, i, k, L)
+                        if h in seen:
+                            c[t][i] = seen[h]
+                        else:
+                            old = T[t].get(h, 0)
+                            live = old >> 24 == tag or mutant == "no_tag_check"
+                            c[t][i] = (old & (0xFFFF if mutant == "pos_16_bits" else 0xFFFFFF)) if live else 0
+                            if states is not None:
+                                if old and not live:
+                                    pos = old & 0xFFFFFF
+                                    states["stale_tag_rejected"] += 1
+                                    states["stale_pos_at_or_past_boundary"] += pos >= i
+                                    states["stale_pos_past_short_last_block"] += short_last and pos > n
+                                if not old and cleared[t].get(h, 0) >> 24 == tag:
+                                    states["entry_cleared_at_wrap_would_have_hit"] += 1
+                                    states["long_table_only_stale"] += t == 1
+                        seen[h] = i
+                        v[t][i] = _walk_len(x, i, c[t][i])
+                        if states is not None and c[t][i]:
+                            states["cand_65536_or_more_back"] += i - c[t][i] >= 65536
+                            states["cand_pos_65536_or_more"] += c[t][i] >= 65536
+                    for h, i in seen.items():   # the round's stores, after every load of the round
+                        T[t][h] = ((tag << 24) | i) & 0xFFFFFFFF
+            ks = []
+            for i, byte in enumerate(x):
+                t = 1 if v[1][i] > v[0][i] else 0
+                vv, cc = v[t][i], c[t][i]
+                e = x[cc] if vv and cc < n else 0
+                lq = lq_of(vv) if vv else 0
+                for j in range(8):
+                    ks.append((lq << 1) | ((e >> (7 - j)) & 1) if vv and byte >> (8 - j) == e >> (8 - j) else 0)
+            out[b] = ks
+    return out
+
+
+def stream_of_keys(block, ks):
+    """leaf_stream from given keys"""
+    x = bytes(block)
+    tbl, out = {}, []
+    for t, k in enumerate(ks):
+        ctx = 0 if t == 0 else (k << 3) | (t & 7)
+        c = tbl.get(ctx)
+        if c is None:
+            c = tbl[ctx] = Counter()
+        out.append(c.p())
+        c.update((x[t >> 3] >> (7 - (t & 7))) & 1)
+    return out
+
+
+def _phrase(block_size, m, seed):
+    """block_size bytes without structure, but for one stretch of 2m + 1 bytes met twice: both contexts of the boundary behind the
+    second occurrence hash as at the first, so an entry left by an equal block lies PAST the first boundary that looks it up (and past
+    a short last block's end); in blocks of more than 64 bytes the second occurrence is in the second round"""
+    p = bytearray(_lcg(block_size, 256, seed))
+    r = block_size // 2 if block_size <= 64 else 64
+    k = min(2 * m + 1, block_size - r)
+    p[r:r + k] = p[:k]
+    return bytes(p)
+
+
+def _hash_sets(p, m, L):
+    return tuple({ctx_hash(p, i, k, L) for i in range(k, len(p))} for k in (m, 2 * m))
+
+
+def tag_phrases(block_size, m, L):
+    """(A, B, C): A as _phrase says; B and C the first such phrases (by seed) whose context hashes are disjoint from A's, in both tables"""
+    A = _phrase(block_size, m, 1)
+    ha = _hash_sets(A, m, L)
+    others, seed = [], 2
+    while len(others) < 2:
+        p = _phrase(block_size, m, seed)
+        hp = _hash_sets(p, m, L)
+        if not (ha[0] & hp[0]) and not (ha[1] & hp[1]):
+            others.append(p)
+        seed += 1
+        assert seed < 100000, "no phrase disjoint from A"
+    return A, others[0], others[1]
+
+
+def tag_blocks(nblocks, block_size, waves, tail=0, m=2, L=12):
+    """the steered input of the tag bookkeeping: nblocks blocks for `waves` wavefronts (block b is number b // waves of wavefront b % waves)
+    plus `tail` bytes of one more.  A wavefront's blocks number 0, 255, 510, ... — where the tag is 1 again — are phrase A; all others
+    alternate between B and C, which never touch A's table entries (tag_phrases).  So A's entries of block 0 are still in the tables, under
+    tag 1, when block 255 comes: only the re-zeroing keeps them from passing for candidates.  Equal naive blocks cannot show that: each
+    block overwrites what the one before left."""
+    A, B, C = tag_phrases(block_size, m, L)
+    out = bytearray()
+    for b in range(nblocks + (1 if tail else 0)):
+        seq = b // waves
+        p = A if seq % TAGS == 0 else B if seq & 1 else C
+        out += p if b < nblocks else p[:tail]
+    return bytes(out)
+
+
+# the shapes the GPU test runs (tests/test_gpu_match_tags.py) and tests/test_match_tags_cpu.py proves sufficient: blocks, block size, the
+# wavefronts the grid is capped to, bytes of a ragged last block, (m, L)
+TAG_CASES = {
+    "520x24_tail_w1_2_12": (520, 24, 1, 12, 2, 12),
+    "1030x12_w2_2_12": (1030, 12, 2, 0, 2, 12),
+    "775x16_w3_3_12": (775, 16, 3, 0, 3, 12),
+    "300x40_w1_4_16": (300, 40, 1, 0, 4, 16),
+    "520x24_w1_2_8": (520, 24, 1, 0, 2, 8),      # 256 slots: B and C collide with each other (never with A)
+    "520x72_w1_2_12": (520, 72, 1, 0, 2, 12),    # two rounds per block: a tag that overflows its 8 bits loses the first round's entries
+}
+
+
+def tag_case(name):
+    nb, bs, waves, tail, m, L = TAG_CASES[name]
+    return tag_blocks(nb, bs, waves, tail, m, L)
+
+
+def two_block_waves(nblocks=70, block_size=24, m=2):
+    """equal blocks: with 64 wavefronts, the first nblocks - 64 of them take a second block over the entries of their first"""
+    return _phrase(block_size, m, 5) * nblocks
+
+
+def long_block(n=70000, phrase_at=(100, 66000, 68500), seed=7):
+    """one block of n bytes: filler, and a 40-byte phrase near the start, again past offset 65,536 (its candidates lie 65,536 or more
+    back) and once more behind that (its candidates' POSITIONS are 65,536 or more: bits 16 .. 23 of an entry's position field)"""
+    x = bytearray(_lcg(n, 256, seed))
+    ph = _lcg(40, 256, seed + 1)
+    for o in phrase_at:
+        x[o:o + 40] = ph
+    return bytes(x)

@@ -1,6 +1,8 @@
 """The match-model leaf's index arithmetic as the kernels compile it (weath3rb0i_amd/csrc/w3_match_plan.h: plain C++, host and device) on
 the CPU: tests/host/match_round.cpp walks blocks of every small size and several shapes in k_match_keys' round order over 64 simulated
-lanes, and in the lane kernels' serial order, against the serial definition, asserting every byte index inside the block — plainly, as a
+lanes, and in the lane kernels' serial order, against the serial definition, asserting every byte index inside the block — one
+wavefront's life over mixed blocks, then over inputs steered at the tag bookkeeping (the blocks where the tag is 1 again share no table
+entry with the others) and one block of 70,000 bytes (entry positions above bit 16) — plainly, as a
 stand-alone program under -fsanitize=undefined,address (each block in a heap buffer of exactly its size), and with headers wrong in one
 behaviour each, which the harness must catch."""
 import os
@@ -81,3 +83,16 @@ def test_the_harness_catches_a_tie_that_goes_to_the_long_context(tmp_path):
 def test_the_harness_catches_a_compare_capped_at_31(tmp_path):
     r = _run_mutant(tmp_path, "cap_31", "MATCH_CAP = 32", "MATCH_CAP = 31")
     assert r.returncode != 0 and "FAIL" in r.stderr
+
+
+@needs_gxx
+def test_the_harness_catches_an_entry_taken_whatever_its_tag(tmp_path):
+    """the tag comparison dropped from match_entry_pos: an earlier block's entry passes for a candidate"""
+    r = _run_mutant(tmp_path, "no_tag_check", "return (entry >> 24) == tag ? entry & 0xFFFFFFu : 0u;", "(void)tag; return entry & 0xFFFFFFu;")
+    assert r.returncode != 0 and "FAIL" in r.stderr
+
+
+@needs_gxx
+def test_the_harness_catches_a_position_field_of_16_bits(tmp_path):
+    r = _run_mutant(tmp_path, "pos_16_bits", "return (entry >> 24) == tag ? entry & 0xFFFFFFu : 0u;", "return (entry >> 24) == tag ? entry & 0xFFFFu : 0u;")
+    assert r.returncode != 0 and "FAIL" in r.stderr and "long block" in r.stderr

@@ -18,6 +18,7 @@ W3_OK, W3_E_INVALID, W3_E_NOSPACE, W3_E_HIP, W3_E_UNSUPPORTED, W3_E_NOMEM, W3_E_
 W3_E_CORRUPT = -7
 W3_OPT_PATH, W3_OPT_TIMING, W3_OPT_CODER, W3_OPT_ACC_LIMIT, W3_OPT_DEBUG_STAMPS, W3_OPT_VARIANT, W3_OPT_SLOT_BUDGET_MB, W3_OPT_VERIFY, W3_OPT_FAULT_BLOCK, W3_OPT_TUNE, W3_OPT_HOST_CHUNK_BLOCKS, W3_OPT_FAULT_KERNELS, W3_OPT_AOH_BATCH_BLOCKS = 1, 2, 3, 4, 5, 7, 8, 9, 10, 11, 12, 13, 14
 W3_OPT_EXPORT_EPOCH = 15
+W3_OPT_WAVE_GRID = 16
 W3_VAR_NO_LDS_ATOMICS, W3_VAR_PARTITION4, W3_VAR_NO_CHAINED_PARTITION, W3_VAR_CM_UNSTAGED, W3_VAR_NO_SIDE_STREAM, W3_VAR_INJECT_LDS_FAULT = 1, 2, 4, 8, 16, 32
 W3_VAR_HALF_CU, W3_VAR_FULL_CU = 64, 128
 W3_VAR_SLOT_TABLE, W3_VAR_SLOT_SORTED, W3_VAR_DECODE_LANE, W3_VAR_AOH_DECODE_SPEC = 256, 512, 1024, 2048
@@ -111,7 +112,7 @@ EXPORTS = [
     "w3_export_entropy_device", "w3_export_entropy_staged", "w3_export_entropy_get_profile",
     "w3_steps_layout_of", "w3_export_steps_device", "w3_export_steps_staged", "w3_export_steps_get_profile",
     "w3_encode_probs_device", "w3_encode_stats_probs_device",
-    "w3_decode_spec_covers", "w3_last_decode_path",
+    "w3_decode_spec_covers", "w3_last_decode_path", "w3_last_wave_grid",
 ]
 
 _lib = None
@@ -232,6 +233,7 @@ def load():
     lib.w3_decode_spec_covers.restype = C.c_int
     lib.w3_last_decode_path.argtypes = [vp]
     lib.w3_last_decode_path.restype = C.c_int
+    lib.w3_last_wave_grid.argtypes = [vp, C.POINTER(C.c_uint32 * 2)]
     lib.w3_rccl_library.argtypes = [C.c_char_p]
     lib.w3_rccl_status.argtypes = [C.c_char_p, sz]
     _lib = lib

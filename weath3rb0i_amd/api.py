@@ -136,6 +136,18 @@ class Context:
         most 2^28; the result is the same)."""
         self._chk(self.lib.w3_ctx_set_option(self.h, L.W3_OPT_EXPORT_EPOCH, int(nbytes)))
 
+    def set_wave_grid(self, n=0):
+        """W3_OPT_WAVE_GRID: most wavefronts the predict phase's k_match_keys and k_predict_wave launches take, so that one wavefront
+        walks several blocks over its private table (0 = default; the output is the same).  What a call ran with: last_wave_grid()."""
+        self._chk(self.lib.w3_ctx_set_option(self.h, L.W3_OPT_WAVE_GRID, int(n)))
+
+    def last_wave_grid(self):
+        """w3_last_wave_grid: (k_match_keys grid, k_predict_wave grid) of this context's most recent two-phase predict phase; 0 where
+        that kernel was not launched, the smallest of several k_predict_wave leaves'"""
+        out = (C.c_uint32 * 2)()
+        self._chk(self.lib.w3_last_wave_grid(self.h, C.byref(out)))
+        return int(out[0]), int(out[1])
+
     def set_timing(self, on=True):
         self._chk(self.lib.w3_ctx_set_option(self.h, L.W3_OPT_TIMING, int(on)))
 

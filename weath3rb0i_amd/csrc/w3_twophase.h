@@ -67,6 +67,7 @@ struct TwoPhaseOptions {
     uint32_t fault_block = 0xFFFFFFFFu;   // W3_OPT_FAULT_BLOCK (with W3_VAR_INJECT_LDS_FAULT)
     uint32_t fault_kernels = 1u;          // W3_OPT_FAULT_KERNELS: which kernels the injected fault hits (1 k_predict_small, 2 k_rank_sorted, 4 k_partition8)
     int debug_stamps = 0;      // W3_OPT_DEBUG_STAMPS
+    uint32_t wave_grid = 0;    // W3_OPT_WAVE_GRID: test hook, most wavefronts of a k_match_keys / k_predict_wave launch (0 = as many as the chip holds)
 };
 
 struct TwoPhaseWs {
@@ -116,6 +117,7 @@ struct TwoPhaseWs {
     size_t huff_redo_cap = 0;
     void *match_tables = nullptr; size_t match_tables_cap = 0;   // k_match_keys: the two candidate tables of every resident wavefront
     bool match_timed = false;           // the last predict recorded W3_EV_MATCH
+    uint32_t *last_wave_grid = nullptr; // w3_last_wave_grid: where the predict phase reports its {k_match_keys, k_predict_wave} grids (the context's), or null
     TwoPhaseOptions opt;       // the context's options as of the call being made (w3hip.hip hands them over when it prepares a call)
     uint64_t verify_calls = 0; // the call's number for the sample's rotation (w3_verify.h: counted per shape by the context)
     TwoPhaseWs *vws = nullptr; // workspace of that re-prediction (owned)
@@ -306,6 +308,8 @@ static inline int twophase_predict_a(TwoPhaseWs &ws, hipStream_t s, const Parsed
     int rc = W3_OK;
     ws.P_valid = false;
     ws.achash_timed = false; ws.match_timed = false;
+    if (ws.last_wave_grid) ws.last_wave_grid[0] = ws.last_wave_grid[1] = 0u;
+    const uint64_t wave_cap = ws.opt.wave_grid ? ws.opt.wave_grid : ~0ull;   // W3_OPT_WAVE_GRID
     const bool lds_atomics = twophase_lds_order_ok(ws, s);
     ws.used_lds_atomics = false;
     const uint32_t grid_small = std::min<uint32_t>(nb, 256 * 20);   // (KEYS leaves; the plain ones: launch_small_shaped)
@@ -398,10 +402,11 @@ static inline int twophase_predict_a(TwoPhaseWs &ws, hipStream_t s, const Parsed
             size_t free_b = 0, total_b = 0;
             if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); err = "hipMemGetInfo failed"; return W3_E_HIP; }
             const uint64_t budget = std::min<uint64_t>(((uint64_t)free_b + ws.wave_tables_cap) / 2, 80ull << 30);
-            const uint64_t waves = std::min<uint64_t>(std::min<uint64_t>(nb, 256 * 32), budget / wa.table_stride);   // latency-bound: as many wavefronts as the chip holds
+            const uint64_t waves = std::min<uint64_t>(std::min<uint64_t>(std::min<uint64_t>(nb, 256 * 32), budget / wa.table_stride), wave_cap);   // latency-bound: as many wavefronts as the chip holds
             if (waves == 0) { err = "the Counter table of one block (" + std::to_string(wa.table_stride) + " B) exceeds the device budget"; return W3_E_NOMEM; }
             if ((rc = tp_ensure(ws.wave_tables, ws.wave_tables_cap, (size_t)(waves * wa.table_stride), err))) return rc;
             wa.tables = (uint8_t *)ws.wave_tables;
+            if (ws.last_wave_grid) ws.last_wave_grid[1] = ws.last_wave_grid[1] ? std::min<uint32_t>(ws.last_wave_grid[1], (uint32_t)waves) : (uint32_t)waves;
             const bool keyed = nd.history == W3_HIST_AC || nd.history == W3_HIST_HUFF;
             if (keyed) {
                 if ((rc = tp_ensure(ws.keys32, ws.keys32_cap, n * 32, err))) return rc;
@@ -492,10 +497,11 @@ static inline int twophase_predict_a(TwoPhaseWs &ws, hipStream_t s, const Parsed
             size_t free_b = 0, total_b = 0;
             if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); err = "hipMemGetInfo failed"; return W3_E_HIP; }
             const uint64_t budget = std::min<uint64_t>(((uint64_t)free_b + ws.match_tables_cap) / 2, 16ull << 30);
-            const uint64_t waves = std::min<uint64_t>(std::min<uint64_t>(nb, 256 * 16), budget / stride);
+            const uint64_t waves = std::min<uint64_t>(std::min<uint64_t>(std::min<uint64_t>(nb, 256 * 16), budget / stride), wave_cap);
             if (waves == 0) { err = "the match tables of one block (" + std::to_string(stride) + " B) exceed the device budget"; return W3_E_NOMEM; }
             if ((rc = tp_ensure(ws.match_tables, ws.match_tables_cap, (size_t)(waves * stride), err))) return rc;
             mk.tables = (uint32_t *)ws.match_tables;
+            if (ws.last_wave_grid) ws.last_wave_grid[0] = ws.last_wave_grid[0] ? std::min<uint32_t>(ws.last_wave_grid[0], (uint32_t)waves) : (uint32_t)waves;
             if (ev) (void)hipEventRecord(ev[2 * W3_EV_MATCH], s);
             hipLaunchKernelGGL(w3::k_match_keys, dim3((unsigned)waves), dim3(64), 0, s, mk);
             if (ev) { (void)hipEventRecord(ev[2 * W3_EV_MATCH + 1], s); ws.match_timed = true; }
@@ -780,7 +786,7 @@ static inline int twophase_verify(TwoPhaseWs &ws, hipStream_t s, const ParsedSpe
     // its options: the call's variant on the ballot rounds and the call's slot budget, everything else at its default
     v.opt = TwoPhaseOptions();
     v.opt.variant = (ws.opt.variant | W3_VAR_NO_LDS_ATOMICS | W3_VAR_PARTITION4 | W3_VAR_NO_SIDE_STREAM) & ~(uint32_t)W3_VAR_INJECT_LDS_FAULT;
-    v.opt.verify = 0; v.opt.slot_budget_mb = ws.opt.slot_budget_mb;
+    v.opt.verify = 0; v.opt.slot_budget_mb = ws.opt.slot_budget_mb; v.opt.wave_grid = ws.opt.wave_grid;
     v.lds_order = 0;
     v.stretch = ws.stretch; v.squash = ws.squash; v.st = ws.st; v.huff = ws.huff;
     // only the leaves whose kernels use the property are re-predicted (not the slot-state leaves, not k_predict_wave's)

@@ -109,6 +109,7 @@ struct w3_ctx {
     int opt_timing = 0;
     w3_timing timing{};
     int last_decode_path = 0;   // w3_last_decode_path: the kernel family of the most recent w3_decode_* call (lane_run), 0 before any
+    uint32_t last_wave_grid[2] = {0u, 0u};   // w3_last_wave_grid: the {k_match_keys, k_predict_wave} grids of the most recent predict phase (twophase_predict_a)
     // workspace that is not a job's
     DevBuf tables, lens, total, io_in, io_out, coffs, misc, cm_luts, achash_luts, sweep;
     DevBuf aoh;   // AC over Huffman (w3_aoh.h): code tables in device form, configurations, block bit lengths, maxima and flags
@@ -365,6 +366,10 @@ extern "C" int w3_ctx_set_option(w3_ctx *ctx, int opt, int64_t value) {
     case W3_OPT_AOH_BATCH_BLOCKS:
         if (value < 0 || value > 0x7FFFFFFF) return W3_E_INVALID;
         ctx->aoh_batch_blocks = (uint32_t)value;
+        return W3_OK;
+    case W3_OPT_WAVE_GRID:
+        if (value < 0 || value > 0x7FFFFFFF) return W3_E_INVALID;
+        ctx->opt.wave_grid = (uint32_t)value;
         return W3_OK;
     case W3_OPT_EXPORT_EPOCH:
         if (value < 0 || value > (int64_t)W3_EXP_EPOCH_MAX || value % 1024) { ctx->err = "an export epoch is a multiple of 1 KiB, at most 2^28 bytes"; return W3_E_INVALID; }
@@ -753,6 +758,11 @@ extern "C" int w3_decode_spec_covers(const w3_model_spec *spec) {
     return decode_takes_spec(ca, 0u, 4) ? 1 : 0;
 }
 extern "C" int w3_last_decode_path(const w3_ctx *ctx) { return ctx ? ctx->last_decode_path : 0; }
+extern "C" int w3_last_wave_grid(const w3_ctx *ctx, uint32_t out[2]) {
+    if (!ctx || !out) return W3_E_INVALID;
+    out[0] = ctx->last_wave_grid[0]; out[1] = ctx->last_wave_grid[1];
+    return W3_OK;
+}
 
 // ---------------------------------------------------------------------------
 // encode (device-resident)
@@ -826,6 +836,7 @@ static void hand_options(w3_ctx *ctx, Job &J, bool two) {
     if (J.index) J.tp.opt.debug_stamps = 0;   // (w3_debug_get_stamps reads job 0's)
     J.tp.stretch = ctx->stretch; J.tp.squash = ctx->squash; J.tp.st = ctx->st;
     J.tp.lds_order = ctx->lds_order;
+    J.tp.last_wave_grid = ctx->last_wave_grid;
     if (two && ctx->lds_order < 0) { (void)twophase_lds_order_ok(J.tp, ctx->stream); ctx->lds_order = J.tp.lds_order; }
 }
 
