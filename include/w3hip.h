@@ -104,7 +104,8 @@ enum {
  *                          W3_E_UNSUPPORTED.  Otherwise an ORDERN leaf like any other (under BestOfTwo, under a MIX, APM stages
  *                          behind, frozen).  Encode: W3_PATH_TWOPHASE computes the keys with one wavefront per block (k_match_keys,
  *                          csrc/w3_match.h; w3_timing.match_ms); decode and W3_PATH_GENERIC: the lane-per-block kernels
- *                          (w3_decode_spec_covers is 0).  w3_export_counters* and w3_export_entropy_* return W3_E_UNSUPPORTED.
+ *                          (w3_decode_spec_covers is 0), or — W3_OPT_VARIANT bit 4096 — the sixteen-lane decoder ("which kernels
+ *                          decode" below).  w3_export_counters* and w3_export_entropy_* return W3_E_UNSUPPORTED.
  */
 enum { W3_NODE_ORDERN = 1, W3_NODE_BEST_OF_TWO = 2, W3_NODE_SLOT_STATE = 3, W3_NODE_APM = 4, W3_NODE_MIX = 5 };
 enum { W3_HIST_NONE = 0, W3_HIST_RAW = 1, W3_HIST_AC = 2, W3_HIST_HUFF = 3, W3_HIST_MATCH = 4 };
@@ -178,7 +179,9 @@ enum {
                            block, no table; default: the replay below 7,000 blocks, k_slot from there on), 1024 = decode on the
                            lane-per-block kernels only (default: sixteen lanes per block where k_decode_spec applies; AC over Huffman: k_aoh in
                            place of k_aoh_decode_spec), 2048 = AC over Huffman: the full decode w3_aoh_decode_blocks[_device] too runs the
-                           sixteen-lane decoder where it covers (the ranges calls do by default).  0 = defaults.
+                           sixteen-lane decoder where it covers (the ranges calls do by default), 4096 = a spec with a match-model leaf
+                           (W3_HIST_MATCH) decodes on the sixteen-lane decoder too, where the rest of the spec is covered (default: the
+                           lane kernels; "which kernels decode" below).  0 = defaults.
                            32 = FAULT INJECTION (test hook of the sampled verification): one LDS-add round of every block returns two
                            lanes each other's value (in the kernels W3_OPT_FAULT_KERNELS names); refused (W3_E_INVALID) unless
                            W3_OPT_VERIFY is on, so it cannot corrupt output */
@@ -307,14 +310,23 @@ int w3_decode_ranges_device(w3_ctx *ctx, const w3_model_spec *spec, const uint8_
  * w3_decode_blocks*, w3_decode_ranges* and their _checked forms run one of two kernel families: the sixteen-lane decoder, which
  * evaluates a nibble's whole context tree at once (csrc/w3_decode_spec.h: up to 8 leaves — Counter leaves with alignment_bits >= 2,
  * slot-state leaves — under BestOfTwo nodes or a W3_MIX_ORDER0 mixer, and at most 2 APM stages), or the lane-per-block kernels
- * (everything else, a W3_MIX_ONE mixer among it; W3_OPT_VARIANT bit 1024 asks for them by name).  The output is the same.
+ * (everything else, a W3_MIX_ONE mixer and — by default — a match-model leaf among it; W3_OPT_VARIANT bit 1024 asks for them by name,
+ * bit 4096 opts a spec with a match-model leaf into the sixteen-lane decoder).  The output is the same.
  *   w3_decode_spec_covers   host only, the twin of w3_aoh_decode_spec_covers: 1 where the sixteen-lane decoder takes a decode of this
  *                           spec under default options, 0 where the lane kernels do, the negative W3_E_* code of w3_spec_validate for
  *                           a spec that call refuses.
+ *   w3_decode_spec_covers_variant   the same answer under the W3_OPT_VARIANT bits given (no other option enters it but W3_OPT_TUNE bit 14,
+ *                           the two-bit groups, which it takes as off).  A spec with ONE live match-model leaf (W3_HIST_MATCH) is the case
+ *                           it exists for: by default such a spec decodes on the lane kernels (w3_decode_spec_covers is 0); with bit 4096
+ *                           (decode_match_spec) the sixteen-lane decoder carries the leaf — the row of sixteen lanes does match_advance
+ *                           at every byte boundary (csrc/w3_match_spec_plan.h), bit-exact with the lane kernels — wherever the rest of
+ *                           the spec is covered.  Still refused under the bit: bit 1024, W3_OPT_TUNE bit 14, a W3_MIX_ONE mixer, a
+ *                           Counter leaf with alignment_bits < 2, three APM stages.
  *   w3_last_decode_path     W3_PATH_SPEC or W3_PATH_GENERIC: the family the context's most recent call of those named above launched,
  *                           by the decision actually taken (options included); 0 before any decode.  w3_timing is not touched by a
  *                           decode.  (The AC-over-Huffman family reports through w3_timing.path.)                                  */
 int w3_decode_spec_covers(const w3_model_spec *spec);
+int w3_decode_spec_covers_variant(const w3_model_spec *spec, uint32_t variant);
 int w3_last_decode_path(const w3_ctx *ctx);
 
 /* ---- how many wavefronts walked the blocks --------------------------------------------------------------------------------------

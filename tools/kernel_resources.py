@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel register / LDS / occupancy table of libw3hip.so's kernels (hipcc -Rpass-analysis=kernel-resource-usage).
-Usage: python3 tools/kernel_resources.py [substring ...]  ->  one line per kernel whose demangled name holds a substring."""
+Usage: python3 tools/kernel_resources.py [--wide] [substring ...]  ->  one line per kernel whose demangled name holds a substring;
+--wide prints the whole name (the default cuts it at 44 characters, which hides the later template arguments of k_decode_spec)."""
 import os
 import re
 import subprocess
@@ -10,7 +11,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def main():
-    pats = sys.argv[1:]
+    wide = "--wide" in sys.argv[1:]
+    pats = [a for a in sys.argv[1:] if a != "--wide"]
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-function",
            "-Rpass-analysis=kernel-resource-usage", "-o", "/tmp/_w3res.so", os.path.join(ROOT, "weath3rb0i_amd", "csrc", "w3hip.hip")]
     cmd += os.environ.get("W3_EXTRA_FLAGS", "").split()
@@ -32,7 +34,7 @@ def main():
     for (k, v), name in zip(rows.items(), names):
         name = re.sub(r"^void ", "", name).split("(")[0]
         if not pats or any(p in name for p in pats):
-            print("%-44s vgpr %3d agpr %3d sgpr %3d lds %6d scratch %4d occ %d" % (name[:44], v.get("vgpr", -1), v.get("agpr", -1), v.get("sgpr", -1),
+            print(("%s" if wide else "%-44s") % (name if wide else name[:44]) + " vgpr %3d agpr %3d sgpr %3d lds %6d scratch %4d occ %d" % (v.get("vgpr", -1), v.get("agpr", -1), v.get("sgpr", -1),
                                                                             v.get("lds", -1), v.get("scratch", -1), v.get("occ", -1)))
 
 

@@ -22,6 +22,7 @@ W3_OPT_WAVE_GRID = 16
 W3_VAR_NO_LDS_ATOMICS, W3_VAR_PARTITION4, W3_VAR_NO_CHAINED_PARTITION, W3_VAR_CM_UNSTAGED, W3_VAR_NO_SIDE_STREAM, W3_VAR_INJECT_LDS_FAULT = 1, 2, 4, 8, 16, 32
 W3_VAR_HALF_CU, W3_VAR_FULL_CU = 64, 128
 W3_VAR_SLOT_TABLE, W3_VAR_SLOT_SORTED, W3_VAR_DECODE_LANE, W3_VAR_AOH_DECODE_SPEC = 256, 512, 1024, 2048
+W3_VAR_DECODE_MATCH_SPEC = 4096
 W3_GATHER_AUTO, W3_GATHER_RCCL, W3_GATHER_PEER_COPY = 0, 1, 2
 W3_PATH_AUTO, W3_PATH_GENERIC, W3_PATH_TWOPHASE, W3_PATH_SPEC = 0, 1, 2, 3
 
@@ -112,7 +113,7 @@ EXPORTS = [
     "w3_export_entropy_device", "w3_export_entropy_staged", "w3_export_entropy_get_profile",
     "w3_steps_layout_of", "w3_export_steps_device", "w3_export_steps_staged", "w3_export_steps_get_profile",
     "w3_encode_probs_device", "w3_encode_stats_probs_device",
-    "w3_decode_spec_covers", "w3_last_decode_path", "w3_last_wave_grid",
+    "w3_decode_spec_covers", "w3_last_decode_path", "w3_last_wave_grid", "w3_decode_spec_covers_variant",
 ]
 
 _lib = None
@@ -231,6 +232,8 @@ def load():
     lib.w3_encode_stats_probs_device.argtypes = [vp, vp, sz, sz, vp, vp, vp]
     lib.w3_decode_spec_covers.argtypes = [C.POINTER(ModelSpec)]
     lib.w3_decode_spec_covers.restype = C.c_int
+    lib.w3_decode_spec_covers_variant.argtypes = [C.POINTER(ModelSpec), C.c_uint32]
+    lib.w3_decode_spec_covers_variant.restype = C.c_int
     lib.w3_last_decode_path.argtypes = [vp]
     lib.w3_last_decode_path.restype = C.c_int
     lib.w3_last_wave_grid.argtypes = [vp, C.POINTER(C.c_uint32 * 2)]

@@ -82,20 +82,26 @@ class Context:
     def set_acc_limit(self, bits):
         self._chk(self.lib.w3_ctx_set_option(self.h, L.W3_OPT_ACC_LIMIT, bits))
 
+    @staticmethod
+    def variant_bits(names):
+        """W3_OPT_VARIANT's mask of the names set_variant takes"""
+        bits = {"no_lds_atomics": L.W3_VAR_NO_LDS_ATOMICS, "partition4": L.W3_VAR_PARTITION4, "no_chained_partition": L.W3_VAR_NO_CHAINED_PARTITION,
+                "cm_unstaged": L.W3_VAR_CM_UNSTAGED, "no_side_stream": L.W3_VAR_NO_SIDE_STREAM, "inject_lds_fault": L.W3_VAR_INJECT_LDS_FAULT,
+                "half_cu": L.W3_VAR_HALF_CU, "full_cu": L.W3_VAR_FULL_CU, "slot_table": L.W3_VAR_SLOT_TABLE, "slot_sorted": L.W3_VAR_SLOT_SORTED, "decode_lane": L.W3_VAR_DECODE_LANE,
+                "aoh_decode_spec": L.W3_VAR_AOH_DECODE_SPEC, "decode_match_spec": L.W3_VAR_DECODE_MATCH_SPEC}
+        v = 0
+        for nm in names:
+            v |= bits[nm]
+        return v
+
     def set_variant(self, *names):
         """Cross-check hook (W3_OPT_VARIANT): alternative bit-exact implementations, by name: no_lds_atomics, partition4,
         no_chained_partition, cm_unstaged, no_side_stream, half_cu (synchronous calls in the pipeline's kernel shapes), full_cu
         (submitted calls in the plain shapes), slot_table / slot_sorted (slot-state leaves on k_slot / on the sorted replay whatever
         the block count), decode_lane (decode on the lane-per-block kernels, not k_decode_spec / k_aoh_decode_spec), aoh_decode_spec (AC
-        over Huffman: the full decode too runs the sixteen-lane decoder where it covers).  No names = defaults."""
-        bits = {"no_lds_atomics": L.W3_VAR_NO_LDS_ATOMICS, "partition4": L.W3_VAR_PARTITION4, "no_chained_partition": L.W3_VAR_NO_CHAINED_PARTITION,
-                "cm_unstaged": L.W3_VAR_CM_UNSTAGED, "no_side_stream": L.W3_VAR_NO_SIDE_STREAM, "inject_lds_fault": L.W3_VAR_INJECT_LDS_FAULT,
-                "half_cu": L.W3_VAR_HALF_CU, "full_cu": L.W3_VAR_FULL_CU, "slot_table": L.W3_VAR_SLOT_TABLE, "slot_sorted": L.W3_VAR_SLOT_SORTED, "decode_lane": L.W3_VAR_DECODE_LANE,
-                "aoh_decode_spec": L.W3_VAR_AOH_DECODE_SPEC}
-        v = 0
-        for nm in names:
-            v |= bits[nm]
-        self._chk(self.lib.w3_ctx_set_option(self.h, L.W3_OPT_VARIANT, v))
+        over Huffman: the full decode too runs the sixteen-lane decoder where it covers), decode_match_spec (a model with a match-model
+        leaf decodes on the sixteen-lane decoder where the rest of it is covered; default: the lane kernels).  No names = defaults."""
+        self._chk(self.lib.w3_ctx_set_option(self.h, L.W3_OPT_VARIANT, self.variant_bits(names)))
 
     def set_verify(self, on=True):
         """W3_OPT_VERIFY: sampled ballot-round re-prediction after every predict phase that used LDS-add rounds (default on)."""
@@ -396,11 +402,16 @@ class Context:
 
     # ---- which kernels decode (include/w3hip.h "which kernels decode") ----
     @staticmethod
-    def decode_spec_covers(model):
+    def decode_spec_covers(model, variant=()):
         """w3_decode_spec_covers: whether the sixteen-lane decoder takes a decode of this model under default options (False: the
-        lane-per-block kernels do).  Host only: needs no context and no device.  A spec the library refuses raises W3Error."""
+        lane-per-block kernels do) — or, with `variant` (set_variant's names), w3_decode_spec_covers_variant: under those variant bits,
+        e.g. ("decode_match_spec",) for a model with a match-model leaf.  Host only: needs no context and no device.  A spec the
+        library refuses raises W3Error."""
         spec = model.spec() if isinstance(model, Model) else model
-        rc = L.load().w3_decode_spec_covers(C.byref(spec))
+        if variant:
+            rc = L.load().w3_decode_spec_covers_variant(C.byref(spec), Context.variant_bits(variant))
+        else:
+            rc = L.load().w3_decode_spec_covers(C.byref(spec))
         if rc < 0:
             raise W3Error(rc, "w3_decode_spec_covers: the spec is refused")
         return bool(rc)

@@ -20,8 +20,39 @@
 // below), and 0..2 APM stages.  Everything else (alignment 0 / 1: the nibble's own updates feed its later contexts; longer chains; a
 // W3_MIX_ONE mixer, whose single weight set every bit trains for the next) stays on the lane-per-block kernels, which also remain the
 // cross-check (W3_OPT_VARIANT bit 1024).
+//
+// MATCH (behind W3_OPT_VARIANT bit 4096, W3_VAR_DECODE_MATCH_SPEC; the general eight-leaf forms only): one of the leaves is the match model,
+// OrderNEntropy(11, 3, MatchHistory(m, L)) (W3_HIST_MATCH; w3_match_plan.h).  Its context at bit position j of a byte is
+// (match_key(lq, e, part, j) << 3) | j with (e, lq) fixed for the whole byte and part the byte's j known bits: for node (k, x) of a nibble
+// plain ALU on the row-uniform (e, lq) — leaf_ctx<true> on the node's history, as the lane kernels call it — into a DIRECT table of 2^11
+// Counters (never the nibble-major index, which belongs to raw histories).  Why "read everything when the nibble starts, update the path
+// afterwards" stays exact differs from the other leaves' argument:
+//   * several nodes of one level MAY read the same Counter — every node whose x disagrees with e's prefix has key 0 — but those are reads of
+//     the state before the nibble only;
+//   * the four path nodes lie on four different j, so their updates never meet, and alignment 3 keeps the two nibbles of a byte apart:
+//     fence_each is not needed for this leaf.
+// New is match_advance at every byte boundary, done by the row (w3_match_spec_plan.h; equal to the serial c = T[h]; T[h] = i over the bytes
+// decoded so far): after the byte's first nibble lane r reads T_m, T_2m at the hashes of its candidate word (history << 4) | r beside the
+// second nibble's look-ups; after the second nibble the row takes the entries of the lane whose r is the low nibble and that lane stores
+// i + 1; lane 0 stores the byte; the boundary side of the compare sits in four rolling words; ten lanes load the candidate side and e.
+// MEMORY ORDERING.  The candidate may be c = i: the compare and e then read the byte lane 0 stored an instant ago, and a table entry read by
+// one lane was stored by another lane one byte earlier.  Mechanism: the two tables and the decoded bytes are stored AND loaded with
+// agent-scope relaxed atomics (ds_st32 / ds_ld32 and their one-byte forms: global_store / global_load ... sc1) and a byte's stores are
+// drained — s_waitcnt vmcnt(0), gfx9 counts loads and stores in one counter — before the loads that may read them are issued.  This
+// rests on the microarchitecture guide's visibility table, row "__hip_atomic_load/store(.., relaxed, agent)": sc1 loads bypass the L1 and
+// are served by the L2, which the sc1 stores write through to; k_match_keys and k_predict_wave rest on the same row.  The candidate-side
+// bytes are loaded one byte per load (eight unconditional loads per lane, in flight together): an atomic load must be naturally aligned,
+// and an aligned wider load would leave [block start, block start + known) of dout, which no load here does — whatever jb.dst and jb.len.
+// The leaf's own Counter table is NOT part of that: like every direct table here it is read and written with pl_ld32 / pl_st32 and rests on
+// the argument at their definition above (one wavefront ever touches it, and its stores go through the CU's L1) — several lanes of the
+// row read a Counter that another lane stored two nibbles or more earlier, exactly as an Order0 leaf's lanes do.
+// SUPPOSED, not shown: that a store's return to vmcnt means a later sc1 load of the same wavefront sees its data in the L2 (the write is
+// acknowledged by the L2, as for the exact maps above), and that the candidate table reads of byte i + 1, issued one nibble after that
+// drain, need nothing more.  Price: one store drain and one load round trip per byte on top of the nibbles' chain; forwarding the last 32
+// bytes from the rolling words instead of loading them would take the drain off the chain and is not built.
 #pragma once
 #include "w3_cm.h"
+#include "w3_match_spec_plan.h"
 
 namespace w3 {
 
@@ -87,7 +118,7 @@ __device__ __forceinline__ void bucket_lookup16(uint32_t *tbl, uint32_t bmask, u
 // of it are decoded already).  Exact maps {ctx + 1, counts}: found, or absent (the empty slot ends the probe; only a path node claims one).
 #define W3_DS_COUNTER_LOOKUP \
                     if constexpr (RAW) ctx[l] = t_n == 0u ? 0u : ((((uint32_t)hist_n & lp[l].hist_mask) << 3) | (t_n & 7u)); \
-                    else ctx[l] = leaf_ctx(lp[l], hist_n, t_n, hs, g.huff); \
+                    else ctx[l] = leaf_ctx<MATCH>(lp[l], hist_n, t_n, hs, g.huff, &mst); \
                     uint32_t *tbl = reinterpret_cast<uint32_t *>(blk_tbl + lp[l].tbl_off); \
                     if (!lp[l].use_hash) { \
                         uint32_t idx = ctx[l]; \
@@ -165,7 +196,7 @@ __device__ __forceinline__ void bucket_lookup16(uint32_t *tbl, uint32_t bmask, u
 // path nodes train their own rows.  The first nibble of a byte touches rows 1..15, the second rows 16..255: a row is read again two nibbles
 // later at the earliest, so — as for the APM tables — no fence beyond what the leaves ask for (fence_each) is needed.  (W3_MIX_ONE has one
 // weight set: every bit's update feeds the next bit's dot product; it stays on the lane kernels.)  D = 4 only.
-template <int NL, int NA, int D, bool HS = false, bool NM = false, bool RAW = false, int KM = 0, bool MIX = false>
+template <int NL, int NA, int D, bool HS = false, bool NM = false, bool RAW = false, int KM = 0, bool MIX = false, bool MATCH = false>
 __global__ void __launch_bounds__(64) k_decode_spec(CmArgs a) {
     // RAW: every Counter leaf is live, over raw history, alignment 3, bits >= 6, and bit l of KM says whether leaf l is a slot-state leaf — all known
     // at compile time (decode_spec_all_raw / launch_decode_spec)
@@ -174,6 +205,7 @@ __global__ void __launch_bounds__(64) k_decode_spec(CmArgs a) {
     constexpr uint32_t LPB = 1u << D, BPW = 64u / LPB;        // lanes per block, blocks per wavefront
     static_assert(!HS || D == 4, "slot-state leaves: one Cell per nibble");
     static_assert(!MIX || D == 4, "the mixer's rows are disjoint over a nibble's tree");
+    static_assert(!MATCH || (D == 4 && !RAW), "the match leaf: the general forms, one boundary per two nibbles");
     __shared__ int16_t s_str[(NA > 0 || MIX) ? 4096 : 1];
     const uint16_t *s_sq = nullptr;
     if constexpr (MIX) {   // the mixer's squash table, as k_cm
@@ -225,8 +257,29 @@ __global__ void __launch_bounds__(64) k_decode_spec(CmArgs a) {
 
     uint64_t hist64 = 0; uint32_t t = 0, c0 = 1u, c1 = 0u;
     HuffState hs;
+    // MATCH: the row's MatchState (uniform in the row), the boundary side of the compare, the leaf's two candidate tables and the entries
+    // this lane read for its candidate word
+    MatchState mst;
+    MatchRowNear mnear;
+    uint32_t *mtab = nullptr, mm = 0u, mL = 0u, mcand[2] = {0u, 0u};
+    if constexpr (MATCH) {
+        const int ml = match_leaf_of(lp, g.n_leaves);   // (launched only for a spec that has one)
+        mtab = match_tables(lp[ml], blk_tbl); mm = lp[ml].max_bits; mL = lp[ml].log_cells;
+    }
     for (uint32_t i = 0; i < len; i++) {
         for (int gi = 0; gi < 8 / D; gi++) {
+            if constexpr (MATCH) {
+                // the second nibble: lane r's candidate word of boundary i + 1 and its two table entries, in flight beside the look-ups below
+                // (what boundary i stored was waited for at the end of byte i - 1)
+                if (gi == 1 && i + 1u < len) {
+                    const uint64_t wc = match_row_word(hist64, r);
+#pragma unroll
+                    for (uint32_t mt = 0; mt < 2u; mt++) {   // (unconditional loads: an entry of a table that takes no part yet is dropped)
+                        const uint32_t ent = ds_ld32(mtab + ((size_t)mt << mL) + match_hash(wc, mm << mt, mL));
+                        mcand[mt] = match_row_active(i + 1u, mm, mt) ? ent : 0u;
+                    }
+                }
+            }
             // ---- the node's prediction: contexts, Counters, mix, APM chain ----
             const uint64_t hist_n = (hist64 << k) | x;
             const uint32_t t_n = t + k;
@@ -458,7 +511,40 @@ __global__ void __launch_bounds__(64) k_decode_spec(CmArgs a) {
         const uint32_t byte = c0 & 0xFFu;
         c1 = byte; c0 = 1u;
         if (!RAW && g.n_huff) hs.push_byte(g.huff, g.n_huff, byte);
-        if (r == 0u) g.dout[off + i] = (uint8_t)byte;
+        if constexpr (MATCH) {
+            // the decoded bytes are read back by other lanes of the row: L2-level store and loads (see the header comment)
+            if (r == 0u) __hip_atomic_store(g.dout + off + i, (uint8_t)byte, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (i + 1u < len) {   // boundary i + 1 (w3_match_spec_plan.h): hist64 is its context word
+                const int sel = (int)(row0 | (byte & 15u));
+                uint32_t mc[2];
+#pragma unroll
+                for (uint32_t mt = 0; mt < 2u; mt++) {
+                    mc[mt] = (uint32_t)__shfl((int)mcand[mt], sel, 64);
+                    if (match_row_is_writer(r, byte) && match_row_active(i + 1u, mm, mt))
+                        ds_st32(mtab + ((size_t)mt << mL) + match_hash(hist64, mm << mt, mL), i + 1u);
+                }
+                // the byte (the candidate may be i: e and the compare read it) and the table entries (the next byte's sixteen candidate
+                // reads come from other lanes) have left for the L2 before any of those loads is issued
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                __builtin_amdgcn_s_waitcnt(0);
+                match_row_push(mnear, hist64);
+                const uint8_t *mblk = g.dout + off;
+                const uint32_t mine = match_row_lane_load([&](uint32_t q) -> uint32_t { return __hip_atomic_load(mblk + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); },
+                                                          mnear, i + 1u, mc[0], mc[1], r);
+                uint32_t mv[2], me[2];
+#pragma unroll
+                for (uint32_t mt = 0; mt < 2u; mt++) {
+                    uint32_t eq[4];
+#pragma unroll
+                    for (uint32_t w = 0; w < 4u; w++) eq[w] = (uint32_t)__shfl((int)mine, (int)(row0 + 4u * mt + w), 64);
+                    mv[mt] = match_row_length(eq, mc[mt]);
+                    me[mt] = (uint32_t)__shfl((int)mine, (int)(row0 + 8u + mt), 64);
+                }
+                match_row_finish(mst, mv[0], mv[1], me[0], me[1]);
+            }
+        } else {
+            if (r == 0u) g.dout[off + i] = (uint8_t)byte;
+        }
     }
 }
 
@@ -468,7 +554,13 @@ static inline bool decode_spec_has_slot(const CmArgs &ca) {
         if (ca.g.leaf[l].kind == 1) return true;
     return false;
 }
-static inline bool decode_spec_covers(const CmArgs &ca) {
+static inline bool decode_spec_has_match(const CmArgs &ca) {   // a live match-model leaf (parse_spec allows one)
+    for (int l = 0; l < ca.g.n_leaves; l++)
+        if (ca.g.leaf[l].kind == 0 && ca.g.leaf[l].hist == W3_HIST_MATCH && !ca.g.leaf[l].frozen) return true;
+    return false;
+}
+// match_spec: W3_VAR_DECODE_MATCH_SPEC is set (the MATCH instances take a spec with a match leaf; without it such a spec is refused)
+static inline bool decode_spec_covers(const CmArgs &ca, bool match_spec = false) {
     if (ca.g.n_leaves < 1 || ca.g.n_leaves > 8 || ca.n_apm > 2) return false;
     // a logistic mixer over the leaves: rows selected by the partial byte are disjoint over a nibble's tree (MIX above).  W3_MIX_ONE has a
     // single weight set, which every bit trains before the next bit's dot product reads it: the lane kernels decode it (w3_cm.h)
@@ -476,7 +568,9 @@ static inline bool decode_spec_covers(const CmArgs &ca) {
     for (int l = 0; l < ca.g.n_leaves; l++) {
         const LeafParam &lp = ca.g.leaf[l];
         if (lp.kind == 0 && !lp.frozen && lp.align < 2) return false;
-        if (lp.kind == 0 && lp.hist == W3_HIST_MATCH) return false;   // the match model: the lane kernels (DESIGN.md 7 names the follow-up)
+        // the match model: the lane kernels by default; behind the variant bit the MATCH instances take a LIVE leaf (its Counter table is
+        // direct: 2^11); a frozen one stays refused with or without the bit, as before
+        if (lp.kind == 0 && lp.hist == W3_HIST_MATCH && (!match_spec || lp.frozen || lp.use_hash)) return false;
     }
     return true;
 }
@@ -520,14 +614,14 @@ static inline void launch_decode_spec_full_cm(const CmArgs &ca, uint32_t cnt, hi
 #define W3_DECODE_NM_MIN_BLOCKS 8192u   // batches of at least this many blocks decode with the nibble-major table formats (measured: 4e8 B 462 against 490 MiB/s, 1e9 B 885 against 684)
 
 // up to eight leaves (the full CM has seven) and slot-state leaves: one instantiation with NL = 8, unused entries marked kind 2
-template <bool HS, bool NM, bool MIX = false>
+template <bool HS, bool NM, bool MIX = false, bool MATCH = false>
 static inline void launch_decode_spec_8(CmArgs ca, uint32_t cnt, hipStream_t s) {
     for (int l = ca.g.n_leaves; l < 8; l++) { ca.g.leaf[l] = LeafParam{}; ca.g.leaf[l].kind = 2; ca.g.leaf[l].frozen = 1; }
     const dim3 grid((cnt + 3u) / 4u), blk(64);
     switch (ca.n_apm) {
-    case 0: hipLaunchKernelGGL((k_decode_spec<8, 0, 4, HS, NM, false, 0, MIX>), grid, blk, 0, s, ca); break;
-    case 1: hipLaunchKernelGGL((k_decode_spec<8, 1, 4, HS, NM, false, 0, MIX>), grid, blk, 0, s, ca); break;
-    default: hipLaunchKernelGGL((k_decode_spec<8, 2, 4, HS, NM, false, 0, MIX>), grid, blk, 0, s, ca); break;
+    case 0: hipLaunchKernelGGL((k_decode_spec<8, 0, 4, HS, NM, false, 0, MIX, MATCH>), grid, blk, 0, s, ca); break;
+    case 1: hipLaunchKernelGGL((k_decode_spec<8, 1, 4, HS, NM, false, 0, MIX, MATCH>), grid, blk, 0, s, ca); break;
+    default: hipLaunchKernelGGL((k_decode_spec<8, 2, 4, HS, NM, false, 0, MIX, MATCH>), grid, blk, 0, s, ca); break;
     }
 }
 
@@ -551,6 +645,18 @@ static inline bool decode_spec_nibble_major(const CmArgs &ca, uint32_t cnt, int 
 // bits_per_group: 4 = the nibble (the shipped form), 2 = half a nibble (a tested variant)
 static inline void launch_decode_spec(const CmArgs &ca, uint32_t cnt, hipStream_t s, int bits_per_group) {
     const bool nm = decode_spec_nibble_major(ca, cnt, bits_per_group);
+    if (decode_spec_has_match(ca)) {
+        // a live match leaf (decode_takes_spec: only behind W3_VAR_DECODE_MATCH_SPEC, nibble groups): the eight-leaf forms with MATCH, whatever else the spec holds
+        const bool hs = decode_spec_has_slot(ca);
+        if (ca.mix.n) {
+            if (hs) { if (nm) launch_decode_spec_8<true, true, true, true>(ca, cnt, s); else launch_decode_spec_8<true, false, true, true>(ca, cnt, s); }
+            else { if (nm) launch_decode_spec_8<false, true, true, true>(ca, cnt, s); else launch_decode_spec_8<false, false, true, true>(ca, cnt, s); }
+        } else {
+            if (hs) { if (nm) launch_decode_spec_8<true, true, false, true>(ca, cnt, s); else launch_decode_spec_8<true, false, false, true>(ca, cnt, s); }
+            else { if (nm) launch_decode_spec_8<false, true, false, true>(ca, cnt, s); else launch_decode_spec_8<false, false, false, true>(ca, cnt, s); }
+        }
+        return;
+    }
     if (ca.mix.n) {
         // a logistic mixer (nibble groups only: lane_run keeps the two-bit-group variant on the lane kernels).  The eight-leaf forms serve every
         // covered spec; order012_mix()'s shape (three raw-history leaves) and full_cm_mix()'s have the compile-time-specialised instances of

@@ -46,7 +46,8 @@ enum { W3_VAR_NO_LDS_ATOMICS = 1, W3_VAR_PARTITION4 = 2, W3_VAR_NO_CHAINED_PARTI
        W3_VAR_SLOT_TABLE = 256  /* slot-state leaves always on k_slot (hash map in HBM, lane per block) */,
        W3_VAR_SLOT_SORTED = 512 /* slot-state leaves always on the sorted replay of w3_slot2.h (default: by block count) */,
        W3_VAR_DECODE_LANE = 1024 /* decode with the lane-per-block kernels only (k_generic_nl / k_cm_nl / k_aoh), not k_decode_spec / k_aoh_decode_spec */,
-       W3_VAR_AOH_DECODE_SPEC = 2048 /* AC over Huffman: the FULL decode too runs k_aoh_decode_spec where it covers (ranges calls do by default) */ };
+       W3_VAR_AOH_DECODE_SPEC = 2048 /* AC over Huffman: the FULL decode too runs k_aoh_decode_spec where it covers (ranges calls do by default) */,
+       W3_VAR_DECODE_MATCH_SPEC = 4096 /* a spec with a match-model leaf decodes on k_decode_spec<.., MATCH> where the rest of it is covered (default: the lane kernels) */ };
 
 #define W3_SLOT_SORTED_MAX_BLOCKS 7000u   // below: slot-state leaves by sorted replay (w3_slot2.h), from here on k_slot
 

@@ -332,7 +332,7 @@ extern "C" int w3_ctx_set_option(w3_ctx *ctx, int opt, int64_t value) {
         ctx->opt.acc_limit = (uint32_t)value;
         return W3_OK;
     case W3_OPT_VARIANT:
-        if (value < 0 || value > 4095) return W3_E_INVALID;
+        if (value < 0 || value > 8191) return W3_E_INVALID;
         // the fault-injection hook exists for the test of the sampled verification: without the verification it would only corrupt output
         if ((value & W3_VAR_INJECT_LDS_FAULT) && !ctx->opt.verify) { ctx->err = "W3_OPT_VARIANT bit 32 (fault injection) needs W3_OPT_VERIFY on"; return W3_E_INVALID; }
         ctx->opt.variant = (uint32_t)value;
@@ -699,10 +699,12 @@ struct LaneIo {
 
 // Does a decode take k_decode_spec?  Where the kernel covers the spec (decode_spec_covers), unless the lane kernels are asked for by name
 // (W3_VAR_DECODE_LANE: the cross-check) — and, for a spec with a logistic mixer, only with nibble groups: the two-bit-group variant
-// (decode_group_bits) is not built for it.  One rule for the launch, the APM tables' format (nm_tables below) and w3_decode_spec_covers.
+// (decode_group_bits) is not built for it.  A spec with a live match-model leaf is taken only where W3_VAR_DECODE_MATCH_SPEC asks for it
+// (the MATCH instances of k_decode_spec; the default stays the lane kernels), and it too only with nibble groups.  One rule for the launch,
+// the APM tables' format (nm_tables below), w3_decode_spec_covers and w3_decode_spec_covers_variant.
 static bool decode_takes_spec(const CmArgs &ca, uint32_t variant, int group_bits) {
-    if (!decode_spec_covers(ca) || (variant & W3_VAR_DECODE_LANE)) return false;
-    return !(ca.mix.n && group_bits != 4);
+    if (!decode_spec_covers(ca, (variant & W3_VAR_DECODE_MATCH_SPEC) != 0) || (variant & W3_VAR_DECODE_LANE)) return false;
+    return !((ca.mix.n || decode_spec_has_match(ca)) && group_bits != 4);
 }
 
 template <bool DECODE>
@@ -756,6 +758,14 @@ extern "C" int w3_decode_spec_covers(const w3_model_spec *spec) {
     memset(&ca, 0, sizeof ca);
     layout_lane(ps, 65536, ca);   // (the leaves' kinds and alignments, the chain, the mixer: nothing the answer reads depends on the block size)
     return decode_takes_spec(ca, 0u, 4) ? 1 : 0;
+}
+extern "C" int w3_decode_spec_covers_variant(const w3_model_spec *spec, uint32_t variant) {
+    ParsedSpec ps;
+    if (const int rc = parse_spec(spec, ps)) return rc;
+    CmArgs ca;
+    memset(&ca, 0, sizeof ca);
+    layout_lane(ps, 65536, ca);
+    return decode_takes_spec(ca, variant, 4) ? 1 : 0;
 }
 extern "C" int w3_last_decode_path(const w3_ctx *ctx) { return ctx ? ctx->last_decode_path : 0; }
 extern "C" int w3_last_wave_grid(const w3_ctx *ctx, uint32_t out[2]) {
